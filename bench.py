@@ -15,6 +15,11 @@ game ids offset by rank, no collective in the timed region (weak scaling); value
 ranks / max-over-ranks time.  Launched either by torch.distributed.run (RANK / WORLD_SIZE in the
 environment) or as plain `python bench.py --gpus N`: with WORLD_SIZE unset the script re-executes
 itself under torch.distributed.run with N ranks (self_launch), so `--gpus N` always means N ranks.
+
+A plain run (`--gpus 1 --steps K --warmup W`) is the headline alone: engine, warm-up to the steady state, K timed waves
+(tower launches timed with HIP events for `roofline`), the line.  `--full` adds everything else after it (the one-group
+leg, the headline variants, the extra configurations and training iterations, the CPU baseline; the exchange leg for
+N > 1).  `--dump-outputs DIR` writes what the timed path hands its caller as .npy files (DumpWindow).
 """
 import argparse
 import json
@@ -121,20 +126,23 @@ def mixing_warmup(game, sims, lengths=1.5):
     return int(lengths * MEAN_MOVES[game] * sims)
 
 
-def warm_up(eng, game, sims, slots, extra_waves=0, lengths=1.5):
+def warm_up(eng, game, sims, slots, extra_waves=0, lengths=1.5, keep=None):
     """Steps the phase until it is in the steady state mixing_warmup describes, whatever the schedule: a lock-step wave is one simulation
     per slot, a free-running one about two, so the warm-up is counted in SIMULATIONS (mixing_warmup x slots) and stepped in chunks.
     lengths: mean game lengths to play first.  1.5 (rounds 2-5) leaves the batch lumpy -- the 4096 games that started together still
     end in bunches, and network evaluations per simulation swing between 0.41 and 0.49 with the period of a game (profiles/r6/
     drift_lock_step.jsonl), i.e. +-10 % of throughput depending on WHEN a short window looks; after ~2.5 game lengths the swing is
-    below 2 %.  The headline and its variants use 3, the extra blocks (their windows are not the driver's 20 waves) keep 1.5."""
+    below 2 %.  The headline and its variants use 3, the extra blocks (their windows are not the driver's 20 waves) keep 1.5.
+    keep: called with every az_selfplay_collect result the warm-up drains (--dump-outputs picks its games out of them)."""
     target = (mixing_warmup(game, sims, lengths) + sims // 2) * slots
     waves = 0
 
     def drain():
         # the games that end are queued for az_selfplay_collect; a refill-forever phase nobody collects grows that queue by 64 B per move
         # -- and the reallocation of a 20 MB vector inside a 20-wave timed region is a 7 ms stall (seen once in three runs): collect and drop
-        eng.selfplay_collect(2 * slots)
+        r = eng.selfplay_collect(2 * slots)
+        if keep is not None:
+            keep(r)
     while eng.selfplay_stats().simulations < target:
         eng.selfplay_step(500)
         waves += 500
@@ -144,6 +152,85 @@ def warm_up(eng, game, sims, slots, extra_waves=0, lengths=1.5):
         waves = extra_waves
         drain()
     return waves
+
+
+# --dump-outputs: what the headline's self-play path hands its caller -- az_selfplay_collect's game and move records (include/azhip.h)
+GAME_DT = np.dtype([("game_id", "<i4"), ("slot", "<i4"), ("num_moves", "<i4"), ("first_move", "<i4"), ("nodes", "<i8"),
+                    ("total_simulations", "<i8"), ("total_nodes_traversed", "<i8"), ("final_key", "<u8", 2)])
+MOVE_DT = np.dtype([("key", "<u8", 2), ("N", "<i4", 10), ("action", "<i4"), ("reward", "<f4")])
+DUMP_GAMES = 256
+DUMP_MAX_BYTES = 64 << 20
+
+
+class DumpWindow:
+    """--dump-outputs: the records of DUMP_GAMES consecutive game ids [lo, hi) of the headline's phase.  With reset_every 1 every
+    record of a game depends on its id alone -- not on the slot that plays it nor on the wave it ends in -- so two
+    runs with the same arguments write the same arrays, whatever the interleaving of the slots.  The window sits where the games
+    end that are expected to end just before the timed steps do (a function of the arguments only): the warm-up's drains keep the
+    ones that end earlier, and after the timed region the phase is stepped on, untimed, until the rest have ended."""
+
+    def __init__(self, first_id, game, sims, slots, steps, warmup, lock_step):
+        spw = 1.0 if lock_step else 2.0                              # simulations per slot and wave (free-running: ~2)
+        warm = max((mixing_warmup(game, sims, HEADLINE_WARMUP_GAME_LENGTHS) + sims // 2) * slots, warmup * slots * spw)
+        ended = int((warm + steps * slots * spw) / (sims * MEAN_MOVES[game]))
+        self.lo = first_id + max(0, ended - DUMP_GAMES)
+        self.hi = self.lo + DUMP_GAMES
+        self.games, self.moves = {}, {}
+
+    def keep(self, r):
+        games, moves, ng, nm = r
+        assert memoryview(games).itemsize == GAME_DT.itemsize and memoryview(moves).itemsize == MOVE_DT.itemsize
+        g = np.frombuffer(memoryview(games).cast("B"), dtype=GAME_DT, count=ng)
+        m = np.frombuffer(memoryview(moves).cast("B"), dtype=MOVE_DT, count=nm)
+        for i in np.nonzero((g["game_id"] >= self.lo) & (g["game_id"] < self.hi))[0]:
+            f, n = int(g["first_move"][i]), int(g["num_moves"][i])
+            self.games[int(g["game_id"][i])] = g[i:i + 1].copy()
+            self.moves[int(g["game_id"][i])] = m[f:f + n].copy()
+
+    def missing(self, aborted=()):
+        return [i for i in range(self.lo, self.hi) if i not in self.games and i not in aborted]
+
+    def collect(self, eng, slots, timed_games, max_waves=100000):
+        """after the timed steps: the games they ended, then more waves until every game of the window has ended (or was aborted)"""
+        self.keep(eng.selfplay_collect(2 * slots + timed_games))
+        waves = 0
+        while True:
+            aborted = set(eng.selfplay_aborted())
+            if not self.missing(aborted):
+                return waves, len(aborted & set(range(self.lo, self.hi)))
+            if waves >= max_waves:
+                raise RuntimeError("--dump-outputs: games %s of the window did not end within %d waves after the timed steps" % (self.missing(aborted)[:8], waves))
+            eng.selfplay_step(200)
+            waves += 200
+            self.keep(eng.selfplay_collect(2 * slots))
+
+    def write(self, eng, out_dir):
+        """DIR/<name>.npy, float64 where an integer needs more than float32's 24 bits (game ids, node counts, 32-bit words of the
+        state keys); move_policy / move_value = the network's answer at every recorded position (az_net_evaluate_keys, the tower
+        and heads of the timed path: every root was a leaf the network evaluated)"""
+        ids = sorted(self.games)
+        g = np.concatenate([self.games[i] for i in ids]) if ids else np.zeros(0, GAME_DT)
+        m = np.concatenate([self.moves[i] for i in ids]) if ids else np.zeros(0, MOVE_DT)
+        if len(m):
+            P, V = eng.net_evaluate_keys(m["key"])
+        else:
+            P, V = np.zeros((0, eng.num_actions), np.float32), np.zeros(0, np.float32)
+
+        def words(k):
+            k = np.ascontiguousarray(k, dtype=np.uint64)
+            return np.stack([k & np.uint64(0xffffffff), k >> np.uint64(32)], axis=-1).reshape(len(k), -1).astype(np.float64)
+        arrays = {"game_id": g["game_id"].astype(np.float64), "game_num_moves": g["num_moves"].astype(np.float32),
+                  "game_nodes": g["nodes"].astype(np.float64), "game_final_key": words(g["final_key"]),
+                  "move_game_id": np.repeat(g["game_id"], g["num_moves"]).astype(np.float64), "move_key": words(m["key"]),
+                  "move_visits": m["N"].astype(np.float32), "move_action": m["action"].astype(np.float32),
+                  "move_reward": m["reward"].astype(np.float32), "move_policy": np.asarray(P, np.float32), "move_value": np.asarray(V, np.float32)}
+        nbytes = sum(a.nbytes for a in arrays.values())
+        assert nbytes <= DUMP_MAX_BYTES, nbytes
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+        return {"dir": out_dir, "game_ids": [self.lo, self.hi], "games": len(ids), "positions": int(len(m)), "bytes": nbytes,
+                "files": sorted(n + ".npy" for n in arrays)}
 
 
 def steady_block(azhip, dev_index, label, game, slots, groups, sims, hp, waves, bf16=False, note=None, max_moves=0):
@@ -676,18 +763,28 @@ def main():
     ap.add_argument("--sims", type=int, default=400)
     ap.add_argument("--groups", type=int, default=1, help="slot groups = num_workers / batch_size: 1 (default since round 5) = one network launch per wave for all 4096 slots (batch_size 4096, BASELINE's 'batch 4096'); 2 = two interleaved half-batches, the tree kernels of one under the network of the other -- the better form while every leaf went to the network (rounds 1-4: 4.9 vs 4.85 M sims/s), the worse one since the evaluation cache answers ~40 %% of the leaves and a half-batch no longer fills the chip (8.0 vs 8.5 M sims/s, profiles/r5)")
     ap.add_argument("--lock-step", action="store_true", help="az_engine_cfg.lock_step = 1: the schedule of rounds 1-5 (one simulation per slot and wave, moves in rounds)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the headline variants (2000-wave run, evaluation cache off, lock step: ~30 s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra configurations (whole phase, C3, C4 Mancala, bf16 10x128, 128 workers) reported under `extra`")
-    ap.add_argument("--no-iteration", action="store_true", help="skip extra.iteration (one whole training iteration at the reference's shipped Connect-Four parameters, ~1-2 min)")
-    ap.add_argument("--iteration", action="store_true", help="run ONLY the headline and extra.iteration (skips the other extras and the CPU baseline)")
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else the benchmark measures (~5 min): the one-group leg (roofline_kernel_alone, "
+                    "roofline_tree), the headline variants, the extra configurations, the training iterations, the CPU baseline, and for N > 1 the exchange leg "
+                    "(gather); the --no-* switches below skip parts of it.  Without it a run is the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the self-play records of a fixed window of %d game ids of the headline's "
+                    "phase and the network's answers at their positions as DIR/<name>.npy (float32 / float64; rank 0): the same arrays for the same "
+                    "arguments, run after run (DumpWindow)" % DUMP_GAMES)
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the headline variants (2000-wave run, evaluation cache off, lock step: ~30 s)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra configurations (whole phase, C3, C4 Mancala, bf16 10x128, 128 workers) reported under `extra`")
+    ap.add_argument("--no-iteration", action="store_true", help="with --full: skip extra.iteration (one whole training iteration at the reference's shipped Connect-Four parameters, ~1-2 min)")
+    ap.add_argument("--iteration", action="store_true", help="run ONLY the headline and extra.iteration (skips the other extras and the CPU baseline; implies --full)")
     ap.add_argument("--backend", default="gloo", help="torch.distributed backend of the RENDEZVOUS for N > 1: a barrier, two scalar reductions and the 128-byte RCCL id are all that goes through it, so gloo (CPU) is the default and the process holds exactly ONE RCCL instance, the one libazhip.so loads for az_comm_*; nccl = torch's bundled RCCL as well")
-    ap.add_argument("--headline-only", action="store_true", help="only the timed region (no one-group leg, no extras, no CPU baseline): the run whose rocprofv3 kernel stats are comparable with roofline.avg_launch_ms (profiles/r4/bench_headline_kernel_stats.csv)")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: only the timed region (no one-group leg, no extras, no CPU baseline) -- what a run without --full does: the run whose rocprofv3 kernel stats are comparable with roofline.avg_launch_ms (profiles/r4/bench_headline_kernel_stats.csv)")
     ap.add_argument("--no-prof", action="store_true", help="do not wrap launches in HIP events")
     ap.add_argument("--prof-all", action="store_true", help="time every kernel class (default: only the dominant kernel, k_tower)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.iteration:
+        args.full = True
+    if not args.full:
+        args.headline_only = True                                    # a plain run: set up, warm up, the timed steps, the line
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args.gpus)                                       # does not return
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != args.gpus:
@@ -733,6 +830,10 @@ def main():
     dev_name, ncu, hbm = eng.device_info()
     eng.selfplay_begin(-1, first_game_id=rank * (1 << 24))
     trace("engine ready (%d slots, %d group(s)), world %d" % (args.slots, args.groups, world))
+    window = None
+    if args.dump_outputs and rank == 0:
+        window = DumpWindow(rank * (1 << 24), azhip.GAME_CONNECT_FOUR, args.sims, args.slots, args.steps, args.warmup,
+                            args.lock_step or os.environ.get("AZHIP_FREE_RUN") == "0")
 
     def barrier():
         if dist is not None:
@@ -740,7 +841,8 @@ def main():
 
     # steady state whatever --warmup says: the state of a LONG phase -- slots at every stage of a game, the evaluation cache
     # holding what earlier games left in it -- not 4096 games in lock step through the same opening (mixing_warmup)
-    warm = warm_up(eng, azhip.GAME_CONNECT_FOUR, args.sims, args.slots, extra_waves=args.warmup, lengths=HEADLINE_WARMUP_GAME_LENGTHS)
+    warm = warm_up(eng, azhip.GAME_CONNECT_FOUR, args.sims, args.slots, extra_waves=args.warmup, lengths=HEADLINE_WARMUP_GAME_LENGTHS,
+                   keep=window.keep if window is not None else None)
     s0 = eng.selfplay_stats()
     trace("warm-up done (%d waves)" % warm)
     if not args.no_prof:
@@ -779,14 +881,22 @@ def main():
         c = torch.tensor([sims, evals, trav, moves, reused], dtype=torch.float64, device=red_dev)
         dist.all_reduce(c, op=dist.ReduceOp.SUM)
         sims, evals, trav, moves, reused = [float(x) for x in c.tolist()]
+    dumped = None
+    if window is not None:
+        # not part of the timed region: the window's games that had not ended yet end in waves stepped here
+        trace("dump: games %d..%d" % (window.lo, window.hi - 1))
+        waves_after, aborted = window.collect(eng, args.slots, s1.games - s0.games)
     eng.selfplay_end()
+    if window is not None:
+        dumped = dict(window.write(eng, args.dump_outputs), waves_after_timed=waves_after, aborted_games=aborted)
+        trace("dump written: %s" % json.dumps(dumped))
     eng.close()                        # frees its ~10 GB before the extra legs build their own engine
 
     # After the timed region (N > 1): the exchange step of the path -- every rank plays a short bounded phase device-only
     # and az_comm_gather_push all-gathers the records over RCCL straight into every rank's device replay memory
     # (simulate_distributed's fetch + push_trace!, src/simulations.jl:280-289, src/memory.jl:74-87).  Not part of `value`.
     gather, gather_hung = None, False
-    if dist is not None and not os.environ.get("AZ_BENCH_NO_GATHER"):
+    if dist is not None and args.full and not os.environ.get("AZ_BENCH_NO_GATHER"):
         # the headline number must survive a failing or hanging extra leg: it runs on a helper thread with a deadline
         box = {}
 
@@ -834,7 +944,10 @@ def main():
             "unique_leaf_frac": (evals - reused) / max(evals, 1),
             # simulations a slot completes per wave (= per launch of the tree kernel): 1 in lock step
             "sims_per_slot_per_wave": sims / max(slot_launches * (world if dist is not None else 1), 1),
+            "full": args.full,
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if prof is not None:
             out["roofline"] = tower_roofline(azhip.GAME_CONNECT_FOUR, hp, False, eng_kernel, prof["tower"], local_evals, local_elapsed)
             out["roofline"]["kernel_ms_per_step"] = out["roofline"]["exclusive_ms"] / args.steps

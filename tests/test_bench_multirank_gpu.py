@@ -1,4 +1,5 @@
-"""bench.py's N > 1 path as the driver launches it (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`),
+"""bench.py's N > 1 path as the driver launches it (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`;
+the exchange leg runs with --full),
 rehearsed on the ONE GPU of the test box: two ranks share cuda:0 and the library's exchange runs over the test-only transport
 (AZHIP_RCCL_LIB -> tests/rccl_stub; RCCL itself refuses two ranks per device).  What it proves: the rendezvous over gloo, the
 barrier + max-over-ranks timing, the summed counters, and the exchange leg after the timed region (weights broadcast, device-only
@@ -36,7 +37,8 @@ def test_two_ranks_on_one_gpu_print_one_line_with_the_gather_leg(tmp_path):
     env = dict(os.environ, AZHIP_RCCL_LIB=stub, HSA_ENABLE_IPC_MODE_LEGACY="0")
     port = 29000 + os.getpid() % 900
     rc, so, se = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                       "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--slots", "512"], env, tmp_path)
+                       "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--slots", "512",
+                       "--full"], env, tmp_path)
     lines = [ln for ln in so.splitlines() if ln.startswith("{")]
     assert rc == 0 and len(lines) == 1, so[-2000:] + se[-2000:]                                # rank 0 prints ONE line
     d = json.loads(lines[0])
@@ -50,14 +52,15 @@ def test_two_ranks_on_one_gpu_print_one_line_with_the_gather_leg(tmp_path):
 
 
 def test_plain_bench_with_gpus_2_launches_two_ranks_itself(tmp_path):
-    """`python bench.py --gpus 2` exactly as a driver without a launcher calls it: the script re-executes itself under
+    """`python bench.py --gpus 2 --full` as a driver without a launcher calls it: the script re-executes itself under
     torch.distributed.run with two ranks (stub transport on the one GPU) and rank 0 prints ONE line with n_gpus = 2."""
     stub = os.path.join(ROOT, "tests", "rccl_stub", "librccl_stub.so")
     if not os.path.exists(stub):
         subprocess.check_call(["make", "-C", os.path.dirname(stub)])
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(AZHIP_RCCL_LIB=stub, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    rc, so, se = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--slots", "512"], env, tmp_path)
+    rc, so, se = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--slots", "512", "--full"],
+                      env, tmp_path)
     lines = [ln for ln in so.splitlines() if ln.startswith("{")]
     assert rc == 0 and len(lines) == 1, so[-2000:] + se[-2000:]
     d = json.loads(lines[0])
