@@ -7,54 +7,17 @@ products accumulate in fp32 inside v_mfma_f32_16x16x32_bf16, folded batch norm /
       rounding boundary;
   (b) against the fp32 network (the CPU oracle): the documented bf16 tolerance, 4e-2 on P and 8e-2 on V for 10-block
       random networks (bf16 keeps 8 significant bits; errors grow with depth).
+With networks whose bf16 arithmetic is exact the same emulation is held to 1e-5: tests/test_net_bf16_exact_gpu.py.
 Self-play with a bf16 network is deterministic and well-formed; it is not comparable move for move with the fp32 oracle."""
 import numpy as np
 import pytest
-import torch
 
 import azref as R
-from azhip.network import ResNetHP, random_params, split_params
+from azhip.network import ResNetHP, random_params
+from exact_nets import torch_forward_bf16      # the emulation of the scheme (also used on exact networks, tests/test_net_bf16_exact_gpu.py)
 from test_net import batch_of, random_positions
 
 pytestmark = pytest.mark.gpu
-
-
-def bf16(x):
-    return x.to(torch.bfloat16).to(torch.float64)
-
-
-def torch_forward_bf16(game, hp, blob, X, A):
-    p = {k: torch.tensor(np.ascontiguousarray(v), dtype=torch.float64) for k, v in split_params(game, hp, blob).items()}
-
-    def conv(x, W, b, pad, round_w):
-        w = W.flip(0, 1).permute(3, 2, 1, 0).contiguous()
-        return torch.nn.functional.conv2d(x, bf16(w) if round_w else w, None, padding=pad), b
-
-    def bn(xb, pre):
-        x, b = xb
-        g, be, mu, var = (p[pre + "." + k].to(torch.float32) for k in ("gamma", "beta", "mean", "var"))
-        scale = g / torch.sqrt(var + torch.tensor(1e-5, dtype=torch.float32))            # the kernels fold in fp32
-        shift = (b.to(torch.float32) - mu) * scale + be
-        s = (1, -1, 1, 1)
-        return x * scale.to(torch.float64).view(s) + shift.to(torch.float64).view(s)
-
-    x = torch.tensor(X, dtype=torch.float64)
-    x = bf16(torch.relu(bn(conv(x, p["stem.conv.W"], p["stem.conv.b"], 1, False), "stem.bn")))      # the stem stays fp32, its output is stored in bf16
-    for b in range(hp.num_blocks):
-        y = bf16(torch.relu(bn(conv(x, p["block%d.conv1.W" % b], p["block%d.conv1.b" % b], 1, True), "block%d.bn1" % b)))
-        y = bn(conv(y, p["block%d.conv2.W" % b], p["block%d.conv2.b" % b], 1, True), "block%d.bn2" % b)
-        x = bf16(torch.relu(y + x))
-    N = x.shape[0]
-    hp_ = torch.relu(bn(conv(x, p["phead.conv.W"], p["phead.conv.b"], 0, True), "phead.bn")).to(torch.float32).to(torch.float64).reshape(N, -1)
-    logits = hp_ @ p["phead.dense.W"].T + p["phead.dense.b"]
-    pol = torch.softmax(logits, dim=1)
-    hv = torch.relu(bn(conv(x, p["vhead.conv.W"], p["vhead.conv.b"], 0, True), "vhead.bn")).to(torch.float32).to(torch.float64).reshape(N, -1)
-    v1 = torch.relu(hv @ p["vhead.dense1.W"].T + p["vhead.dense1.b"])
-    val = torch.tanh(v1 @ p["vhead.dense2.W"].T + p["vhead.dense2.b"]).reshape(N)
-    A = torch.tensor(A, dtype=torch.float64)
-    pm = pol * A
-    sp = pm.sum(dim=1, keepdim=True)
-    return (pm / (sp + float(np.finfo(np.float32).eps))).numpy(), val.numpy()
 
 
 @pytest.mark.parametrize("game,nblocks,F,n,tower", [(R.C4, 10, 128, 40, "16"), (R.C4, 10, 128, 9, "3"), (R.C4, 5, 64, 37, ""),
