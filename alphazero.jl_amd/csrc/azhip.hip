@@ -441,6 +441,7 @@ extern "C" int az_engine_create(const az_engine_cfg* c, az_engine** out) {
     memset(&e->net, 0, sizeof e->net);
     memset(&e->net16, 0, sizeof e->net16);
     { const char* tw = getenv("AZHIP_TOWER"); e->tower_pick = tw ? atoi(tw) : 0; }
+    { const char* mx = getenv("AZHIP_TOWER_MIXED"); e->tower_mixed = mx && atoi(mx) != 0; }
     { const char* hd = getenv("AZHIP_HEADS"); e->heads_pick = hd ? atoi(hd) : 0; }
     { const char* ep = getenv("AZHIP_XCH_EPOCH0"); e->xch_epoch = ep ? strtoull(ep, nullptr, 0) : 0; }   // tests: start k_tower16s' launch epoch near its 24-bit wrap
     { hipDeviceProp_t pr; HIPCHK(hipGetDeviceProperties(&pr, c->device)); e->num_cu = pr.multiProcessorCount; }
@@ -643,6 +644,48 @@ static void pack_conv(const float* Wt, int ksz, int Cin, int Cout, int CoutPad, 
   }
 }
 
+// Flux conv weight (as pack_conv) -> k_tower16 B-fragment order (16x16x4 MFMA): lane l of step s = 4 sq + q supplies input channel c = (g&1)*F/2 + 2s + (g>>1),
+// g = l >> 4, for output column ct*16 + (l & 15).  ksz = 3: a tower layer, 1: the concatenated head convolution
+static void pack_conv16(const float* Wt, int ksz, int F, float* dst /* [ntap][F/16 col tiles][F/16][64][4] */) {
+  const int ntap = ksz * ksz, CT = F / 16;
+  for (int t = 0; t < ntap; ++t) {
+    int dy = ksz == 3 ? t / 3 - 1 : 0, dx = ksz == 3 ? t % 3 - 1 : 0;
+    int wi = ksz == 3 ? 1 - dx : 0, wj = ksz == 3 ? 1 - dy : 0;
+    for (int ct = 0; ct < CT; ++ct) for (int sq = 0; sq < CT; ++sq) for (int ln = 0; ln < 64; ++ln) for (int q = 0; q < 4; ++q) {
+      int s = 4 * sq + q, g = ln >> 4, ci = (g & 1) * (F / 2) + 2 * s + (g >> 1), co = ct * 16 + (ln & 15);
+      dst[((((size_t)t * CT + ct) * CT + sq) * 64 + ln) * 4 + q] = Wt[(size_t)wi + (size_t)ksz * (wj + (size_t)ksz * (ci + (size_t)F * co))];
+    }
+  }
+}
+static uint16_t to_bf16(float f) {                                   // round to nearest even
+  uint32_t u; memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
+  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+// Flux conv weight -> k_tower16b B-fragment order (bf16, 16x16x32 MFMA): lane l of k step ks supplies input channels ks*32 + (l >> 4)*8 + el, el = 0..7,
+// for output column ct*16 + (l & 15)
+static void pack_conv16b(const float* Wt, int ksz, int F, uint16_t* dst /* [ntap][F/16 col tiles][F/32 k steps][64][8] */) {
+  const int ntap = ksz * ksz, CT = F / 16, KSB = F / 32;
+  for (int t = 0; t < ntap; ++t) {
+    int dy = ksz == 3 ? t / 3 - 1 : 0, dx = ksz == 3 ? t % 3 - 1 : 0;
+    int wi = ksz == 3 ? 1 - dx : 0, wj = ksz == 3 ? 1 - dy : 0;
+    for (int ct = 0; ct < CT; ++ct) for (int ks = 0; ks < KSB; ++ks) for (int ln = 0; ln < 64; ++ln) for (int el = 0; el < 8; ++el) {
+      int ci = ks * 32 + (ln >> 4) * 8 + el, co = ct * 16 + (ln & 15);
+      dst[((((size_t)t * CT + ct) * KSB + ks) * 64 + ln) * 8 + el] = to_bf16(Wt[(size_t)wi + (size_t)ksz * (wj + (size_t)ksz * (ci + (size_t)F * co))]);
+    }
+  }
+}
+// a packed piece of the network goes to the device (released by the next az_net_set_params)
+template <class T, class P> static int net_upload(az_engine* e, const std::vector<T>& h, const P** d) {
+  T* q = nullptr;
+  AZCHK(dalloc(e, &q, h.size(), false));
+  e->allocs.pop_back();
+  e->net_allocs.push_back(q);
+  HIPCHK(hipMemcpyAsync(q, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, e->stream));
+  *d = (const P*)q;
+  return AZ_OK;
+}
+
 static int ec_empty(az_engine* e, bool wipe = false);
 extern "C" int az_net_set_params(az_engine* e, const float* blob, int64_t n) {
   ENGINE(e);
@@ -674,23 +717,14 @@ extern "C" int az_net_set_params(az_engine* e, const float* blob, int64_t n) {
     bn_fold(w + (size_t)9 * F * F, w + (size_t)9 * F * F + F, F, conv_ss.data() + (size_t)l * 2 * F, conv_ss.data() + (size_t)l * 2 * F + F);
     w += (size_t)9 * F * F + 5 * F;
   }
-  // k_tower16 fragments (16x16x4 MFMA): lane l of step s = 4 sq + q supplies channel c = (g&1)*32 + 2s + (g>>1),
-  // g = l >> 4, for output column ct*16 + (l & 15)
+  // k_tower16 fragments (pack_conv16) and its stem
   std::vector<float> c16_w(4), s16_w(4);
   const int CT = F / 16;                     // column tiles = waves = float4 of B per tap and lane
+  const float* const wc0 = blob + (size_t)9 * C * F + 5 * F;        // the first tower layer
+  const size_t layer_w = (size_t)9 * F * F + 5 * F, layer16 = (size_t)9 * CT * CT * 64 * 4;
   {
-    c16_w.assign((size_t)2 * nb * 9 * CT * CT * 64 * 4 + 4, 0.0f);
-    const float* wc = blob + (size_t)9 * C * F + 5 * F;
-    for (int l = 0; l < 2 * nb; ++l) {
-      for (int t = 0; t < 9; ++t) {
-        int dy = t / 3 - 1, dx = t % 3 - 1, wi = 1 - dx, wj = 1 - dy;
-        for (int ct = 0; ct < CT; ++ct) for (int sq = 0; sq < CT; ++sq) for (int ln = 0; ln < 64; ++ln) for (int q = 0; q < 4; ++q) {
-          int s = 4 * sq + q, g = ln >> 4, ci = (g & 1) * (F / 2) + 2 * s + (g >> 1), co = ct * 16 + (ln & 15);
-          c16_w[(((((size_t)l * 9 + t) * CT + ct) * CT + sq) * 64 + ln) * 4 + q] = wc[wi + 3 * (wj + 3 * (ci + (size_t)F * co))];
-        }
-      }
-      wc += (size_t)9 * F * F + 5 * F;
-    }
+    c16_w.assign(layer16 * 2 * nb + 4, 0.0f);
+    for (int l = 0; l < 2 * nb; ++l) pack_conv16(wc0 + layer_w * l, 3, F, c16_w.data() + layer16 * l);
     const int KK = 9 * C, K2s = (KK + 1) / 2, NS = (2 * K2s + 3) / 4;
     s16_w.assign((size_t)CT * NS * 64, 0.0f);
     for (int ct = 0; ct < CT; ++ct) for (int s = 0; s < NS; ++s) for (int ln = 0; ln < 64; ++ln) {
@@ -700,28 +734,12 @@ extern "C" int az_net_set_params(az_engine* e, const float* blob, int64_t n) {
       s16_w[((size_t)ct * NS + s) * 64 + ln] = blob[wi + 3 * (wj + 3 * (ci + (size_t)C * co))];
     }
   }
-  // k_tower16b fragments (bf16, 16x16x32 MFMA): lane l of k step ks supplies input channels ks*32 + (l >> 4)*8 + e, e = 0..7,
-  // for output column ct*16 + (l & 15); values rounded to nearest even
-  auto to_bf16 = [](float f) -> uint16_t {
-    uint32_t u; memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-  };
+  // k_tower16b fragments (pack_conv16b)
   std::vector<uint16_t> c16b_w(8), h16b_w(8);
-  const int KSB = F / 32;
+  const size_t layer16b = (size_t)9 * CT * (F / 32) * 64 * 8;
   if (c.net_bf16) {
-    c16b_w.assign((size_t)2 * nb * 9 * CT * KSB * 64 * 8 + 8, 0);
-    const float* wc = blob + (size_t)9 * C * F + 5 * F;
-    for (int l = 0; l < 2 * nb; ++l) {
-      for (int t = 0; t < 9; ++t) {
-        int dy = t / 3 - 1, dx = t % 3 - 1, wi = 1 - dx, wj = 1 - dy;
-        for (int ct = 0; ct < CT; ++ct) for (int ks = 0; ks < KSB; ++ks) for (int ln = 0; ln < 64; ++ln) for (int el = 0; el < 8; ++el) {
-          int ci = ks * 32 + (ln >> 4) * 8 + el, co = ct * 16 + (ln & 15);
-          c16b_w[(((((size_t)l * 9 + t) * CT + ct) * KSB + ks) * 64 + ln) * 8 + el] = to_bf16(wc[wi + 3 * (wj + 3 * (ci + (size_t)F * co))]);
-        }
-      }
-      wc += (size_t)9 * F * F + 5 * F;
-    }
+    c16b_w.assign(layer16b * 2 * nb + 8, 0);
+    for (int l = 0; l < 2 * nb; ++l) pack_conv16b(wc0 + layer_w * l, 3, F, c16b_w.data() + layer16b * l);
   }
   // heads: concatenate the two 1x1 convolutions along the output channel
   std::vector<float> hw((size_t)F * HF, 0.0f), hb(HF, 0.0f), hbn((size_t)4 * HF, 0.0f), head_w((size_t)(HF / 32) * (F / 8) * 64 * 4), head_ss(2 * HF);
@@ -743,16 +761,10 @@ extern "C" int az_net_set_params(az_engine* e, const float* blob, int64_t n) {
   }
   pack_conv(hw.data(), 1, F, HF, HF, head_w.data());
   std::vector<float> h16_w((size_t)CT * CT * 64 * 4, 0.0f);
-  for (int ct = 0; ct < CT; ++ct) for (int sq = 0; sq < CT; ++sq) for (int ln = 0; ln < 64; ++ln) for (int q = 0; q < 4; ++q) {
-    int s = 4 * sq + q, g = ln >> 4, ci = (g & 1) * (F / 2) + 2 * s + (g >> 1), co = ct * 16 + (ln & 15);
-    h16_w[((((size_t)ct) * CT + sq) * 64 + ln) * 4 + q] = hw[ci + (size_t)F * co];
-  }
+  pack_conv16(hw.data(), 1, F, h16_w.data());
   if (c.net_bf16) {
-    h16b_w.assign((size_t)CT * KSB * 64 * 8, 0);
-    for (int ct = 0; ct < CT; ++ct) for (int ks = 0; ks < KSB; ++ks) for (int ln = 0; ln < 64; ++ln) for (int el = 0; el < 8; ++el) {
-      int ci = ks * 32 + (ln >> 4) * 8 + el, co = ct * 16 + (ln & 15);
-      h16b_w[((((size_t)ct) * KSB + ks) * 64 + ln) * 8 + el] = to_bf16(hw[ci + (size_t)F * co]);
-    }
+    h16b_w.assign((size_t)CT * (F / 32) * 64 * 8, 0);
+    pack_conv16b(hw.data(), 1, F, h16b_w.data());
   }
   bn_fold(hb.data(), hbn.data(), HF, head_ss.data(), head_ss.data() + HF);
   // dense layers, k-major with k = p*nf + f; Flux Dense W[out + nout*(p + P*f)]
@@ -802,62 +814,32 @@ extern "C" int az_net_set_params(az_engine* e, const float* blob, int64_t n) {
   for (void* q : e->net_allocs) (void)hipFree(q);
   e->net_allocs.clear();
   e->net_loaded = false;
-  auto up = [&](const std::vector<float>& h, const float** d) -> int {
-    float* q = nullptr;
-    AZCHK(dalloc(e, &q, h.size(), false));
-    e->allocs.pop_back();
-    e->net_allocs.push_back(q);
-    HIPCHK(hipMemcpyAsync(q, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    *d = q;
-    return AZ_OK;
-  };
   NetDev nd;
   memset(&nd, 0, sizeof nd);
   nd.nblocks = nb; nd.F = F; nd.npf = npf; nd.nvf = nvf; nd.HF = HF;
-  const float* tmp = nullptr;
-  AZCHK(up(stem_w, &nd.stem_w)); AZCHK(up(stem_ss, &nd.stem_ss));
-  AZCHK(up(conv_w, &tmp)); nd.conv_w = (const float4*)tmp;
-  AZCHK(up(conv_ss, &nd.conv_ss));
-  AZCHK(up(head_w, &tmp)); nd.head_w = (const float4*)tmp;
-  AZCHK(up(head_ss, &nd.head_ss));
-  AZCHK(up(pol_w, &nd.pol_w)); AZCHK(up(pol_b, &nd.pol_b)); AZCHK(up(val_w, &nd.val_w)); AZCHK(up(val_b, &nd.val_b)); AZCHK(up(val2_w, &nd.val2_w));
+  AZCHK(net_upload(e, stem_w, &nd.stem_w)); AZCHK(net_upload(e, stem_ss, &nd.stem_ss));
+  AZCHK(net_upload(e, conv_w, &nd.conv_w)); AZCHK(net_upload(e, conv_ss, &nd.conv_ss));
+  AZCHK(net_upload(e, head_w, &nd.head_w)); AZCHK(net_upload(e, head_ss, &nd.head_ss));
+  AZCHK(net_upload(e, pol_w, &nd.pol_w)); AZCHK(net_upload(e, pol_b, &nd.pol_b)); AZCHK(net_upload(e, val_w, &nd.val_w)); AZCHK(net_upload(e, val_b, &nd.val_b)); AZCHK(net_upload(e, val2_w, &nd.val2_w));
   nd.val2_b = *v2b;
-  AZCHK(up(hd_w, &tmp)); nd.hd_w = (const float2*)tmp;
+  AZCHK(net_upload(e, hd_w, &nd.hd_w));
   nd.hd_ok = hd_ok ? 1 : 0;
-  AZCHK(up(hd16_w, &tmp)); nd.hd16_w = (const float4*)tmp;
+  AZCHK(net_upload(e, hd16_w, &nd.hd16_w));
   nd.hd16_ok = hd16_ok ? 1 : 0;
   Net16Dev n16;
   memset(&n16, 0, sizeof n16);
-  {
-    n16.nblocks = nb;
-    AZCHK(up(s16_w, &n16.stem_w)); n16.stem_ss = nd.stem_ss;
-    AZCHK(up(c16_w, &tmp)); n16.conv_w = (const float4*)tmp; n16.conv_ss = nd.conv_ss;
-    AZCHK(up(h16_w, &tmp)); n16.head_w = (const float4*)tmp; n16.head_ss = nd.head_ss;
-    for (int k = 0; k < 3; ++k) n16.geo[k] = e->d_geo[k];
-    n16.geo[3] = e->d_geo[5];
-    n16.geo[4] = e->d_geo[6];
-  }
+  n16.nblocks = nb;
+  AZCHK(net_upload(e, s16_w, &n16.stem_w)); n16.stem_ss = nd.stem_ss;
+  AZCHK(net_upload(e, c16_w, &n16.conv_w)); n16.conv_ss = nd.conv_ss;
+  AZCHK(net_upload(e, h16_w, &n16.head_w)); n16.head_ss = nd.head_ss;
+  memcpy(n16.geo, e->d_geo, sizeof n16.geo);
   e->net16 = n16;
-  {
-    Net16bDev nbd;
-    memset(&nbd, 0, sizeof nbd);
-    nbd.nblocks = nb; nbd.stem_w = n16.stem_w; nbd.stem_ss = n16.stem_ss; nbd.conv_ss = n16.conv_ss; nbd.head_ss = n16.head_ss;
-    for (int k = 0; k < 3; ++k) nbd.geo[k] = e->d_geo[k];
-    nbd.geo[2] = e->d_geo[3];                                        // bf16 tower: [2] = the 22-tile geometry (8 Connect-Four boards per workgroup)
-    if (c.net_bf16) {
-      auto up16 = [&](const std::vector<uint16_t>& h, const bf16x8v** d) -> int {
-        uint16_t* q = nullptr;
-        AZCHK(dalloc(e, &q, h.size(), false));
-        e->allocs.pop_back();
-        e->net_allocs.push_back(q);
-        HIPCHK(hipMemcpyAsync(q, h.data(), h.size() * sizeof(uint16_t), hipMemcpyHostToDevice, e->stream));
-        *d = (const bf16x8v*)q;
-        return AZ_OK;
-      };
-      AZCHK(up16(c16b_w, &nbd.conv_w)); AZCHK(up16(h16b_w, &nbd.head_w));
-    }
-    e->net16b = nbd;
-  }
+  Net16bDev nbd;
+  memset(&nbd, 0, sizeof nbd);
+  nbd.nblocks = nb; nbd.stem_w = n16.stem_w; nbd.stem_ss = n16.stem_ss; nbd.conv_ss = n16.conv_ss; nbd.head_ss = n16.head_ss;
+  memcpy(nbd.geo, e->d_geo, sizeof nbd.geo);
+  if (c.net_bf16) { AZCHK(net_upload(e, c16b_w, &nbd.conv_w)); AZCHK(net_upload(e, h16b_w, &nbd.head_w)); }
+  e->net16b = nbd;
   HIPCHK(hipStreamSynchronize(e->stream));
   e->net = nd;
   e->net_loaded = true;
@@ -893,6 +875,17 @@ static bool split_gave_up(az_engine* e) {
   e->stats.tower_fallbacks++;
   return true;
 }
+// One launch of the network seam on the engine's stream, m boards: from_planes ? d_X / d_A : the states in d_tmp_env (count in d_ntmp).
+// Launched once more if the split tower gave up.
+static int seam_launch(az_engine* e, bool from_planes, int m) {
+  auto launch = [&]() -> int {
+    return from_planes ? net_launch(e, e->stream, true, e->d_hfeat, nullptr, nullptr, nullptr, m, e->d_X, e->d_A, e->d_P, e->d_V, e->d_Pinv, e->gi.A)
+                       : net_launch(e, e->stream, false, e->d_hfeat, e->d_tmp_env, e->d_iota, e->d_ntmp, m, nullptr, nullptr, e->d_P, e->d_V, nullptr, e->gi.A);
+  };
+  AZCHK(launch());
+  if (split_gave_up(e)) AZCHK(launch());
+  return AZ_OK;
+}
 
 extern "C" int az_net_forward(az_engine* e, const float* X, const float* A, int32_t N, float* P, float* V, float* Pinv) {
   ENGINE(e);
@@ -904,8 +897,7 @@ extern "C" int az_net_forward(az_engine* e, const float* X, const float* A, int3
     int m = std::min(e->nn_cap, N - off);
     HIPCHK(hipMemcpyAsync(e->d_X, X + xs * off, sizeof(float) * xs * m, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->d_A, A + (size_t)gi.A * off, sizeof(float) * gi.A * m, hipMemcpyHostToDevice, e->stream));
-    AZCHK(net_launch(e, e->stream, true, e->d_hfeat, nullptr, nullptr, nullptr, m, e->d_X, e->d_A, e->d_P, e->d_V, e->d_Pinv, gi.A));
-    if (split_gave_up(e)) AZCHK(net_launch(e, e->stream, true, e->d_hfeat, nullptr, nullptr, nullptr, m, e->d_X, e->d_A, e->d_P, e->d_V, e->d_Pinv, gi.A));
+    AZCHK(seam_launch(e, true, m));
     HIPCHK(hipMemcpyAsync(P + (size_t)gi.A * off, e->d_P, sizeof(float) * gi.A * m, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipMemcpyAsync(V + off, e->d_V, sizeof(float) * m, hipMemcpyDeviceToHost, e->stream));
     if (Pinv) HIPCHK(hipMemcpyAsync(Pinv + off, e->d_Pinv, sizeof(float) * m, hipMemcpyDeviceToHost, e->stream));
@@ -925,8 +917,7 @@ static int evaluate_envs(az_engine* e, const std::vector<GEnv>& envs, std::vecto
     int m = std::min(e->nn_cap, N - off);
     HIPCHK(hipMemcpyAsync(e->d_tmp_env, envs.data() + off, sizeof(GEnv) * m, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->d_ntmp, &m, sizeof(int), hipMemcpyHostToDevice, e->stream));
-    AZCHK(net_launch(e, e->stream, false, e->d_hfeat, e->d_tmp_env, e->d_iota, e->d_ntmp, m, nullptr, nullptr, e->d_P, e->d_V, nullptr, gi.A));
-    if (split_gave_up(e)) AZCHK(net_launch(e, e->stream, false, e->d_hfeat, e->d_tmp_env, e->d_iota, e->d_ntmp, m, nullptr, nullptr, e->d_P, e->d_V, nullptr, gi.A));
+    AZCHK(seam_launch(e, false, m));
     HIPCHK(hipMemcpyAsync(P.data() + (size_t)gi.A * off, e->d_P, sizeof(float) * gi.A * m, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipMemcpyAsync(V.data() + off, e->d_V, sizeof(float) * m, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -949,8 +940,7 @@ extern "C" int az_net_evaluate_keys(az_engine* e, const uint64_t* keys, int32_t 
     float* hP = e->h_pv; float* hV = e->h_pv + (size_t)gi.A * e->nn_cap;
     HIPCHK(hipMemcpyAsync(e->d_tmp_env, envs, sizeof(GEnv) * m, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->d_ntmp, e->h_n, sizeof(int), hipMemcpyHostToDevice, e->stream));
-    AZCHK(net_launch(e, e->stream, false, e->d_hfeat, e->d_tmp_env, e->d_iota, e->d_ntmp, m, nullptr, nullptr, e->d_P, e->d_V, nullptr, gi.A));
-    if (split_gave_up(e)) AZCHK(net_launch(e, e->stream, false, e->d_hfeat, e->d_tmp_env, e->d_iota, e->d_ntmp, m, nullptr, nullptr, e->d_P, e->d_V, nullptr, gi.A));
+    AZCHK(seam_launch(e, false, m));
     HIPCHK(hipMemcpyAsync(hP, e->d_P, sizeof(float) * gi.A * m, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipMemcpyAsync(hV, e->d_V, sizeof(float) * m, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));

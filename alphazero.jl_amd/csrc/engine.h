@@ -58,6 +58,21 @@ inline bool game_info(int gid, GameInfo* gi) {
 }
 
 // ------------------------------------------------------------------------------- engine
+// The tower forms.  The values are the AZHIP_TOWER numbers (az_engine::tower_pick); net_impl.h holds one descriptor per form
+// (kernel, layout, geometry table, availability, name, tower_hist bucket) and pick_tower, which chooses among them.
+enum TowerForm : int {
+  TW_AUTO = 0,     // AZHIP_TOWER unset: pick_tower chooses per launch
+  TW_SPLIT = 2,    // k_tower16s: two workgroups per board tile (fp32, 128 filters, where the pairs can be co-resident)
+  TW_NTS = 3,      // k_tower16 / k_tower16b with the game's latency tile count NTS
+  TW_NTM = 7,      // k_tower16 with the game's exact-fit tile count NTM (fp32, games that have one)
+  TW_11 = 16,      // k_tower16 / k_tower16b with 11 row tiles
+  TW_P19 = 19,     // k_tower16x2 with 10 + 9 row tiles (fp32, 64 filters)
+  TW_P21C = 20,    // k_tower16x2c: 11 + 10 row tiles within 176 registers (fp32, 64 filters)
+  TW_P21 = 21,     // k_tower16x2 with 11 + 10 row tiles (fp32, 64 filters)
+  TW_B22 = 22,     // k_tower16b with 22 row tiles (bf16, 128 filters)
+  TW_32 = 32,      // k_tower (32x32x2 MFMA, every tap; fp32)
+  TW_MIXED = -1    // k_tower16x2m: not an AZHIP_TOWER value -- wave_net_f launches it where AZHIP_TOWER_MIXED allows
+};
 // AZ_MAX_GROUPS: tree.h
 struct ProfRec { hipEvent_t a = nullptr, b = nullptr; int cls = 0; };
 struct az_engine {
@@ -110,13 +125,12 @@ struct az_engine {
   NetDev net;
   Net16bDev net16b;              // bf16 fragments (cfg.net_bf16)
   Net16Dev net16;                // k_tower16 fragments (64 filters)
-  uint16_t* d_geo[7];            // [6]: the 19-tile paired form (k_tower16x2<.., 10, 9>); [0..5]: Geo16 tables of the 11-tile, 3-tile and 21-tile tower kernels (resnet16.h), [3]: 22 tiles (k_tower16b, 8 boards), [4]: 6 tiles (k_conv16_layer of the trainer at small batches), [5]: the exact-fit variant (NTM<Game> tiles), if the game has one
-  int nts;                       // row tiles of the game's latency tower variant (NTS<Game>, resnet16.h)
-  int ntm;                       // row tiles of the game's exact-fit variant (NTM<Game>), 0 = none
+  uint16_t* d_geo[GEO_COUNT];    // Geo16 tables by GeoSlot (resnet16.h); GEO_NTM is NULL where the game has no exact-fit variant
   long long tower_hist[4];       // network launches served by: the split tower, the 3-row-tile form, the packed 11 / 21-tile forms, others (AZHIP_TRACE_ARENA)
   char last_tower[96];           // name of the tower kernel that served the most recent network launch (az_net_last_kernel)
   int heads_pick;                // AZHIP_HEADS=16|32 forces k_heads16 / k_heads_mfma; 0 = by launch size
-  int tower_pick;                // AZHIP_TOWER=16|32|3|21|22|7 forces a tower kernel (3 = k_tower16 with 3 row tiles, 21 = k_tower16x2, 7 = the exact-fit variant NTM); 0 = choose per launch
+  int tower_pick;                // AZHIP_TOWER = a TowerForm value (2 | 3 | 7 | 16 | 19 | 20 | 21 | 22 | 32) forces that form where it exists; 0 = choose per launch
+  bool tower_mixed;              // AZHIP_TOWER_MIXED=1: a free-running wave of 15 .. 16 boards per CU goes out as one k_tower16x2m launch (measured slower: wave_net_f)
   int num_cu;
   int nn_cap;
   float* d_hfeat; float* d_X; float* d_A; float* d_P; float* d_V; float* d_Pinv;
@@ -213,7 +227,7 @@ inline int prof_begin(az_engine* e, hipStream_t st, int cls, int64_t units) {
   r.cls = cls;
   e->prof.launches[cls] += 1;
   e->prof.units[cls] += units;
-  e->prof.exec_units[cls] += (double)units * e->next_exec;          // the tower launches set next_exec (tower_exec_frac); everything else counts in full
+  e->prof.exec_units[cls] += (double)units * e->next_exec;          // the tower launches set next_exec (the form's frac(), net_impl.h); everything else counts in full
   e->next_exec = 1.0;
   HIPCHK(hipEventRecord(r.a, st));
   return AZ_OK;

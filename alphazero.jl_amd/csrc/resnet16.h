@@ -23,6 +23,20 @@
 #include "resnet.h"
 
 
+// The row permutation tables (Geo16 below) of an engine, one per tile count in use.  This is the ONE index space of az_engine::d_geo,
+// Net16Dev::geo and Net16bDev::geo; every layout struct names its slot (T16 / T16P / T16B ::GEO) and upload, kernels and the trainer
+// index with that.  The order is free but for GEO_22: k_tower16b<.., 22> is at its scalar-register limit, and with its table next to
+// Net16bDev::dbg in the kernel arguments it keeps the register allocation it was measured with.
+enum GeoSlot {
+  GEO_11,      // 11 tiles: k_tower16 / k_tower16b / k_conv16_layer
+  GEO_NTS,     // the game's latency variant (NTS tiles), k_tower16s
+  GEO_21,      // the paired form, 11 + 10 tiles
+  GEO_6,       // 6 tiles: k_conv16_layer of the trainer at small batches (Connect-Four: NTM = 6, its table is GEO_NTM's)
+  GEO_NTM,     // the game's exact-fit variant (NTM tiles); no table where the game has none
+  GEO_19,      // the paired form, 10 + 9 tiles
+  GEO_22,      // 22 tiles: k_tower16b at 128 filters
+  GEO_COUNT
+};
 struct Net16Dev {
   int nblocks;
   const float* stem_w;      // [4 col tiles][K2s steps][64] : W[k(4s + g)][col]
@@ -31,7 +45,7 @@ struct Net16Dev {
   const float* conv_ss;     // [2*nblocks][2][64]
   const float4* head_w;     // [4 col tiles][4][64] float4
   const float* head_ss;     // [2][64]
-  const uint16_t* geo[5];   // row permutation tables (Geo16: pos [RPAD], nbr [9][RPAD]) of the 11-tile, 3-tile and 21-tile kernels, [3]: the exact-fit variant (NTM), [4]: the 19-tile paired form
+  const uint16_t* geo[GEO_COUNT];   // row permutation tables (Geo16: pos [RPAD], nbr [9][RPAD]), one per GeoSlot: a kernel reads net.geo[T::GEO] of its layout T
   unsigned long long* dbg;  // optional [workgroups][8] s_memtime stamps (az_debug_tower_timeline): 0 start, 1 stem done, 2 tower done, 3 features written; layer 2: 6 start, 4 convolution done, 5 barrier passed, 7 epilogue done
 };
 // ---------------------------------------------------------------------------------------------------------------
@@ -223,6 +237,18 @@ template <class Gm, int NTILES, int TBOARDS> struct Geo16 {
   static constexpr Tab tab = best();
 };
 
+// row tiles of the latency variant: 3 (one Connect-Four board, 5 Tic-tac-toe, 3 Mancala), or what one board needs (9x9: 6)
+template <class Gm> constexpr int NTS = Gm::P <= 48 ? 3 : (Gm::P + 15) / 16;
+// (r4) row tiles of the EXACT-FIT variant: the smallest tile count (4 .. 10) whose rows are a whole number of boards -- no
+// padding rows and, for the slot counts of the BASELINE configurations, a whole number of workgroups per CU: Mancala 7 tiles =
+// 112 rows = 8 boards (8192 slots = 1024 workgroups = 4 per CU; the 11-tile form: 12 boards of 176 rows, 683 workgroups = 2.67
+// per CU), Tic-tac-toe 9 tiles = 16 boards.  0 = the game has none (Connect-Four's is the paired 21-tile kernel).
+// (r5) A game without one (Connect-Four: 42 positions) gets the HALF-SIZE form instead -- 6 tiles = 96 rows = 2 boards + 12 padding
+// rows: since the evaluation cache answers part of every wave, a launch holds 1000 ... 1600 boards instead of 2048 / 4096, and what
+// a launch costs is set by the CU with the most boards: with 4-board workgroups that is 8 boards wherever 256 CUs share more than
+// 1024, with 2-board workgroups 6 (pick_tower prices both with the launch size the device reported for the last waves).
+template <class Gm> constexpr int ntm_of() { for (int nt = 4; nt <= 10; ++nt) if ((16 * nt) % Gm::P == 0) return nt; return Gm::P == 42 ? 6 : 0; }
+template <class Gm> constexpr int NTM = ntm_of<Gm>();
 // NT = row tiles per workgroup: 11 (throughput: 4 Connect-Four boards, 2 workgroups per CU at 64 filters) or 3
 // (latency: ONE Connect-Four board per workgroup, so a small batch spreads over 4x as many CUs and the
 // sequential layer chain of a workgroup is 3.7x shorter -- the reference's 128-worker configurations).
@@ -241,6 +267,8 @@ template <class Gm, int F = 64, int NT = 11> struct T16 {
   static constexpr int SQ = F / 16;                  // float4 of B per tap and lane
   using Game = Gm;
   using Geo = Geo16<Gm, NTILE, TB>;
+  static constexpr GeoSlot GEO = NT == 11 ? GEO_11 : NT == NTS<Gm> ? GEO_NTS : NT == NTM<Gm> ? GEO_NTM : GEO_6;
+  static_assert(GEO != GEO_6 || NT == 6, "no table slot for this tile count");
   static constexpr int FILT = F;
 };
 // Paired geometry (k_tower16x2, 64 filters): TWO sets of F/16 wavefronts share one LDS buffer of 21 row tiles =
@@ -263,6 +291,8 @@ template <class Gm, int F = 64, int NT0_ = 11, int NT1_ = 10> struct T16P {
   static constexpr int KH = F / 64, SQ = F / 16;
   using Game = Gm;
   using Geo = Geo16<Gm, NTW, TB>;
+  static constexpr GeoSlot GEO = NT0 == 11 ? GEO_21 : GEO_19;
+  static_assert(NTW == 21 || NTW == 19, "no table slot for this tile count");
   static constexpr int FILT = F;
 };
 
@@ -413,18 +443,6 @@ __device__ __forceinline__ void conv16p(const float* __restrict__ buf, const uin
 }
 
 template <int F> struct T16Threads { static constexpr int V = 64 * (F / 16); };
-// row tiles of the latency variant: 3 (one Connect-Four board, 5 Tic-tac-toe, 3 Mancala), or what one board needs (9x9: 6)
-template <class Gm> constexpr int NTS = Gm::P <= 48 ? 3 : (Gm::P + 15) / 16;
-// (r4) row tiles of the EXACT-FIT variant: the smallest tile count (4 .. 10) whose rows are a whole number of boards -- no
-// padding rows and, for the slot counts of the BASELINE configurations, a whole number of workgroups per CU: Mancala 7 tiles =
-// 112 rows = 8 boards (8192 slots = 1024 workgroups = 4 per CU; the 11-tile form: 12 boards of 176 rows, 683 workgroups = 2.67
-// per CU), Tic-tac-toe 9 tiles = 16 boards.  0 = the game has none (Connect-Four's is the paired 21-tile kernel).
-// (r5) A game without one (Connect-Four: 42 positions) gets the HALF-SIZE form instead -- 6 tiles = 96 rows = 2 boards + 12 padding
-// rows: since the evaluation cache answers part of every wave, a launch holds 1000 ... 1600 boards instead of 2048 / 4096, and what
-// a launch costs is set by the CU with the most boards: with 4-board workgroups that is 8 boards wherever 256 CUs share more than
-// 1024, with 2-board workgroups 6 (pick_tower prices both with the launch size the device reported for the last waves).
-template <class Gm> constexpr int ntm_of() { for (int nt = 4; nt <= 10; ++nt) if ((16 * nt) % Gm::P == 0) return nt; return Gm::P == 42 ? 6 : 0; }
-template <class Gm> constexpr int NTM = ntm_of<Gm>();
 
 // What a workgroup does after it has written a layer's outputs (its own channels) into the activation buffer.
 // NoXch: the workgroup owns every channel -- a barrier.
@@ -696,7 +714,7 @@ k_tower16(Net16Dev net, const GEnv* __restrict__ leaf_env, const int* __restrict
   const int n = FROM_PLANES ? n_fixed : *n_eval_ptr;
   const int board0 = blockIdx.x * T::TB;
   if (board0 >= n) return;
-  tower16_fill<T, FROM_PLANES>(buf, planes, nbr, pos, net.geo[NT == 11 ? 0 : NT == NTS<Gm> ? 1 : 3], leaf_env, eval_slots, X, n, board0, threadIdx.x);
+  tower16_fill<T, FROM_PLANES>(buf, planes, nbr, pos, net.geo[T::GEO], leaf_env, eval_slots, X, n, board0, threadIdx.x);
   __syncthreads();
   tower16_wave<T, FROM_PLANES, NT, 0>(net, buf, planes, nbr, pos, threadIdx.x >> 6, threadIdx.x & 63, n, board0, hfeat);
 }
@@ -717,16 +735,15 @@ __device__ __forceinline__ void tower16x2_body(const Net16Dev& net, const GEnv* 
   if (wave < T::CT) tower16_wave<T, FROM_PLANES, T::NT0, 0>(net, buf, planes, nbr, pos, wave, lane, n, board0, hfeat);
   else tower16_wave<T, FROM_PLANES, T::NT1, T::NT0>(net, buf, planes, nbr, pos, wave - T::CT, lane, n, board0, hfeat);
 }
-// base = index of the launch's first board
 template <class Gm, int F, bool FROM_PLANES, int NT0 = 11, int NT1 = 10>
 __global__ void __launch_bounds__(2 * T16Threads<F>::V, 1)
 k_tower16x2(Net16Dev net, const GEnv* __restrict__ leaf_env, const int* __restrict__ eval_slots,
-            const int* __restrict__ n_eval_ptr, int n_fixed, const float* __restrict__ X, float* __restrict__ hfeat, int base) {
+            const int* __restrict__ n_eval_ptr, int n_fixed, const float* __restrict__ X, float* __restrict__ hfeat) {
   using T = T16P<Gm, F, NT0, NT1>;
   const int n = FROM_PLANES ? n_fixed : *n_eval_ptr;
-  const int board0 = base + blockIdx.x * T::TB;
+  const int board0 = blockIdx.x * T::TB;
   if (board0 >= n) return;
-  tower16x2_body<T, FROM_PLANES>(net, leaf_env, eval_slots, n, X, hfeat, board0, net.geo[NT0 == 11 ? 2 : 4]);
+  tower16x2_body<T, FROM_PLANES>(net, leaf_env, eval_slots, n, X, hfeat, board0, net.geo[T::GEO]);
 }
 // (r6) The 8-board form within 176 registers per lane (the compiler takes 198 when it may: 92 B of scratch per lane here, +2 % per launch).
 // A free-running phase runs k_tree's background launch UNDER the tower (azhip.hip wave_group), and a k_tree wavefront (152 registers)
@@ -739,12 +756,12 @@ k_tower16x2(Net16Dev net, const GEnv* __restrict__ leaf_env, const int* __restri
 template <class Gm, int F, bool FROM_PLANES>
 __global__ void __launch_bounds__(2 * T16Threads<F>::V, 1) __attribute__((amdgpu_num_vgpr(88)))
 k_tower16x2c(Net16Dev net, const GEnv* __restrict__ leaf_env, const int* __restrict__ eval_slots,
-             const int* __restrict__ n_eval_ptr, int n_fixed, const float* __restrict__ X, float* __restrict__ hfeat, int base) {
+             const int* __restrict__ n_eval_ptr, int n_fixed, const float* __restrict__ X, float* __restrict__ hfeat) {
   using T = T16P<Gm, F, 11, 10>;
   const int n = FROM_PLANES ? n_fixed : *n_eval_ptr;
-  const int board0 = base + blockIdx.x * T::TB;
+  const int board0 = blockIdx.x * T::TB;
   if (board0 >= n) return;
-  tower16x2_body<T, FROM_PLANES>(net, leaf_env, eval_slots, n, X, hfeat, board0, net.geo[2]);
+  tower16x2_body<T, FROM_PLANES>(net, leaf_env, eval_slots, n, X, hfeat, board0, net.geo[T::GEO]);
 }
 // (r6) Both paired forms in ONE launch: workgroups 0 .. first - 1 take 8 boards each (21 row tiles), the workgroups behind them 7 (19 tiles).
 // A batch between 15 and 16 boards per CU -- a free-running wave's 3700-3840 boards on 256 CUs -- is two rounds of workgroups either
@@ -760,11 +777,11 @@ k_tower16x2m(Net16Dev net, const GEnv* __restrict__ leaf_env, const int* __restr
   if ((int)blockIdx.x < first) {
     const int board0 = blockIdx.x * T8::TB;
     if (board0 >= n) return;
-    tower16x2_body<T8, FROM_PLANES>(net, leaf_env, eval_slots, n, X, hfeat, board0, net.geo[2]);
+    tower16x2_body<T8, FROM_PLANES>(net, leaf_env, eval_slots, n, X, hfeat, board0, net.geo[T8::GEO]);
   } else {
     const int board0 = first * T8::TB + ((int)blockIdx.x - first) * T7::TB;
     if (board0 >= n) return;
-    tower16x2_body<T7, FROM_PLANES>(net, leaf_env, eval_slots, n, X, hfeat, board0, net.geo[4]);
+    tower16x2_body<T7, FROM_PLANES>(net, leaf_env, eval_slots, n, X, hfeat, board0, net.geo[T7::GEO]);
   }
 }
 
@@ -799,7 +816,7 @@ k_tower16s(Net16Dev net, const GEnv* __restrict__ leaf_env, const int* __restric
   // will be recomputed (azhip.hip recover_split) -- do not wait for partners again
   if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)DERR_EXCHANGE) return;
   if ((epoch >> 63) && blockIdx.x == 1) return;      // fault injection (az_debug_exchange_timeout): workgroup 0 loses its partner
-  tower16_fill<T, FROM_PLANES>(buf, planes, nbr, pos, net.geo[1], leaf_env, eval_slots, X, n, board0, threadIdx.x);
+  tower16_fill<T, FROM_PLANES>(buf, planes, nbr, pos, net.geo[T::GEO], leaf_env, eval_slots, X, n, board0, threadIdx.x);
   __syncthreads();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int cwl = wave;

@@ -55,7 +55,7 @@ struct Net16bDev {
   const float* conv_ss;     // [2*nblocks][2][F]
   const bf16x8v* head_w;    // [F/16][F/32][64] x 8 bf16
   const float* head_ss;     // [2][F]
-  const uint16_t* geo[3];   // Geo16 tables: [0] 11 tiles, [1] the latency variant's (NTS), [2] 22 tiles
+  const uint16_t* geo[GEO_COUNT];   // Geo16 tables by GeoSlot, as Net16Dev::geo
   unsigned long long* dbg;  // optional [workgroups][8] cycle stamps, as Net16Dev::dbg (az_debug_tower_timeline)
 };
 
@@ -74,6 +74,8 @@ template <class Gm, int F = 128, int NT = 11> struct T16B {
   static constexpr int WAVES = F / 16, THREADS = 64 * WAVES, CT = F / 16, KS = F / 32;
   using Game = Gm;
   using Geo = Geo16<Gm, NTILE, TB>;
+  static constexpr GeoSlot GEO = NT == 11 ? GEO_11 : NT == 22 ? GEO_22 : GEO_NTS;
+  static_assert(GEO != GEO_NTS || NT == NTS<Gm>, "no table slot for this tile count");
   static constexpr int FILT = F;
   static_assert(BUFH * 2 % 16 == 0 && (SH * 2) % 16 == 0, "rows must stay 16-byte aligned");
 };
@@ -323,7 +325,7 @@ k_tower16b(Net16bDev net, const GEnv* __restrict__ leaf_env, const int* __restri
   const int board0 = blockIdx.x * TB;
   if (board0 >= n) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint16_t* geo = net.geo[NT == 11 ? 0 : NT == 22 ? 2 : 1];
+  const uint16_t* geo = net.geo[T::GEO];
   // ---- input planes (fp32, permuted row order), tables, the buffer's zero row -------------------------------------------
   for (int i = tid; i < T::PLANES; i += T::THREADS) {
     const int row = i / C, c = i % C;

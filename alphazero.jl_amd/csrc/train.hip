@@ -550,7 +550,7 @@ template <class Gm, int F, bool STATS, int NT> static int tr_conv16_f(az_trainer
   using T = T16<Gm, F, NT>;
   static bool attr_done = false;
   if (!attr_done) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv16_layer<Gm, F, STATS, false, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, T::BYTES)); attr_done = true; }
-  hipLaunchKernelGGL((k_conv16_layer<Gm, F, STATS, false, NT>), dim3((t->B + T::TB - 1) / T::TB), dim3(T::THREADS), T::BYTES, t->stream, in, (const float4*)frag, out, t->B, t->e->d_geo[NT == 11 ? 0 : 4], t->part, addend, (long long*)nullptr, bn, fin);
+  hipLaunchKernelGGL((k_conv16_layer<Gm, F, STATS, false, NT>), dim3((t->B + T::TB - 1) / T::TB), dim3(T::THREADS), T::BYTES, t->stream, in, (const float4*)frag, out, t->B, t->e->d_geo[T::GEO], t->part, addend, (long long*)nullptr, bn, fin);
   return AZ_OK;
 }
 // 3x3 F -> F convolution of [R][F] activations on the MFMA layer kernel; stats: also the first stage of the column sums

@@ -40,7 +40,7 @@
  * is within the 1e-5 tolerance BASELINE.json states, this one is also reproducible.
  *
  * Environment (diagnostics and tests; the product path sets none of them): AZHIP_TOWER / AZHIP_HEADS force a tower / heads kernel
- * (read at az_engine_create), AZHIP_GRAPH=1 replays wave pairs as hipGraphs, AZHIP_VMM=0|1 forces the plain / mapped-on-demand
+ * and AZHIP_TOWER_MIXED=1 allows the mixed paired tower launch (all read at az_engine_create), AZHIP_GRAPH=1 replays wave pairs as hipGraphs, AZHIP_VMM=0|1 forces the plain / mapped-on-demand
  * node pool and AZHIP_POOL_GB bounds the physical memory of the latter, AZHIP_RCCL_LIB=<path> substitutes the library az_comm_*
  * loads (tests/rccl_stub: several ranks on one GPU), AZHIP_TRAIN_ONE_STREAM=1 keeps the trainer's weight gradients on the
  * step's own stream and AZHIP_TRAIN_WG_LATE=1 starts them after the data gradient of their layer instead of beside it (same values

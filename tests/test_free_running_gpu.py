@@ -194,4 +194,4 @@ def test_the_176_register_paired_tower_changes_no_record(monkeypatch):
             assert ng == 6000 and st.aborted_games == 0
             out[mode] = _by_id(g, m, ng)
     assert out["own"] == out["capped"] == out["lock"]
-    assert ("capped", "k_tower16x2c") in kernels and {k for md, k in kernels if md == "own"} <= {"k_tower16x2", "k_tower16x2c", "k_tower16x2m", "k_tower16", "k_tower"}, kernels   # (16x2m: the mixed launch, if an earlier test of this process switched it on)
+    assert ("capped", "k_tower16x2c") in kernels and {k for md, k in kernels if md == "own"} <= {"k_tower16x2", "k_tower16x2c", "k_tower16", "k_tower"}, kernels
