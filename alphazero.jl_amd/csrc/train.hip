@@ -860,6 +860,104 @@ extern "C" int az_debug_trainer_activation(az_trainer* t, int32_t which, float* 
   return AZ_OK;
 }
 
+// debug aids (not part of the ABI in azhip.h): the step's three MFMA kernels one at a time, on caller-supplied host arrays, through
+// the trainer's own launch helpers on t->stream -- so the geometry table, wg_splits, the partial buffers, the fragment maps and the
+// GEMM workspace with its split rule are the ones a step uses.  tests/test_train_kernels_gpu.py feeds them small integers, whose
+// fp32 sums are exact in any order, and compares bit for bit at the batches where the kernels' inner loops iterate.
+struct TrTemp {                                                      // device memory of one call
+  std::vector<void*> allocs;
+  ~TrTemp() { for (void* p : allocs) (void)hipFree(p); }
+  int up(float** p, const float* host, size_t n) {
+    AZCHK(mem_alloc(&allocs, p, n));
+    if (host) HIPCHK(hipMemcpy(*p, host, sizeof(float) * n, hipMemcpyHostToDevice));
+    return AZ_OK;
+  }
+};
+#define TR_TOWER(t) if ((t)->nblocks < 1) return fail(AZ_ERR_BAD_ARG, "the trainer's tower has no F -> F convolution (num_blocks = 0)")
+// weight gradient of a 3x3 F -> F convolution (tr_wgrad16 = k_wgrad16 + k_wgrad_reduce): a, dg = [B P][F] with row = board P + y W + x;
+// out[9][F][F] = [tap][ci][co], tap = 3 (dy + 1) + (dx + 1): sum over the rows whose neighbour (y + dy, x + dx) is on the board of a[neighbour][ci] dg[row][co]
+extern "C" int az_debug_trainer_wgrad(az_trainer* t, const float* a, const float* dg, int64_t n_in, float* out, int64_t n_out) {
+  TRAINER(t);
+  TR_TOWER(t);
+  const int64_t want_in = (int64_t)t->R * t->F, want_out = 9LL * t->F * t->F;
+  if (!a || !dg || n_in != want_in) return fail(AZ_ERR_BAD_ARG, "a and dg must hold %lld floats", (long long)want_in);
+  if (!out || n_out != want_out) return fail(AZ_ERR_BAD_ARG, "out must hold %lld floats", (long long)want_out);
+  HIPCHK(hipStreamSynchronize(t->stream));
+  HIPCHK(hipStreamSynchronize(t->side));
+  HIPCHK(hipMemcpy(t->dact, a, sizeof(float) * (size_t)want_in, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(t->dact2, dg, sizeof(float) * (size_t)want_in, hipMemcpyHostToDevice));
+  float* dw = t->gwork + t->convs[1].wk_wm;
+  AZCHK(tr_wgrad16(t, t->dact, t->dact2, dw, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(out, dw, sizeof(float) * (size_t)want_out, hipMemcpyDeviceToHost));
+  return AZ_OK;
+}
+// tower layer `layer` >= 1 on the trainer's CURRENT parameters (k_tr_gather, then tr_conv16 = k_conv16_layer), all arrays [B P][F]:
+//   dgrad = 1: out = conv(in, wk_fdg fragments) (+ addend)        -- the data gradient of the layer's input
+//   dgrad = 0: a_out = relu(gamma ((in - mean) invstd) + beta (+ res)), out = conv(a_out, wk_ffwd fragments), with the column sums of
+//              out finished by k_tr_colsum_final in mode 0: sums[2][F] = (sum, sum of squares); bn = [4][F]: mean, invstd, gamma, beta
+// nparts: the workgroups of the launch (64 filters: which tile count ran -- ceil(B / boards of the 6- or the 11-tile form))
+extern "C" int az_debug_trainer_conv(az_trainer* t, int32_t layer, int32_t dgrad, const float* in, const float* addend, const float* bn, const float* res,
+                                     int64_t n, float* out, float* a_out, double* sums, int32_t* nparts) {
+  TRAINER(t);
+  TR_TOWER(t);
+  if (layer < 1 || layer > 2 * t->nblocks) return fail(AZ_ERR_BAD_ARG, "layer %d: the F -> F convolutions are 1 .. %d", layer, 2 * t->nblocks);
+  const int F = t->F;
+  const int64_t want = (int64_t)t->R * F;
+  if (!in || !out || n != want) return fail(AZ_ERR_BAD_ARG, "in and out must hold %lld floats", (long long)want);
+  if (dgrad ? (bn || res || a_out || sums) : (addend || !bn || !a_out || !sums))
+    return fail(AZ_ERR_BAD_ARG, dgrad ? "the data gradient takes in, addend and out only" : "the forward pass takes in, bn, res, out, a_out and sums");
+  const TrConv& c = t->convs[layer];
+  const size_t bytes = sizeof(float) * (size_t)want;
+  HIPCHK(hipStreamSynchronize(t->stream));
+  HIPCHK(hipStreamSynchronize(t->side));
+  hipLaunchKernelGGL(k_tr_gather, dim3(tr_grid((long long)t->nwork)), dim3(256), 0, t->stream, t->blob, t->map, (long long)t->nwork, t->work);
+  HIPCHK(hipMemcpy(t->dact, in, bytes, hipMemcpyHostToDevice));
+  const float* second = dgrad ? addend : res;
+  if (second) HIPCHK(hipMemcpy(t->dact2, second, bytes, hipMemcpyHostToDevice));
+  int np = 0;
+  TrTemp tmp;                                                       // lives until the stream has been waited for
+  if (dgrad) {
+    AZCHK(tr_conv16(t, t->dact, t->work + c.wk_fdg, t->dact3, false, &np, second ? t->dact2 : nullptr));
+  } else {
+    float* dbn = nullptr;
+    AZCHK(tmp.up(&dbn, bn, 4 * (size_t)F));
+    TrFinal fin{};                                                  // mode 0: the sums only; no counter: the second stage is the separate launch
+    AZCHK(tr_conv16(t, nullptr, t->work + c.wk_ffwd, t->dact3, true, &np, nullptr, BnIn{t->dact, dbn, dbn + F, dbn + 2 * F, dbn + 3 * F, second ? t->dact2 : nullptr, t->dcol}, fin));
+    hipLaunchKernelGGL(k_tr_colsum_final, dim3(F), dim3(64), 0, t->stream, t->part, np, F, t->sums, fin);
+  }
+  HIPCHK(hipStreamSynchronize(t->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(out, t->dact3, bytes, hipMemcpyDeviceToHost));
+  if (!dgrad) {
+    HIPCHK(hipMemcpy(a_out, t->dcol, bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sums, t->sums, sizeof(double) * 2 * (size_t)F, hipMemcpyDeviceToHost));
+  }
+  if (nparts) *nparts = np;
+  return AZ_OK;
+}
+// C[M][N] = alpha op(A) op(B) + beta C through tr_gemm: the trainer's workspace and gemm_f32's split rule.  Row-major host arrays
+// with leading dimensions lda / ldb / ldc; na / nb / nc = their sizes in floats (rows x leading dimension).
+extern "C" int az_debug_trainer_gemm(az_trainer* t, int32_t ta, int32_t tb, int32_t M, int32_t N, int32_t K, float alpha, const float* A, int32_t lda, int64_t na,
+                                     const float* B, int32_t ldb, int64_t nb, float beta, float* Cm, int32_t ldc, int64_t nc) {
+  TRAINER(t);
+  if (M < 1 || N < 1 || K < 1) return fail(AZ_ERR_BAD_ARG, "M, N and K must be positive");
+  const int ra = ta ? K : M, ca = ta ? M : K, rb = tb ? N : K, cb = tb ? K : N;
+  if (!A || lda < ca || na != (int64_t)ra * lda) return fail(AZ_ERR_BAD_ARG, "A must hold %d rows of lda >= %d floats", ra, ca);
+  if (!B || ldb < cb || nb != (int64_t)rb * ldb) return fail(AZ_ERR_BAD_ARG, "B must hold %d rows of ldb >= %d floats", rb, cb);
+  if (!Cm || ldc < N || nc != (int64_t)M * ldc) return fail(AZ_ERR_BAD_ARG, "C must hold %d rows of ldc >= %d floats", M, N);
+  TrTemp tmp;
+  float *dA = nullptr, *dB = nullptr, *dC = nullptr;
+  AZCHK(tmp.up(&dA, A, (size_t)na)); AZCHK(tmp.up(&dB, B, (size_t)nb)); AZCHK(tmp.up(&dC, Cm, (size_t)nc));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  AZCHK(tr_gemm(t, ta != 0, tb != 0, M, N, K, alpha, dA, lda, dB, ldb, beta, dC, ldc));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(Cm, dC, sizeof(float) * (size_t)nc, hipMemcpyDeviceToHost));
+  return AZ_OK;
+}
+
 // batch_updates!(tr, n) (learning.jl:131-141): n optimiser steps on successive batches; losses[i] = L before update i
 extern "C" int az_trainer_batch_updates(az_trainer* t, int32_t n, float* losses) {
   TRAINER(t);

@@ -179,13 +179,27 @@ def test_gradients_with_default_heads_and_no_blocks():
         mem.close()
 
 
-@pytest.mark.parametrize("game,nblocks,F,B,policy", [(1, 1, 64, 24, 1), (0, 2, 64, 16, 0), (2, 1, 64, 20, 2), (0, 1, 128, 12, 1),
-                                                     (0, 1, 128, 203, 1), (0, 2, 64, 333, 0), (1, 1, 64, 500, 2),    # many workgroups, ragged tails
-                                                     (0, 5, 128, 96, 1), (2, 3, 64, 130, 0),    # deep towers: the three-buffer gradient ring of the backward pass wraps
-                                                     (1, 1, 128, 70, 1), (2, 2, 128, 45, 0)])   # 128 filters on the small boards: k_wgrad16's 4-wavefront form with 5 / 3 boards per LDS chunk
-def test_gradients_match_torch_autograd(game, nblocks, F, B, policy):
+# the batches at which the step's MFMA kernels loop (tests/test_train_kernels_gpu.py holds the same kernels bit-exact one at a time; 256 CUs):
+# 128 filters: k_wgrad16's 4-wavefront form has 85 workgroups per tap group and 1 / 5 / 3 boards (Connect-Four / Tic-tac-toe / Mancala)
+# per LDS chunk; 64 filters: 256 workgroups, 3 boards per chunk at Connect-Four
+LOOP_CASES = [(0, 1, 128, 1024, 1),     # the shipped batch: 12 or 13 one-board chunks per workgroup; the dense heads' weight gradients (K = B) split their reduction
+              (2, 1, 128, 1024, 0),     # 12 or 13 boards per workgroup: four chunks of 3 (+ a chunk of 1)
+              (0, 1, 128, 345, 2),      # 4 or 5 chunks
+              (1, 1, 128, 600, 1),      # 7 or 8 boards per workgroup: chunks of 5+2 and 5+3
+              (0, 1, 64, 1024, 1),      # 4 boards per workgroup: chunks of 3+1; the last batch of the 6-tile k_conv16_layer
+              (0, 1, 64, 1028, 0)]      # chunks of 3+1 and 3+2; 257 > 256 workgroups: the 11-tile k_conv16_layer
+
+
+def _memory_games(B):
+    """self-play games that leave at least B distinct samples in the data set (merged by state)"""
+    return 12 if B < 100 else 60 if B <= 500 else 400
+
+
+def _check_gradients(game, nblocks, F, B, policy, device_masks_only=False):
+    """device_masks_only: the fp64 reference is differentiated with the DEVICE's ReLU masks only (a layer has millions of activations at
+    these batches, see _rel_err_by_array), its own pass runs forward only.  Bounds tol = 1e-3, l2_tol = 3e-4 as for the deep towers."""
     import azhip
-    gspec, mem = _memory(game, 12 if B < 100 else 60, 3)
+    gspec, mem = _memory(game, _memory_games(B), 3)
     hp = azhip.ResNetHP(num_blocks=nblocks, num_filters=F, num_policy_head_filters=32, num_value_head_filters=32)
     nn = azhip.ResNet(gspec, hp, seed=8)
     lp = azhip.LearningParams(samples_weighing_policy=policy, l2_regularization=1e-4, loss_computation_batch_size=64, batch_size=B,
@@ -193,17 +207,21 @@ def test_gradients_match_torch_autograd(game, nblocks, F, B, policy):
     with azhip.Trainer(gspec, nn, mem, lp, use_symmetries=game != 2) as tr:
         data = tr.data.tensors()
         n = len(data[0])
+        assert n >= B and tr.batch_size() == B, (n, B)              # the data set holds the batch: distinct indices
         rng = np.random.default_rng(5)
         idx = rng.choice(n, size=B, replace=False)
         loss, parts, grad = tr.gradients(idx)
         batch = [x[idx] for x in data]
         ref = TorchNet(game, hp, nn.params())
-        L, (Lp, Lv, Lreg, Linv, scale) = ref.losses(batch, float(tr.Wmean), float(tr.Hp), 1e-4, 1.0, 2.0)
-        (L - scale * Lreg).backward()                              # the device gradient excludes the L2 term (added in the update)
-        want = ref.blob(grads=True)
+        with torch.set_grad_enabled(not device_masks_only):
+            L, (Lp, Lv, Lreg, Linv, scale) = ref.losses(batch, float(tr.Wmean), float(tr.Hp), 1e-4, 1.0, 2.0)
+        want = None
+        if not device_masks_only:
+            (L - scale * Lreg).backward()                          # the device gradient excludes the L2 term (added in the update)
+            want = ref.blob(grads=True)
         assert abs(loss - L.item()) < 2e-5 * max(1.0, abs(L.item()))
         assert np.allclose(parts, [Lp.item(), Lv.item(), Lreg.item(), Linv.item(), scale.item()], rtol=5e-5, atol=5e-6), (parts, Lp.item(), Lv.item())
-        if nblocks >= 3:
+        if nblocks >= 3 or device_masks_only:
             # the same reference differentiated with the ReLU masks the device actually had: the comparison is then between
             # two chains of the SAME piecewise-linear function, and the 1e-3 of the shallow cases holds for every entry
             masks, flips = _device_relu_masks(tr, hp, ref)
@@ -212,12 +230,30 @@ def test_gradients_match_torch_autograd(game, nblocks, F, B, policy):
             (L2 - scale2 * Lreg2).backward()
             assert abs(L2.item() - L.item()) < 1e-12 * max(1.0, abs(L.item()))      # the masks change derivatives, not values
             _rel_err_by_array(game, hp, grad.astype(np.float64), ref2.blob(grads=True), tol=1e-3, l2_tol=3e-4)
-            _rel_err_by_array(game, hp, grad.astype(np.float64), want, tol=1e-2, l2_tol=1e-3)   # and against the reference's own masks, as before
+            if want is not None:
+                _rel_err_by_array(game, hp, grad.astype(np.float64), want, tol=1e-2, l2_tol=1e-3)   # and against the reference's own masks, as before
         else:
             _rel_err_by_array(game, hp, grad.astype(np.float64), want, tol=1e-3)
         # the probe does not move the parameters or the running statistics
         assert np.array_equal(tr.trained_params(), nn.params())
     mem.close()
+
+
+@pytest.mark.parametrize("game,nblocks,F,B,policy", [(1, 1, 64, 24, 1), (0, 2, 64, 16, 0), (2, 1, 64, 20, 2), (0, 1, 128, 12, 1),
+                                                     (0, 1, 128, 203, 1), (0, 2, 64, 333, 0), (1, 1, 64, 500, 2),    # many workgroups, ragged tails
+                                                     (0, 5, 128, 96, 1), (2, 3, 64, 130, 0),    # deep towers: the three-buffer gradient ring of the backward pass wraps
+                                                     (1, 1, 128, 70, 1), (2, 2, 128, 45, 0)]    # 128 filters on the small boards: k_wgrad16's 4-wavefront form, one board per workgroup (70 / 45 boards over 85 workgroups)
+                         + LOOP_CASES)
+def test_gradients_match_torch_autograd(game, nblocks, F, B, policy):
+    _check_gradients(game, nblocks, F, B, policy, device_masks_only=(game, nblocks, F, B, policy) in LOOP_CASES)
+
+
+@pytest.mark.parametrize("game,B", [(0, 203), (1, 333), (2, 250)])
+def test_gradients_match_torch_autograd_with_the_11_tile_layer_kernel(game, B, monkeypatch):
+    """AZHIP_TRAIN_NT6=0: 64 filters on the 11-tile k_conv16_layer, which the batch alone selects only above one workgroup per CU
+    (Connect-Four B > 1024, Tic-tac-toe B > 4864, Mancala B > 3072); ragged last workgroups (4 / 19 / 12 boards per workgroup)"""
+    monkeypatch.setenv("AZHIP_TRAIN_NT6", "0")
+    _check_gradients(game, 1, 64, B, 1, device_masks_only=True)
 
 
 @pytest.mark.parametrize("reset_at", [None, 2])
