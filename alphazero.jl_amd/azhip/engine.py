@@ -275,14 +275,15 @@ class Engine:
 # Engines are therefore kept by configuration and only their parameters are replaced between phases (az_net_set_params =
 # Network.copy per phase, training.jl:278-279).  The key is everything az_engine_create looks at: a role (the two players
 # of an arena get two engines), the az_engine_cfg bytes AND the environment overrides the library reads at creation
-# (AZHIP_TOWER / AZHIP_TOWER_MIXED / AZHIP_HEADS / AZHIP_GRAPH / AZHIP_XCH_EPOCH0 -- an engine built under one override must not serve a call
-# made under another).  Bounded by count and by device bytes (az_engine_device_bytes), least recently used first out; a
+# (CREATE_ENV -- an engine built under one override must not serve a call made under another).  Bounded by count and by device bytes (az_engine_device_bytes), least recently used first out; a
 # cached engine does not keep its last phase's records (az_engine_release_phase at eviction time is too late: callers
 # release them once pushed, see training.py).
 CACHE_MAX = 4
 CACHE_MAX_BYTES = int(float(os.environ.get("AZHIP_CACHE_GB", "96")) * (1 << 30))
+# the names inside `struct EnvCreate` of csrc/env.h, no more and no fewer (tests/test_env_overrides.py compares); what the
+# other structs there name is read later and is no part of the key
 CREATE_ENV = ("AZHIP_TOWER", "AZHIP_TOWER_MIXED", "AZHIP_HEADS", "AZHIP_GRAPH", "AZHIP_XCH_EPOCH0", "AZHIP_VMM", "AZHIP_POOL_GB", "AZHIP_XCH_FAIL_AT", "AZHIP_POOLED_QUEUE",
-              "AZHIP_HT_TAG_BITS", "AZHIP_HT_EPOCH0", "AZHIP_EVAL_CACHE", "AZHIP_EVAL_CACHE_LOG2", "AZHIP_VMM_KEYS", "AZHIP_TREE_ATOMIC", "AZHIP_TREE_SORT")   # (AZHIP_FREE_RUN / AZHIP_RUN_K / AZHIP_FR_ROUND are read per phase, not at creation)
+              "AZHIP_HT_TAG_BITS", "AZHIP_HT_EPOCH0", "AZHIP_EVAL_CACHE", "AZHIP_EVAL_CACHE_LOG2", "AZHIP_VMM_KEYS", "AZHIP_TREE_ATOMIC", "AZHIP_TREE_SORT", "AZHIP_EXPLORE_K")
 _cache = {}
 
 

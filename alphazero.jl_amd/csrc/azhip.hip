@@ -115,17 +115,10 @@ extern "C" int az_engine_destroy(az_engine* e) {
   }
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   split_register(e, 0);
-  if (e->h_xflag) (void)hipHostFree(e->h_xflag);
-  if (e->h_nleaf) (void)hipHostFree(e->h_nleaf);
-  if (e->h_needy) (void)hipHostFree(e->h_needy);
-  if (e->h_fr_words) (void)hipHostFree(e->h_fr_words);
-  if (e->h_busy) (void)hipHostFree(e->h_busy);
   for (int i = 0; i < 4; ++i) { if (e->fr_s[i]) { (void)hipStreamSynchronize(e->fr_s[i]); (void)hipStreamDestroy(e->fr_s[i]); } if (e->fr_ev[i]) (void)hipEventDestroy(e->fr_ev[i]); }
   if (e->d_done) (void)hipFree(e->d_done);
   if (e->d_done_off) (void)hipFree(e->d_done_off);
-  if (e->h_env) (void)hipHostFree(e->h_env);
-  if (e->h_n) (void)hipHostFree(e->h_n);
-  if (e->h_pv) (void)hipHostFree(e->h_pv);
+  for (void* q : e->host_allocs) (void)hipHostFree(q);
   drop_wave_graphs(e);
   for (auto& r : e->prof_pool) { if (r.a) (void)hipEventDestroy(r.a); if (r.b) (void)hipEventDestroy(r.b); }
   for (void* q : e->net_allocs) (void)hipFree(q);
@@ -218,12 +211,12 @@ static int vm_grow(az_engine* e, int ahead) {
   return AZ_OK;
 }
 
-extern "C" int az_engine_create(const az_engine_cfg* c, az_engine** out) {
-  if (!c || !out) return fail(AZ_ERR_BAD_ARG, "NULL argument");
-  *out = nullptr;
+// ---- az_engine_create, step by step.  Every step takes the engine as far as its title says and returns a status; after a failure
+// az_engine_destroy takes apart whatever the steps before it left.  The ORDER of the steps is the order of the device allocations and
+// of the work on the engine's stream.
+static int check_cfg(const az_engine_cfg* c, GameInfo* gi) {          // everything that can be refused before the device is touched
   if (c->struct_size != (int32_t)sizeof(az_engine_cfg)) return fail(AZ_ERR_BAD_ARG, "az_engine_cfg size mismatch (%d vs %zu): call az_engine_cfg_init", c->struct_size, sizeof(az_engine_cfg));
-  GameInfo gi;
-  if (!game_info(c->game, &gi)) return fail(AZ_ERR_BAD_ARG, "unknown game id %d", c->game);
+  if (!game_info(c->game, gi)) return fail(AZ_ERR_BAD_ARG, "unknown game id %d", c->game);
   if (c->oracle < AZ_ORACLE_UNIFORM || c->oracle > AZ_ORACLE_ROLLOUT) return fail(AZ_ERR_BAD_ARG, "unknown oracle kind %d", c->oracle);
   if (c->game == AZ_GAME_GO9_PLANES && c->oracle != AZ_ORACLE_RESNET) return fail(AZ_ERR_BAD_ARG, "the 9x9x4 plane geometry has no device twin: it serves az_net_forward only (ResNet oracle)");
   if (c->num_workers < 1) return fail(AZ_ERR_BAD_ARG, "num_workers must be >= 1");
@@ -243,295 +236,288 @@ extern "C" int az_engine_create(const az_engine_cfg* c, az_engine** out) {
     if (c->num_blocks < 0 || c->num_blocks > 64) return fail(AZ_ERR_BAD_ARG, "num_blocks out of range");
     if (c->net_bf16 != 0 && c->net_bf16 != 1) return fail(AZ_ERR_BAD_ARG, "net_bf16 must be 0 or 1");
   }
+  return AZ_OK;
+}
+
+// The engine's own stream gets a hardware queue of its own (a stream made with a CU mask -- here: every CU -- is not folded
+// into the runtime's pool of GPU_MAX_HW_QUEUES shared queues).  Two one-group engines searching side by side (the arena's two
+// players) otherwise overlap or take turns depending on which pooled queue their streams happened to land on (DESIGN.md 6b:
+// 5.6 s against 8.2 s for the same evaluation).  AZHIP_POOLED_QUEUE keeps the runtime's assignment.
+static int create_stream(az_engine* e) {
+  int ncu = 0;
+  HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, e->device));
+  std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
+  for (int i = 0; i < ncu; ++i) mask[(size_t)i / 32] |= 1u << (i % 32);
+  if (e->env.pooled_queue || ncu <= 0 || hipExtStreamCreateWithCUMask(&e->stream, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
+    (void)hipGetLastError();
+    e->stream = nullptr;
+    HIPCHK(hipStreamCreate(&e->stream));
+  }
+  return AZ_OK;
+}
+
+// the node pool of create_tree: a virtual range backed on demand (above VM_THRESHOLD, or as AZHIP_VMM says), else one hipMalloc
+static int create_node_pool(az_engine* e) {
+  DView& v = e->v; const GameInfo& gi = e->gi; const int G = v.G; const long long cap = v.cap_nodes;
+  const size_t pool_bytes = (size_t)G * cap * gi.node_bytes;
+  const size_t chunk_nodes = VM_CHUNK / gi.node_bytes;
+  const bool pow2 = (chunk_nodes & (chunk_nodes - 1)) == 0 && chunk_nodes * gi.node_bytes == VM_CHUNK;
+  const bool want = e->env.vmm >= 0 ? e->env.vmm != 0 : pool_bytes > VM_THRESHOLD;
+  void* base = nullptr;
+  const int rows = (int)((cap + chunk_nodes - 1) / chunk_nodes);
+  const size_t vbytes = (size_t)rows * G * VM_CHUNK;
+  // a runtime without virtual memory management (or without room in the address space) gets the plain pool
+  const bool vm_ok = want && pow2 && (size_t)cap > chunk_nodes && gi.node_bytes > 0 &&
+                     hipMemAddressReserve(&base, vbytes, VM_CHUNK, nullptr, 0) == hipSuccess;
+  if (want && !vm_ok) (void)hipGetLastError();
+  if (!vm_ok) {
+    AZCHK(dalloc(e, &v.nodes, pool_bytes, false));
+    v.node_sh = 31; v.node_mask = 0x7fffffffu; v.node_row = 0; v.node_stride = (size_t)cap * gi.node_bytes; v.slot_cap = nullptr;
+    return AZ_OK;
+  }
+  e->vm_chunk = VM_CHUNK; e->vm_chunk_nodes = (int)chunk_nodes; e->vm_rows = rows; e->vm_bytes = vbytes; e->vm_base = (char*)base;
+  e->vm_budget = ~(size_t)0;                                         // set once every fixed allocation of the engine is made (create_finish)
+  v.nodes = e->vm_base;
+  int sh = 0; while (((size_t)1 << sh) < chunk_nodes) ++sh;
+  v.node_sh = sh; v.node_mask = (uint32_t)chunk_nodes - 1; v.node_row = (size_t)G * VM_CHUNK; v.node_stride = VM_CHUNK;
+  e->h_slot_cap.assign(G, 0); e->h_node_count.assign(G, 0);
+  AZCHK(dalloc(e, &e->d_slot_cap, G));
+  v.slot_cap = e->d_slot_cap;
+  return AZ_OK;
+}
+
+// the whole-engine view: sizes, the per-slot tables of the search and the node pool
+static int create_tree(az_engine* e) {
+  const az_engine_cfg* c = &e->cfg; const GameInfo& gi = e->gi; DView& v = e->v; const int G = c->num_workers;
+  memset(&v, 0, sizeof v);
+  v.G = G;
+  v.max_moves = c->max_moves_per_game > 0 ? c->max_moves_per_game : gi.max_plies;
+  v.max_depth = gi.max_plies + 1;
+  long long cap = c->max_nodes_per_slot;
+  if (cap <= 0) {
+    // Mancala has no fixed length (MAX_PLIES = 256 bounds the trace); self-play games of the shipped parameters last
+    // 30-70 plies, the pool holds 128 plies of new nodes per game between resets (288 GB of HBM pay for the margin);
+    // a longer game reports AZ_ERR_CAPACITY and max_nodes_per_slot raises the bound
+    long long plies = c->game == AZ_GAME_MANCALA ? 128 : gi.max_plies;
+    cap = (long long)c->num_iters_per_turn * plies * std::max(1, c->reset_every);
+    if (c->reset_every == 0) cap *= 4;
+    cap = std::max<long long>(cap, 1024);
+  }
+  if (cap > (1LL << 30)) return fail(AZ_ERR_BAD_ARG, "max_nodes_per_slot too large");
+  v.cap_nodes = (int)cap;
+  int hs = 1024;
+  while ((long long)hs * 2 < cap * 3) hs <<= 1;
+  v.ht_size = hs;
+  v.tag_mask = e->env.tag_mask; v.epoch0 = e->env.epoch0; v.bk_mode = e->env.bk_mode;   // test knobs and a k_tree experiment (env.h)
+  AZCHK(dalloc(e, &v.sr, G)); AZCHK(dalloc(e, &v.game_id, G));
+  AZCHK(dalloc(e, &v.move_idx, G)); AZCHK(dalloc(e, &e->d_node_count, G));
+  AZCHK(dalloc(e, &v.worker_sim_id, G));
+  AZCHK(dalloc(e, &v.eta, (size_t)G * gi.APAD));
+  AZCHK(dalloc(e, &v.ht, (size_t)G * hs));
+  AZCHK(create_node_pool(e));
+  AZCHK(dalloc(e, &v.path, (size_t)G * v.max_depth));
+  AZCHK(dalloc(e, &v.leaf_env, G));
+  AZCHK(dalloc(e, &v.eval_slots, (size_t)2 * G)); v.eval_stride = G;
+  AZCHK(dalloc(e, &v.bg_list, (size_t)2 * G)); AZCHK(dalloc(e, &v.bg_cnt, 2 * AZ_MAX_GROUPS));
+  return dalloc(e, &v.n_eval, 2 * AZ_MAX_GROUPS);
+}
+
+// side records (state key + Vest, 32 B per node).  Plain pool: dense [G][cap][4].  Mapped-on-demand pool: a second virtual
+// range whose pieces follow the node chunks (DView::keys), so that they cost 32 B per node that EXISTS -- dense they were
+// 26.8 GB of BASELINE configs[3]'s 57 GB engine.  AZHIP_VMM_KEYS=0 keeps the dense array beside a mapped pool.
+static int create_side_records(az_engine* e) {
+  DView& v = e->v; const int G = v.G;
+  const size_t piece = (size_t)e->vm_chunk_nodes * 32;
+  void* kbase = nullptr;
+  bool mapped_keys = e->vm_rows > 0 && e->env.vmm_keys && piece > 0 && VM_CHUNK % piece == 0;
+  size_t kbytes = 0;
+  if (mapped_keys) {
+    kbytes = ((size_t)e->vm_rows * G * piece + VM_CHUNK - 1) / VM_CHUNK * VM_CHUNK;
+    if (hipMemAddressReserve(&kbase, kbytes, VM_CHUNK, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); mapped_keys = false; }
+  }
+  if (mapped_keys) {
+    e->vmk_base = (char*)kbase; e->vmk_bytes = kbytes; e->vmk_piece = piece;
+    e->vmk_granule.assign(kbytes / VM_CHUNK, 0);
+    v.keys = (unsigned long long*)kbase;
+    v.key_row = (size_t)G * piece / 8; v.key_stride = piece / 8;
+  } else {
+    AZCHK(dalloc(e, &v.keys, (size_t)G * v.cap_nodes * 4, false));
+    v.key_row = 0; v.key_stride = (size_t)v.cap_nodes * 4;
+    if (e->vm_rows) v.key_row = (size_t)e->vm_chunk_nodes * 4;       // dense array under a mapped pool: idx = (row, offset) again, rows of a slot are contiguous
+  }
+  hipLaunchKernelGGL(k_slot_records, dim3((G + 255) / 256), dim3(256), 0, e->stream, v, (int)SR_ZERO);   // epoch 1, no root, nothing else
+  return AZ_OK;
+}
+
+// The oracle's answers per slot and the evaluation cache (tree.h): on for the ResNet oracle -- what an evaluation costs there makes a
+// repeated one worth a look-up.  AZHIP_EVAL_CACHE=0 switches it off, =1 forces it on for the exact synthetic oracles as well (tests;
+// never for the rollout oracle, whose answer depends on the simulation's RNG stream, nor under hipGraph replay: the launch number is
+// a kernel argument).
+static int create_eval_cache(az_engine* e) {
+  const az_engine_cfg* c = &e->cfg; const GameInfo& gi = e->gi; DView& v = e->v; const int G = v.G;
+  AZCHK(dalloc(e, &v.Pout, (size_t)std::max(G, 1) * gi.APAD)); AZCHK(dalloc(e, &v.Vout, G));
+  const bool on = e->env.eval_cache >= 0 ? e->env.eval_cache != 0 && c->oracle != AZ_ORACLE_ROLLOUT : c->oracle == AZ_ORACLE_RESNET;
+  if (!on || e->env.use_graphs) return AZ_OK;
+  // sized from the workload: 8 x slots x simulations per move entries of 64 bytes, 2^16 (4 MB) ... 2^24 (1 GB: BASELINE
+  // configs[1]; a phase there evaluates 2-6 x 10^7 states) -- an 8-slot test engine and the 128-worker arena players no longer hold
+  // 1 GB each; AZHIP_EVAL_CACHE_LOG2 says otherwise
+  int lg = e->env.eval_cache_log2;
+  if (!lg) for (lg = 16; lg < 24 && ((long long)1 << lg) < 8LL * G * std::max(1, c->num_iters_per_turn);) ++lg;
+  AZCHK(dalloc(e, &e->d_ec, (size_t)1 << lg));                      // zeroed: every entry EC_EMPTY
+  e->ec_mask = ((uint32_t)1 << lg) - 1u;
+  AZCHK(dalloc(e, &e->d_ec_claim, (size_t)2 * G, false));
+  HIPCHK(hipMemsetAsync(e->d_ec_claim, 0xff, sizeof(int) * 2 * (size_t)G, e->stream));
+  AZCHK(dalloc(e, &e->d_Phit, (size_t)G * gi.APAD)); AZCHK(dalloc(e, &e->d_Vhit, G));
+  v.ec = e->d_ec; v.ec_mask = e->ec_mask; v.ec_seq = 0; v.ec_claim = e->d_ec_claim; v.Phit = e->d_Phit; v.Vhit = e->d_Vhit;
+  return AZ_OK;
+}
+
+// the records a phase leaves, the device's error word, and the words host and kernels exchange without a sync (host-mapped)
+static int create_words(az_engine* e) {
+  DView& v = e->v; const int G = v.G;
+  AZCHK(dalloc(e, &v.trace, (size_t)G * v.max_moves)); AZCHK(dalloc(e, &v.grec, G));
+  AZCHK(dalloc(e, &v.finished, G)); AZCHK(dalloc(e, &v.err, 1));
+  // split tower fallback: one exchange word per slot group (+ one nobody sets for the whole-engine view), the counters of the
+  // k_tree launches that stood still meanwhile, and a host-mapped word the kernel raises so that the host notices without a sync
+  AZCHK(dalloc(e, &e->d_xerr, AZ_MAX_GROUPS + 1)); AZCHK(dalloc(e, &e->d_skipped, 2 * (AZ_MAX_GROUPS + 1)));
+  v.xerr = e->d_xerr + AZ_MAX_GROUPS; v.skipped = e->d_skipped + 2 * AZ_MAX_GROUPS;
+  AZCHK(halloc_mapped(e, &e->h_xflag, &e->d_xflag, 1, 0));
+  AZCHK(halloc_mapped(e, &e->h_nleaf, &e->d_nleaf, AZ_MAX_GROUPS, -1));   // nothing reported yet: launches are priced at their upper bound
+  AZCHK(halloc_mapped(e, &e->h_needy, &e->d_needy, AZ_MAX_GROUPS, 0));
+  // free-running phases: the device's own bookkeeping (FRState) and two host-mapped progress words
+  AZCHK(dalloc(e, &e->d_fr, 1)); AZCHK(dalloc(e, &e->d_bg_stop, 1));
+  AZCHK(halloc_mapped(e, &e->h_busy, &e->d_busy, AZ_MAX_GROUPS, -1));
+  return halloc_mapped(e, &e->h_fr_words, &e->d_fr_words, 2, 0);
+}
+
+static int create_staging(az_engine* e) {
+  const int G = e->v.G;
+  e->io_cap = std::max(G, 4096);
+  AZCHK(dalloc(e, &e->d_slots, e->io_cap)); AZCHK(dalloc(e, &e->d_gids, e->io_cap)); AZCHK(dalloc(e, &e->d_roots, e->io_cap));
+  AZCHK(dalloc(e, &e->d_moves, e->io_cap)); AZCHK(dalloc(e, &e->d_eta, (size_t)e->io_cap * AZ_MAX_ACTIONS));
+  AZCHK(dalloc(e, &e->d_offsets, e->io_cap)); AZCHK(dalloc(e, &e->d_stage, (size_t)G * e->v.max_moves));
+  AZCHK(dalloc(e, &e->d_keys, (size_t)2 * e->io_cap)); AZCHK(dalloc(e, &e->d_actions, e->io_cap));
+  AZCHK(dalloc(e, &e->d_next, (size_t)2 * e->io_cap)); AZCHK(dalloc(e, &e->d_term, e->io_cap)); AZCHK(dalloc(e, &e->d_reward, e->io_cap));
+  AZCHK(dalloc(e, &e->d_nodebuf, 512));
+  return dalloc(e, &e->d_visits, (size_t)e->io_cap * (AZ_MAX_ACTIONS + 1));
+}
+
+static int create_net_buffers(az_engine* e) {
+  const az_engine_cfg* c = &e->cfg; const GameInfo& gi = e->gi;
+  e->nn_cap = e->io_cap;
+  AZCHK(dalloc(e, &e->d_hfeat, (size_t)e->nn_cap * gi.P * std::max(64, c->num_filters), false));
+  AZCHK(dalloc(e, &e->d_X, (size_t)e->nn_cap * gi.C * gi.P)); AZCHK(dalloc(e, &e->d_A, (size_t)e->nn_cap * gi.A));
+  AZCHK(dalloc(e, &e->d_P, (size_t)e->nn_cap * std::max(16, gi.APAD))); AZCHK(dalloc(e, &e->d_V, e->nn_cap)); AZCHK(dalloc(e, &e->d_Pinv, e->nn_cap));
+  AZCHK(dalloc(e, &e->d_tmp_env, e->nn_cap)); AZCHK(dalloc(e, &e->d_iota, e->nn_cap)); AZCHK(dalloc(e, &e->d_ntmp, 1));
+  AZCHK(halloc_pinned(e, &e->h_env, (size_t)e->nn_cap)); AZCHK(halloc_pinned(e, &e->h_n, 1)); AZCHK(halloc_pinned(e, &e->h_pv, (size_t)e->nn_cap * (gi.A + 1)));
+  hipLaunchKernelGGL(k_iota, dim3((e->nn_cap + 255) / 256), dim3(256), 0, e->stream, e->d_iota, e->nn_cap);
+  e->xch_epoch = e->env.xch_epoch0;
+  { hipDeviceProp_t pr; HIPCHK(hipGetDeviceProperties(&pr, c->device)); e->num_cu = pr.multiProcessorCount; }
+  return net_set_kernel_attrs(e);
+}
+
+// slot groups: their views into the whole-engine tables, their streams and events, their feature buffers
+static int create_groups(az_engine* e) {
+  const az_engine_cfg* c = &e->cfg; const GameInfo& gi = e->gi; DView& v = e->v; const int G = v.G;
+  if (e->env.tree_sort) { AZCHK(dalloc(e, &e->d_perm, (size_t)2 * G)); AZCHK(dalloc(e, &e->d_perm_prev, (size_t)2 * G)); }
+  int ng = std::min(std::max(c->batch_size > 0 ? G / c->batch_size : 1, 1), (int)AZ_MAX_GROUPS);
+  while (ng > 1 && G % ng != 0) --ng;
+  const int Gh = G / ng;
+  // statistics accumulators: one record per k_tree workgroup of every slot group (and of the whole-engine view, used by the hooks)
+  const int blk_group = (Gh * gi.APAD + 255) / 256, blk_all = (G * gi.APAD + 255) / 256;
+  e->stat_words = (size_t)4 * ((size_t)blk_group * ng + blk_all);
+  AZCHK(dalloc(e, &v.stat, e->stat_words));
+  long long* stat_base = v.stat;
+  v.stat = stat_base + (size_t)4 * blk_group * ng;                   // the whole-engine view's records come after the groups'
+  int lo = 0, hi = 0;
+  HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+  for (int g = 0; g < ng; ++g) {
+    DView gv = v;
+    gv.stat = stat_base + (size_t)4 * blk_group * g;
+    const size_t o = (size_t)g * Gh;
+    gv.G = Gh; gv.slot0 = (int)o;
+    gv.sr += o; gv.game_id += o; gv.move_idx += o;
+    gv.worker_sim_id += o; gv.eta += o * gi.APAD;
+    gv.ht += o * v.ht_size; gv.nodes += o * v.node_stride; gv.path += o * v.max_depth;
+    if (gv.slot_cap) gv.slot_cap += o;
+    gv.leaf_env += o; gv.eval_slots += o; gv.bg_list += o; gv.bg_cnt += 2 * g;
+    if (gv.ec) { gv.ec_claim += 2 * o; gv.Phit += o * gi.APAD; gv.Vhit += o; }
+    gv.xerr = e->d_xerr + g; gv.skipped = e->d_skipped + 2 * g;
+    if (e->env.tree_sort) {                                          // group-relative order, identity until the first move step
+      gv.perm = e->d_perm + o;
+      hipLaunchKernelGGL(k_iota, dim3((Gh + 255) / 256), dim3(256), 0, e->stream, e->d_perm + o, Gh);
+    }
+    gv.needy_host = e->d_needy + g;
+    gv.nleaf_host = e->d_ec ? e->d_nleaf + g : nullptr;              // only the evaluation cache makes a wave's network batch differ from its active slots
+    gv.n_eval += 2 * g; gv.keys += o * v.key_stride; gv.Pout += o * gi.APAD; gv.Vout += o; gv.trace += o * v.max_moves; gv.grec += o; gv.finished += o;
+    e->gv[g] = gv;
+    if (ng == 1) {
+      e->gs[g] = e->gt[g] = e->stream;
+      // a free-running phase runs the group's tree kernels under its own network launch: streams for that (az_selfplay_begin / _end)
+      for (int i = 0; i < 4; ++i) HIPCHK(hipStreamCreateWithPriority(&e->fr_s[i], hipStreamNonBlocking, hi));
+      for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreateWithFlags(&e->fr_ev[i], hipEventDisableTiming));
+    } else {
+      // the short latency-bound tree kernels must not queue behind the other group's tower workgroups:
+      // they get the high-priority queue, the tower the normal one
+      HIPCHK(hipStreamCreateWithPriority(&e->gs[g], hipStreamNonBlocking, hi));
+      HIPCHK(hipStreamCreateWithPriority(&e->gt[g], hipStreamNonBlocking, lo));
+      HIPCHK(hipEventCreateWithFlags(&e->ev_tree[g], hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&e->ev_net[g], hipEventDisableTiming));
+    }
+    AZCHK(dalloc(e, &e->g_hfeat[g], (size_t)Gh * gi.P * std::max(64, c->num_filters), false));
+    e->ngroups = g + 1;
+  }
+  return AZ_OK;
+}
+
+static int set_search_params(az_engine* e) {
+  const az_engine_cfg* c = &e->cfg; DParams& p = e->p;
+  memset(&p, 0, sizeof p);
+  p.gamma = c->gamma; p.cpuct = c->cpuct; p.eps = c->dirichlet_noise_eps; p.alpha = c->dirichlet_noise_alpha;
+  p.prior_temp = c->prior_temperature; p.nsims = c->num_iters_per_turn; p.temp_len = c->temperature_len;
+  for (int i = 0; i < AZ_SCHED_MAX; ++i) { p.temp_xs[i] = c->temperature_xs[i]; p.temp_ys[i] = c->temperature_ys[i]; }
+  p.seed = c->seed; p.oracle = c->oracle; p.reset_every = c->reset_every; p.retire = 0;
+  p.flip_p = c->flip_probability;                                    // read by the self-play kernels only (k_move, k_start_games without roots)
+  return AZ_OK;
+}
+
+// the budget and the first chunks of a mapped-on-demand pool, the host's own buffers; waits for everything the steps enqueued
+static int create_finish(az_engine* e) {
+  if (e->vm_rows) {
+    // Budget of the growing pool: what the device has left AFTER this engine's fixed allocations, minus what is
+    // still to come -- the phase buffer of a bounded phase (num_workers x 4 games of move records is the usual order), the
+    // replay memory / trainer of the same process -- as a margin of 1/8 of the device, at least 4 GB.  AZHIP_POOL_GB overrides.
+    size_t fr = 0, tot = 0;
+    HIPCHK(hipMemGetInfo(&fr, &tot));
+    const size_t margin = std::max<size_t>(tot / 8, (size_t)4 << 30);
+    e->vm_budget = e->env.pool_gb >= 0 ? (size_t)(e->env.pool_gb * (double)((size_t)1 << 30)) : (fr > margin ? fr - margin : fr / 2);
+    AZCHK(vm_grow(e, 1));                                            // the first chunk of every slot
+  }
+  e->h_finished.resize(e->v.G); e->h_grec.resize(e->v.G);
+  e->prof_pool.resize(2048);
+  for (auto& r : e->prof_pool) { HIPCHK(hipEventCreate(&r.a)); HIPCHK(hipEventCreate(&r.b)); }
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipGetLastError());
+  return AZ_OK;
+}
+
+static int (*const CREATE_STEPS[])(az_engine*) = {create_stream, create_tree, create_side_records, create_eval_cache, create_words, create_staging,
+                                                   create_net_buffers, create_groups, set_search_params, create_finish};
+
+extern "C" int az_engine_create(const az_engine_cfg* c, az_engine** out) {
+  if (!c || !out) return fail(AZ_ERR_BAD_ARG, "NULL argument");
+  *out = nullptr;
+  GameInfo gi;
+  AZCHK(check_cfg(c, &gi));
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (c->device < 0 || c->device >= ndev) return fail(AZ_ERR_BAD_ARG, "device %d not available (%d visible)", c->device, ndev);
   HIPCHK(hipSetDevice(c->device));
-  az_engine* e = new (std::nothrow) az_engine();
+  az_engine* e = new (std::nothrow) az_engine();                      // (e->env: reads the creation-time overrides)
   if (!e) return fail(AZ_ERR_HIP, "out of host memory");
-  e->cfg = *c; e->gi = gi; e->device = c->device; e->stream = nullptr; e->ngroups = 0; e->alloc_bytes = 0;
-  e->vm_base = nullptr; e->vm_bytes = 0; e->vm_chunk = 0; e->vm_rows = 0; e->vm_chunk_nodes = 0; e->d_slot_cap = nullptr; e->vm_budget = 0; e->vm_mapped = 0;
-  e->vmk_base = nullptr; e->vmk_bytes = 0; e->vmk_piece = 0; e->tree_sort = 0; e->d_perm = nullptr; e->d_perm_prev = nullptr;
-  e->next_exec = 1.0;
-  e->h_env = nullptr; e->h_n = nullptr; e->h_pv = nullptr; e->h_nleaf = nullptr; e->d_nleaf = nullptr; e->h_needy = nullptr; e->d_needy = nullptr;
-  e->d_ec = nullptr; e->ec_mask = 0; e->ec_seq = 0; e->d_ec_claim = nullptr; e->d_Phit = nullptr; e->d_Vhit = nullptr;
-  e->fr_on = false; e->fr_k = 0; e->fr_kbg = 0; e->fr_round_waves = 0; for (int i = 0; i < 4; ++i) { e->fr_s[i] = nullptr; e->fr_ev[i] = nullptr; } e->d_fr = nullptr; e->d_done = nullptr; e->d_done_off = nullptr; e->done_cap = 0;
-  e->h_fr_words = nullptr; e->d_fr_words = nullptr; e->h_busy = nullptr; e->d_busy = nullptr; e->explore_k = 0; e->fr_prev_done = 0; e->fr_since_round = 0; e->fr_given_up = 0; e->fr_prev_recs = 0;
-  e->h_xflag = nullptr; e->d_xflag = nullptr; e->split_off = false; e->split_registered = 0; e->xch_launches = 0;
-  { const char* fa = getenv("AZHIP_XCH_FAIL_AT"); e->xch_fail_at = fa ? atoll(fa) : 0; }
-  e->net_loaded = false; e->running = false; e->prof_on = false; { const char* ug = getenv("AZHIP_GRAPH"); e->use_graphs = ug ? atoi(ug) : 0; }
-  e->d_phase = nullptr; e->phase_cap = 0; e->phase_n = 0; e->host_moves = true; e->last_tower[0] = 0; memset(e->tower_hist, 0, sizeof e->tower_hist); e->prof_mask = 0; e->prof_used = 0;
-  memset(&e->prof, 0, sizeof e->prof);
-  memset(&e->stats, 0, sizeof e->stats);
-  int st = [&]() -> int {
-    // The engine's own stream gets a hardware queue of its own (a stream made with a CU mask -- here: every CU -- is not folded
-    // into the runtime's pool of GPU_MAX_HW_QUEUES shared queues).  Two one-group engines searching side by side (the arena's two
-    // players) otherwise overlap or take turns depending on which pooled queue their streams happened to land on (DESIGN.md 6b:
-    // 5.6 s against 8.2 s for the same evaluation).  AZHIP_POOLED_QUEUE=1 keeps the runtime's assignment.
-    {
-      int ncu = 0;
-      HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
-      std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
-      for (int i = 0; i < ncu; ++i) mask[(size_t)i / 32] |= 1u << (i % 32);
-      if (getenv("AZHIP_POOLED_QUEUE") || ncu <= 0 || hipExtStreamCreateWithCUMask(&e->stream, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
-        (void)hipGetLastError();
-        e->stream = nullptr;
-        HIPCHK(hipStreamCreate(&e->stream));
-      }
-    }
-    const int G = c->num_workers;
-    DView& v = e->v;
-    memset(&v, 0, sizeof v);
-    v.G = G;
-    v.max_moves = c->max_moves_per_game > 0 ? c->max_moves_per_game : gi.max_plies;
-    v.max_depth = gi.max_plies + 1;
-    long long cap = c->max_nodes_per_slot;
-    if (cap <= 0) {
-      // Mancala has no fixed length (MAX_PLIES = 256 bounds the trace); self-play games of the shipped parameters last
-      // 30-70 plies, the pool holds 128 plies of new nodes per game between resets (288 GB of HBM pay for the margin);
-      // a longer game reports AZ_ERR_CAPACITY and max_nodes_per_slot raises the bound
-      long long plies = c->game == AZ_GAME_MANCALA ? 128 : gi.max_plies;
-      cap = (long long)c->num_iters_per_turn * plies * std::max(1, c->reset_every);
-      if (c->reset_every == 0) cap *= 4;
-      cap = std::max<long long>(cap, 1024);
-    }
-    if (cap > (1LL << 30)) return fail(AZ_ERR_BAD_ARG, "max_nodes_per_slot too large");
-    v.cap_nodes = (int)cap;
-    int hs = 1024;
-    while ((long long)hs * 2 < cap * 3) hs <<= 1;
-    v.ht_size = hs;
-    // test knobs for events that are rare at the shipped sizes: AZHIP_HT_TAG_BITS narrows the 16-bit tag of a table entry (unequal
-    // states then share tags and every probe chain is decided by the exact key compare), AZHIP_HT_EPOCH0 starts the 16-bit table
-    // epoch near its wrap (a reset past 0xfffe really clears the table)
-    { const char* tb = getenv("AZHIP_HT_TAG_BITS"); const int b = tb ? atoi(tb) : 16; v.tag_mask = b >= 16 ? 0xffffu : b <= 0 ? 0u : ((1u << b) - 1u); }
-    { const char* e0 = getenv("AZHIP_HT_EPOCH0"); const long x = e0 ? atol(e0) : 1; v.epoch0 = (uint32_t)(x >= 1 && x < 0xffff ? x : 1); }
-    AZCHK(dalloc(e, &v.sr, G)); AZCHK(dalloc(e, &v.game_id, G));
-    AZCHK(dalloc(e, &v.move_idx, G)); AZCHK(dalloc(e, &e->d_node_count, G));
-    AZCHK(dalloc(e, &v.worker_sim_id, G));
-    AZCHK(dalloc(e, &v.eta, (size_t)G * gi.APAD));
-    AZCHK(dalloc(e, &v.ht, (size_t)G * hs));
-    {
-      const size_t pool_bytes = (size_t)G * cap * gi.node_bytes;
-      const char* fv = getenv("AZHIP_VMM");                          // 1 / 0 force the mapped-on-demand pool on / off (tests)
-      const size_t chunk_nodes = VM_CHUNK / gi.node_bytes;
-      const bool pow2 = (chunk_nodes & (chunk_nodes - 1)) == 0 && chunk_nodes * gi.node_bytes == VM_CHUNK;
-      const bool want = fv ? atoi(fv) != 0 : pool_bytes > VM_THRESHOLD;
-      void* base = nullptr;
-      const int rows = (int)((cap + chunk_nodes - 1) / chunk_nodes);
-      const size_t vbytes = (size_t)rows * G * VM_CHUNK;
-      // a runtime without virtual memory management (or without room in the address space) gets the plain pool
-      const bool vm_ok = want && pow2 && (size_t)cap > chunk_nodes && gi.node_bytes > 0 &&
-                         hipMemAddressReserve(&base, vbytes, VM_CHUNK, nullptr, 0) == hipSuccess;
-      if (want && !vm_ok) (void)hipGetLastError();
-      if (vm_ok) {
-        e->vm_chunk = VM_CHUNK; e->vm_chunk_nodes = (int)chunk_nodes;
-        e->vm_rows = rows;
-        e->vm_bytes = vbytes;
-        e->vm_base = (char*)base;
-        e->vm_budget = ~(size_t)0;                                   // set once every fixed allocation of the engine is made (below)
-        v.nodes = e->vm_base;
-        int sh = 0; while (((size_t)1 << sh) < chunk_nodes) ++sh;
-        v.node_sh = sh; v.node_mask = (uint32_t)chunk_nodes - 1; v.node_row = (size_t)G * VM_CHUNK; v.node_stride = VM_CHUNK;
-        e->h_slot_cap.assign(G, 0); e->h_node_count.assign(G, 0);
-        AZCHK(dalloc(e, &e->d_slot_cap, G));
-        v.slot_cap = e->d_slot_cap;
-      } else {
-        AZCHK(dalloc(e, &v.nodes, pool_bytes, false));
-        v.node_sh = 31; v.node_mask = 0x7fffffffu; v.node_row = 0; v.node_stride = (size_t)cap * gi.node_bytes; v.slot_cap = nullptr;
-      }
-    }
-    AZCHK(dalloc(e, &v.path, (size_t)G * v.max_depth));
-    AZCHK(dalloc(e, &v.leaf_env, G));
-    AZCHK(dalloc(e, &v.eval_slots, (size_t)2 * G)); v.eval_stride = G;
-    AZCHK(dalloc(e, &v.bg_list, (size_t)2 * G)); AZCHK(dalloc(e, &v.bg_cnt, 2 * AZ_MAX_GROUPS));
-    AZCHK(dalloc(e, &v.n_eval, 2 * AZ_MAX_GROUPS));
-    {
-      // side records (state key + Vest, 32 B per node).  Plain pool: dense [G][cap][4].  Mapped-on-demand pool: a second virtual
-      // range whose pieces follow the node chunks (DView::keys), so that they cost 32 B per node that EXISTS -- dense they were
-      // 26.8 GB of BASELINE configs[3]'s 57 GB engine.  AZHIP_VMM_KEYS=0 keeps the dense array beside a mapped pool.
-      const char* fk = getenv("AZHIP_VMM_KEYS");
-      const size_t piece = (size_t)e->vm_chunk_nodes * 32;
-      void* kbase = nullptr;
-      bool mapped_keys = e->vm_rows > 0 && !(fk && atoi(fk) == 0) && piece > 0 && VM_CHUNK % piece == 0;
-      size_t kbytes = 0;
-      if (mapped_keys) {
-        kbytes = ((size_t)e->vm_rows * G * piece + VM_CHUNK - 1) / VM_CHUNK * VM_CHUNK;
-        if (hipMemAddressReserve(&kbase, kbytes, VM_CHUNK, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); mapped_keys = false; }
-      }
-      if (mapped_keys) {
-        e->vmk_base = (char*)kbase; e->vmk_bytes = kbytes; e->vmk_piece = piece;
-        e->vmk_granule.assign(kbytes / VM_CHUNK, 0);
-        v.keys = (unsigned long long*)kbase;
-        v.key_row = (size_t)G * piece / 8; v.key_stride = piece / 8;
-      } else {
-        AZCHK(dalloc(e, &v.keys, (size_t)G * cap * 4, false));
-        v.key_row = 0; v.key_stride = (size_t)cap * 4;
-        if (e->vm_rows) v.key_row = (size_t)e->vm_chunk_nodes * 4;   // dense array under a mapped pool: idx = (row, offset) again, rows of a slot are contiguous
-      }
-    }
-    hipLaunchKernelGGL(k_slot_records, dim3((G + 255) / 256), dim3(256), 0, e->stream, v, (int)SR_ZERO);   // epoch 1, no root, nothing else
-    AZCHK(dalloc(e, &v.Pout, (size_t)std::max(G, 1) * gi.APAD)); AZCHK(dalloc(e, &v.Vout, G));
-    {
-      // Evaluation cache (tree.h): on for the ResNet oracle -- what an evaluation costs there makes a repeated one worth a look-up.
-      // AZHIP_EVAL_CACHE=0 switches it off, =1 forces it on for the exact synthetic oracles as well (tests; never for the rollout
-      // oracle, whose answer depends on the simulation's RNG stream, nor under hipGraph replay: the launch number is a kernel argument).
-      // AZHIP_EVAL_CACHE_LOG2 = log2 of the number of 64-byte entries (default 24: 1 GB; a BASELINE phase evaluates 2-6 x 10^7 states).
-      const char* ce = getenv("AZHIP_EVAL_CACHE");
-      const bool on = ce ? atoi(ce) != 0 && c->oracle != AZ_ORACLE_ROLLOUT : c->oracle == AZ_ORACLE_RESNET;
-      if (on && !e->use_graphs) {
-        // sized from the workload: 8 x slots x simulations per move entries, 2^16 (4 MB) ... 2^24 (1 GB: BASELINE configs[1];
-        // a phase there evaluates 2-6 x 10^7 states) -- an 8-slot test engine and the 128-worker arena players no longer hold 1 GB each
-        const char* cl = getenv("AZHIP_EVAL_CACHE_LOG2");
-        int lg = 16;
-        while (lg < 24 && ((long long)1 << lg) < 8LL * G * std::max(1, c->num_iters_per_turn)) ++lg;
-        if (cl) lg = atoi(cl);
-        lg = std::min(std::max(lg, 4), 28);
-        AZCHK(dalloc(e, &e->d_ec, (size_t)1 << lg));                // zeroed: every entry EC_EMPTY
-        e->ec_mask = ((uint32_t)1 << lg) - 1u;
-        AZCHK(dalloc(e, &e->d_ec_claim, (size_t)2 * G, false));
-        HIPCHK(hipMemsetAsync(e->d_ec_claim, 0xff, sizeof(int) * 2 * (size_t)G, e->stream));
-        AZCHK(dalloc(e, &e->d_Phit, (size_t)G * gi.APAD)); AZCHK(dalloc(e, &e->d_Vhit, G));
-        v.ec = e->d_ec; v.ec_mask = e->ec_mask; v.ec_seq = 0; v.ec_claim = e->d_ec_claim; v.Phit = e->d_Phit; v.Vhit = e->d_Vhit;
-      }
-    }
-    AZCHK(dalloc(e, &v.trace, (size_t)G * v.max_moves)); AZCHK(dalloc(e, &v.grec, G));
-    AZCHK(dalloc(e, &v.finished, G)); AZCHK(dalloc(e, &v.err, 1));
-    // split tower fallback: one exchange word per slot group (+ one nobody sets for the whole-engine view), the counters of the
-    // k_tree launches that stood still meanwhile, and a host-mapped word the kernel raises so that the host notices without a sync
-    AZCHK(dalloc(e, &e->d_xerr, AZ_MAX_GROUPS + 1)); AZCHK(dalloc(e, &e->d_skipped, 2 * (AZ_MAX_GROUPS + 1)));
-    v.xerr = e->d_xerr + AZ_MAX_GROUPS; v.skipped = e->d_skipped + 2 * AZ_MAX_GROUPS;
-    HIPCHK(hipHostMalloc((void**)&e->h_xflag, sizeof(int), hipHostMallocMapped));
-    *e->h_xflag = 0;
-    HIPCHK(hipHostGetDevicePointer((void**)&e->d_xflag, e->h_xflag, 0));
-    HIPCHK(hipHostMalloc((void**)&e->h_nleaf, sizeof(int) * AZ_MAX_GROUPS, hipHostMallocMapped));
-    for (int g = 0; g < AZ_MAX_GROUPS; ++g) e->h_nleaf[g] = -1;      // nothing reported yet: launches are priced at their upper bound
-    HIPCHK(hipHostGetDevicePointer((void**)&e->d_nleaf, e->h_nleaf, 0));
-    HIPCHK(hipHostMalloc((void**)&e->h_needy, sizeof(int) * AZ_MAX_GROUPS, hipHostMallocMapped));
-    for (int g = 0; g < AZ_MAX_GROUPS; ++g) e->h_needy[g] = 0;
-    HIPCHK(hipHostGetDevicePointer((void**)&e->d_needy, e->h_needy, 0));
-    // free-running phases: the device's own bookkeeping (FRState) and two host-mapped progress words
-    AZCHK(dalloc(e, &e->d_fr, 1)); AZCHK(dalloc(e, &e->d_bg_stop, 1)); e->bg_seq = 0; e->bg_signal = false;
-    HIPCHK(hipHostMalloc((void**)&e->h_busy, sizeof(int) * AZ_MAX_GROUPS, hipHostMallocMapped));
-    for (int g = 0; g < AZ_MAX_GROUPS; ++g) e->h_busy[g] = -1;
-    HIPCHK(hipHostGetDevicePointer((void**)&e->d_busy, e->h_busy, 0));
-    { const char* ek = getenv("AZHIP_EXPLORE_K"); e->explore_k = ek ? atoi(ek) : 8; }
-    HIPCHK(hipHostMalloc((void**)&e->h_fr_words, sizeof(int) * 2, hipHostMallocMapped));
-    e->h_fr_words[0] = e->h_fr_words[1] = 0;
-    HIPCHK(hipHostGetDevicePointer((void**)&e->d_fr_words, e->h_fr_words, 0));
-
-    // staging
-    e->io_cap = std::max(G, 4096);
-    AZCHK(dalloc(e, &e->d_slots, e->io_cap)); AZCHK(dalloc(e, &e->d_gids, e->io_cap)); AZCHK(dalloc(e, &e->d_roots, e->io_cap));
-    AZCHK(dalloc(e, &e->d_moves, e->io_cap)); AZCHK(dalloc(e, &e->d_eta, (size_t)e->io_cap * AZ_MAX_ACTIONS));
-    AZCHK(dalloc(e, &e->d_offsets, e->io_cap)); AZCHK(dalloc(e, &e->d_stage, (size_t)G * v.max_moves));
-    AZCHK(dalloc(e, &e->d_keys, (size_t)2 * e->io_cap)); AZCHK(dalloc(e, &e->d_actions, e->io_cap));
-    AZCHK(dalloc(e, &e->d_next, (size_t)2 * e->io_cap)); AZCHK(dalloc(e, &e->d_term, e->io_cap)); AZCHK(dalloc(e, &e->d_reward, e->io_cap));
-    AZCHK(dalloc(e, &e->d_nodebuf, 512));
-    AZCHK(dalloc(e, &e->d_visits, (size_t)e->io_cap * (AZ_MAX_ACTIONS + 1)));
-    // network buffers
-    e->nn_cap = e->io_cap;
-    AZCHK(dalloc(e, &e->d_hfeat, (size_t)e->nn_cap * gi.P * std::max(64, c->num_filters), false));
-    AZCHK(dalloc(e, &e->d_X, (size_t)e->nn_cap * gi.C * gi.P)); AZCHK(dalloc(e, &e->d_A, (size_t)e->nn_cap * gi.A));
-    AZCHK(dalloc(e, &e->d_P, (size_t)e->nn_cap * std::max(16, gi.APAD))); AZCHK(dalloc(e, &e->d_V, e->nn_cap)); AZCHK(dalloc(e, &e->d_Pinv, e->nn_cap));
-    AZCHK(dalloc(e, &e->d_tmp_env, e->nn_cap)); AZCHK(dalloc(e, &e->d_iota, e->nn_cap)); AZCHK(dalloc(e, &e->d_ntmp, 1));
-    HIPCHK(hipHostMalloc((void**)&e->h_env, sizeof(GEnv) * (size_t)e->nn_cap, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void**)&e->h_n, sizeof(int), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void**)&e->h_pv, sizeof(float) * (size_t)e->nn_cap * (gi.A + 1), hipHostMallocDefault));
-    hipLaunchKernelGGL(k_iota, dim3((e->nn_cap + 255) / 256), dim3(256), 0, e->stream, e->d_iota, e->nn_cap);
-    memset(&e->net, 0, sizeof e->net);
-    memset(&e->net16, 0, sizeof e->net16);
-    { const char* tw = getenv("AZHIP_TOWER"); e->tower_pick = tw ? atoi(tw) : 0; }
-    { const char* mx = getenv("AZHIP_TOWER_MIXED"); e->tower_mixed = mx && atoi(mx) != 0; }
-    { const char* hd = getenv("AZHIP_HEADS"); e->heads_pick = hd ? atoi(hd) : 0; }
-    { const char* ep = getenv("AZHIP_XCH_EPOCH0"); e->xch_epoch = ep ? strtoull(ep, nullptr, 0) : 0; }   // tests: start k_tower16s' launch epoch near its 24-bit wrap
-    { hipDeviceProp_t pr; HIPCHK(hipGetDeviceProperties(&pr, c->device)); e->num_cu = pr.multiProcessorCount; }
-    AZCHK(net_set_kernel_attrs(e));
-    // round-5 experiments on k_tree (off by default, measured in profiles/r5/README.md): AZHIP_TREE_ATOMIC = 1 | 2
-    // backs up with no-return atomics (DView::bk_mode), AZHIP_TREE_SORT = 1 orders the slots of a launch by depth at every move step
-    { const char* ta = getenv("AZHIP_TREE_ATOMIC"); const int m = ta ? atoi(ta) : 0; v.bk_mode = m == 1 || m == 2 ? m : 0; }
-    { const char* ts = getenv("AZHIP_TREE_SORT"); e->tree_sort = ts && atoi(ts) != 0 ? 1 : 0; }
-    if (e->tree_sort) { AZCHK(dalloc(e, &e->d_perm, (size_t)2 * G)); AZCHK(dalloc(e, &e->d_perm_prev, (size_t)2 * G)); }
-    // slot groups
-    int ng = c->batch_size > 0 ? G / c->batch_size : 1;
-    if (ng < 1) ng = 1;
-    if (ng > AZ_MAX_GROUPS) ng = AZ_MAX_GROUPS;
-    while (ng > 1 && G % ng != 0) --ng;
-    const int Gh = G / ng;
-    // statistics accumulators: one record per k_tree workgroup of every slot group (and of the whole-engine view, used by the hooks)
-    const int blk_group = (Gh * gi.APAD + 255) / 256, blk_all = (G * gi.APAD + 255) / 256;
-    e->stat_words = (size_t)4 * ((size_t)blk_group * ng + blk_all);
-    AZCHK(dalloc(e, &v.stat, e->stat_words));
-    long long* stat_base = v.stat;
-    v.stat = stat_base + (size_t)4 * blk_group * ng;                 // the whole-engine view's records come after the groups'
-    for (int g = 0; g < ng; ++g) {
-      DView gv = v;
-      gv.stat = stat_base + (size_t)4 * blk_group * g;
-      const size_t o = (size_t)g * Gh;
-      gv.G = Gh; gv.slot0 = (int)o;
-      gv.sr += o; gv.game_id += o; gv.move_idx += o;
-      gv.worker_sim_id += o; gv.eta += o * gi.APAD;
-      gv.ht += o * hs; gv.nodes += o * v.node_stride; gv.path += o * v.max_depth;
-      if (gv.slot_cap) gv.slot_cap += o;
-      gv.leaf_env += o; gv.eval_slots += o; gv.bg_list += o; gv.bg_cnt += 2 * g;
-      if (gv.ec) { gv.ec_claim += 2 * o; gv.Phit += o * gi.APAD; gv.Vhit += o; }
-      gv.xerr = e->d_xerr + g; gv.skipped = e->d_skipped + 2 * g;
-      if (e->tree_sort) {                                            // group-relative order, identity until the first move step
-        gv.perm = e->d_perm + o;
-        hipLaunchKernelGGL(k_iota, dim3((Gh + 255) / 256), dim3(256), 0, e->stream, e->d_perm + o, Gh);
-      }
-      gv.needy_host = e->d_needy + g;
-      gv.nleaf_host = e->d_ec ? e->d_nleaf + g : nullptr;            // only the evaluation cache makes a wave's network batch differ from its active slots
-      gv.n_eval += 2 * g; gv.keys += o * v.key_stride; gv.Pout += o * gi.APAD; gv.Vout += o; gv.trace += o * v.max_moves; gv.grec += o; gv.finished += o;
-      e->gv[g] = gv;
-      if (ng == 1) {
-        e->gs[g] = e->gt[g] = e->stream;
-        // a free-running phase runs the group's tree kernels under its own network launch: two streams for that (az_selfplay_begin / _end)
-        int lo = 0, hi = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIPCHK(hipStreamCreateWithPriority(&e->fr_s[0], hipStreamNonBlocking, hi));
-        HIPCHK(hipStreamCreateWithPriority(&e->fr_s[1], hipStreamNonBlocking, hi));
-        HIPCHK(hipStreamCreateWithPriority(&e->fr_s[2], hipStreamNonBlocking, hi));
-        HIPCHK(hipStreamCreateWithPriority(&e->fr_s[3], hipStreamNonBlocking, hi));
-        for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreateWithFlags(&e->fr_ev[i], hipEventDisableTiming));
-      } else {
-        // the short latency-bound tree kernels must not queue behind the other group's tower workgroups:
-        // they get the high-priority queue, the tower the normal one
-        int lo = 0, hi = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIPCHK(hipStreamCreateWithPriority(&e->gs[g], hipStreamNonBlocking, hi));
-        HIPCHK(hipStreamCreateWithPriority(&e->gt[g], hipStreamNonBlocking, lo));
-        HIPCHK(hipEventCreateWithFlags(&e->ev_tree[g], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&e->ev_net[g], hipEventDisableTiming));
-      }
-      AZCHK(dalloc(e, &e->g_hfeat[g], (size_t)Gh * gi.P * std::max(64, c->num_filters), false));
-      e->ngroups = g + 1;
-    }
-    // search parameters
-    DParams& p = e->p;
-    memset(&p, 0, sizeof p);
-    p.gamma = c->gamma; p.cpuct = c->cpuct; p.eps = c->dirichlet_noise_eps; p.alpha = c->dirichlet_noise_alpha;
-    p.prior_temp = c->prior_temperature; p.nsims = c->num_iters_per_turn; p.temp_len = c->temperature_len;
-    for (int i = 0; i < AZ_SCHED_MAX; ++i) { p.temp_xs[i] = c->temperature_xs[i]; p.temp_ys[i] = c->temperature_ys[i]; }
-    p.seed = c->seed; p.oracle = c->oracle; p.reset_every = c->reset_every; p.retire = 0;
-    p.flip_p = c->flip_probability;                                  // read by the self-play kernels only (k_move, k_start_games without roots)
-    if (e->vm_rows) {
-      // Budget of the growing pool: what the device has left AFTER this engine's fixed allocations, minus what is
-      // still to come -- the phase buffer of a bounded phase (num_workers x 4 games of move records is the usual order), the
-      // replay memory / trainer of the same process -- as a margin of 1/8 of the device, at least 4 GB.  AZHIP_POOL_GB overrides.
-      size_t fr = 0, tot = 0;
-      HIPCHK(hipMemGetInfo(&fr, &tot));
-      const size_t margin = std::max<size_t>(tot / 8, (size_t)4 << 30);
-      const char* gb = getenv("AZHIP_POOL_GB");
-      e->vm_budget = gb ? (size_t)(atof(gb) * (double)((size_t)1 << 30)) : (fr > margin ? fr - margin : fr / 2);
-      AZCHK(vm_grow(e, 1));                                          // the first chunk of every slot
-    }
-    e->h_finished.resize(G); e->h_grec.resize(G);
-    e->prof_pool.resize(2048);
-    for (auto& r : e->prof_pool) { HIPCHK(hipEventCreate(&r.a)); HIPCHK(hipEventCreate(&r.b)); }
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipGetLastError());
-    return AZ_OK;
-  }();
+  e->cfg = *c; e->gi = gi; e->device = c->device;
+  int st = AZ_OK;
+  for (auto step : CREATE_STEPS) if (st == AZ_OK) st = step(e);
   if (st != AZ_OK) { std::string keep = g_err; az_engine_destroy(e); g_err = keep; return st; }
   *out = e;
   return AZ_OK;
@@ -998,8 +984,7 @@ template <class Gm> static int wave_group(az_engine* e, int g, uint32_t sim_idx)
   const bool side = e->fr_on && !split && e->cfg.oracle == AZ_ORACLE_RESNET && e->fr_s[1] && st == e->fr_s[0];
   // (the stop word of the background search: without it a background launch of fr_kbg simulations outlasts a SHORT tower and the next wave
   // waits for it -- Mancala, 8192 slots: 19.8 instead of 39.7 M sims/s; AZHIP_BG_STOP=0 switches it off)
-  static const bool bg_stop_on = !(getenv("AZHIP_BG_STOP") && atoi(getenv("AZHIP_BG_STOP")) == 0);
-  if (side) { s2 = e->fr_s[1]; HIPCHK(hipEventRecord(e->fr_ev[0], st)); ++e->bg_seq; e->bg_signal = bg_stop_on && e->fr_kbg > 0; }
+  if (side) { s2 = e->fr_s[1]; HIPCHK(hipEventRecord(e->fr_ev[0], st)); ++e->bg_seq; e->bg_signal = env_process().bg_stop && e->fr_kbg > 0; }
   if (e->cfg.oracle == AZ_ORACLE_RESNET) {
     AZCHK(net_wave(e, g, split, e->group_active[g]));
   } else {
@@ -1013,16 +998,15 @@ template <class Gm> static int wave_group(az_engine* e, int g, uint32_t sim_idx)
     fa.st = e->d_fr; fa.done = e->d_done; fa.done_off = e->d_done_off;
     fa.recs = e->d_phase ? e->d_phase : e->d_stage; fa.recs_cap = e->d_phase ? (long long)e->phase_cap : (long long)e->v.G * e->v.max_moves;
     fa.done_cap = e->done_cap; fa.total_games = e->total_games; fa.first_game_id = (uint32_t)e->first_game_id; fa.group = g; fa.host_words = e->d_fr_words;
-    static const int bg_prio = getenv("AZHIP_BG_PRIO") ? atoi(getenv("AZHIP_BG_PRIO")) : 0;   // A/B aid: 3 = the background launches keep the wave launches' priority
     // (side streams: the move step and the background search touch different slots -- explore! complete / still searching -- and run
     // side by side: one serial move under a busy tower takes 0.4 ms, which the background search would otherwise wait out)
     hipStream_t s3 = side ? e->fr_s[2] : s2;
     if (side) { HIPCHK(hipStreamWaitEvent(s2, e->fr_ev[0], 0)); HIPCHK(hipStreamWaitEvent(s3, e->fr_ev[0], 0)); }
-    { DView mv = v; mv.low_prio = bg_prio ? 0 : 1; LAUNCH_ON(e, s3, AZ_K_MOVE, G, (k_move_fr<Gm>), (G + 255) / 256, 256, 0, mv, e->p, fa); }
+    { DView mv = v; mv.low_prio = env_process().bg_prio ? 0 : 1; LAUNCH_ON(e, s3, AZ_K_MOVE, G, (k_move_fr<Gm>), (G + 255) / 256, 256, 0, mv, e->p, fa); }
     if (e->fr_kbg > 0) {
       AZCHK(ec_next_launch(e, &e->gv[g]));
       DView bv = e->gv[g];
-      bv.run_k = e->fr_kbg; bv.low_prio = bg_prio ? 0 : 1;
+      bv.run_k = e->fr_kbg; bv.low_prio = env_process().bg_prio ? 0 : 1;
       if (side && e->bg_signal) { bv.bg_stop = e->d_bg_stop; bv.bg_seq = e->bg_seq; }   // ... until the wave's tower has run (net_impl.h sets the word)
       LAUNCH_ON(e, s2, AZ_K_EXPAND, G, (k_tree<Gm>), gb, 256, 0, bv, e->p, 0, 1, par ^ 1);
     }
@@ -1126,7 +1110,7 @@ template <class Gm> static int wave_pair_graph(az_engine* e, hipGraphExec_t* out
 // runs up to `n` waves of the current explore! (all slot groups); returns how many it ran
 template <class Gm> static int run_waves(az_engine* e, int nga, int n, uint32_t sim0) {
   int done = 0;
-  const bool graphable = e->use_graphs && e->ngroups == 1 && nga == 1 && !e->prof_on && e->cfg.oracle != AZ_ORACLE_ROLLOUT && e->group_active[0] > 0;
+  const bool graphable = e->env.use_graphs && e->ngroups == 1 && nga == 1 && !e->prof_on && e->cfg.oracle != AZ_ORACLE_ROLLOUT && e->group_active[0] > 0;
   while (done < n) {
     if (graphable && n - done >= 2 && e->pending[0] && e->wave_par[0] == 0) {
       hipGraphExec_t ex = nullptr;
@@ -1202,8 +1186,8 @@ static int explore_begin(az_engine* e, const std::vector<int>& slots, const std:
   // (round 6) the explore! runs ahead: inside one launch a slot completes every simulation that ends on a terminal state or on a
   // state the evaluation cache answers (tree.h k_tree, run_k > 0 with fr = 0), every slot exactly nsims of them; the host launches
   // waves until the device reports nobody busy (explore_waves).  Not for the rollout oracle (keyed by the wave's index) nor under hipGraph replay.
-  const bool ahead = e->explore_k > 1 && e->cfg.oracle != AZ_ORACLE_ROLLOUT && !e->use_graphs && !e->tree_sort;
-  for (int g = 0; g < e->ngroups; ++g) { e->gv[g].run_k = ahead ? e->explore_k : 0; e->gv[g].fr = 0; e->gv[g].busy_host = ahead ? e->d_busy + g : nullptr; e->h_busy[g] = -1; }
+  const bool ahead = e->env.explore_k > 1 && e->cfg.oracle != AZ_ORACLE_ROLLOUT && !e->env.use_graphs && !e->env.tree_sort;
+  for (int g = 0; g < e->ngroups; ++g) { e->gv[g].run_k = ahead ? e->env.explore_k : 0; e->gv[g].fr = 0; e->gv[g].busy_host = ahead ? e->d_busy + g : nullptr; e->h_busy[g] = -1; }
   return AZ_OK;
 }
 // the waves of an explore! of `nsims` simulations per slot on `nga` slot groups: nsims lock-step waves, or -- running ahead -- as many
@@ -1380,17 +1364,13 @@ extern "C" int az_selfplay_begin(az_engine* e, int32_t num_games, int32_t first_
   {
     // free-running or lock step (az_engine_cfg.lock_step; AZHIP_FREE_RUN=0|1 overrides).  Always lock step: the rollout oracle (its
     // answer is keyed by the simulation's index in the wave sequence), hipGraph replay (fixed launch sequences), the depth-ordering experiment
-    const char* fr = getenv("AZHIP_FREE_RUN");
-    const bool want = fr ? atoi(fr) != 0 : e->cfg.lock_step == 0;
-    const bool on = want && e->cfg.oracle != AZ_ORACLE_ROLLOUT && !e->use_graphs && !e->tree_sort;
-    const char* rk = getenv("AZHIP_RUN_K"); const char* rw = getenv("AZHIP_FR_ROUND");
-    const char* rb = getenv("AZHIP_RUN_KBG");
+    const EnvPhase ph;                                                // AZHIP_FREE_RUN, AZHIP_RUN_K, AZHIP_RUN_KBG, AZHIP_FR_ROUND
+    const bool want = ph.free_run >= 0 ? ph.free_run != 0 : e->cfg.lock_step == 0;
+    const bool on = want && e->cfg.oracle != AZ_ORACLE_ROLLOUT && !e->env.use_graphs && !e->env.tree_sort;
     // wave launch: up to 3 simulations per slot (it is on the wave's critical path: 35 / 50 / 62 / 75 us for 1 / 2 / 3 / 4 at 4096 slots);
     // background launch: one slot group -- up to 32 more, or until the tower has run (the stop word); several groups -- a few (it runs on
     // the group's tree stream, ahead of the next wave's launch).  profiles/r6/README.md has the sweeps.
-    e->fr_k = std::max(1, rk ? atoi(rk) : 3);
-    e->fr_kbg = std::max(0, rb ? atoi(rb) : (e->ngroups == 1 ? 32 : 8));
-    e->fr_round_waves = std::max(1, rw ? atoi(rw) : 128);
+    e->fr_k = ph.run_k; e->fr_kbg = ph.run_kbg >= 0 ? ph.run_kbg : (e->ngroups == 1 ? 32 : 8); e->fr_round_waves = ph.round_waves;
     if (on) {
       const int want_cap = num_games > 0 ? num_games : G;
       if (want_cap > e->done_cap) {
@@ -1440,7 +1420,7 @@ template <class Gm> static int move_round(az_engine* e) {
     if (*(volatile int*)e->h_xflag) { AZCHK(recover_split<Gm>(e)); AZCHK(flush_pending<Gm>(e)); AZCHK(sync_all(e)); }
   }
   LAUNCH(e, AZ_K_MOVE, G, (k_move<Gm>), (G + 255) / 256, 256, 0, e->v, e->p);
-  if (e->tree_sort)                                                // the explore! that just ended says how deep each slot searches now
+  if (e->env.tree_sort)                                                // the explore! that just ended says how deep each slot searches now
     for (int g = 0; g < e->ngroups; ++g) {
       const size_t o = (size_t)g * e->gv[0].G;
       hipLaunchKernelGGL(k_depth_order, dim3(1), dim3(1024), 0, e->stream, e->gv[g], e->d_perm_prev + 2 * o, e->d_perm + o, e->d_perm + G + o);
@@ -1933,7 +1913,7 @@ extern "C" int az_arena_run(az_engine* contender, az_engine* baseline, int32_t n
   for (az_engine* e : {contender, baseline})
     if (e->cfg.oracle == AZ_ORACLE_RESNET && !e->net_loaded) return fail(AZ_ERR_STATE, "az_net_set_params has not been called");
   if (out && (!out->games || !out->moves)) return fail(AZ_ERR_BAD_ARG, "NULL trace buffers");
-  const bool trace = getenv("AZHIP_TRACE_ARENA") != nullptr;      // which tower forms served the evaluation, and who else counted as a split-tower user
+  const bool trace = EnvArena().trace;     // which tower forms served the evaluation, and who else counted as a split-tower user
   long long h0[2][4];
   const int others = split_streams_on_device(contender->device);
   for (int k = 0; k < 2; ++k) memcpy(h0[k], (k ? baseline : contender)->tower_hist, sizeof h0[k]);

@@ -53,7 +53,7 @@ static int load() {
   if (g.so) return AZ_OK;
   void* so = nullptr;
   Dl_info info;
-  const char* forced = getenv("AZHIP_RCCL_LIB");
+  const char* forced = EnvComm().rccl_lib;
   if (forced && *forced) {
     // a transport seam for the tests (several ranks on one GPU: tests/rccl_stub), not a plug-in point: only a library that calls
     // itself librccl* is accepted, and it must export the NCCL entry points below like the real one

@@ -18,6 +18,7 @@
 
 #include "../../include/az_numerics.h"
 #include "../../include/azhip.h"
+#include "env.h"
 #include "games.h"
 #include "resnet.h"
 #include "resnet16.h"
@@ -58,7 +59,7 @@ inline bool game_info(int gid, GameInfo* gi) {
 }
 
 // ------------------------------------------------------------------------------- engine
-// The tower forms.  The values are the AZHIP_TOWER numbers (az_engine::tower_pick); net_impl.h holds one descriptor per form
+// The tower forms.  The values are the AZHIP_TOWER numbers (az_engine::env.tower_pick); net_impl.h holds one descriptor per form
 // (kernel, layout, geometry table, availability, name, tower_hist bucket) and pick_tower, which chooses among them.
 enum TowerForm : int {
   TW_AUTO = 0,     // AZHIP_TOWER unset: pick_tower chooses per launch
@@ -75,111 +76,111 @@ enum TowerForm : int {
 };
 // AZ_MAX_GROUPS: tree.h
 struct ProfRec { hipEvent_t a = nullptr, b = nullptr; int cls = 0; };
+// Every member has its initial value here: az_engine_create builds the record step by step and az_engine_destroy takes it apart at
+// any point in between.  DView / DParams go to the kernels by value and stay trivially copyable (memset by the step that fills them).
 struct az_engine {
-  az_engine_cfg cfg;
-  GameInfo gi;
-  int device;
-  hipStream_t stream;
-  DView v;                       // global view over all G slots (start / move / hooks)
-  DParams p;
+  az_engine_cfg cfg = {};
+  GameInfo gi = {};
+  EnvCreate env;                 // the AZHIP_* overrides, read when az_engine_create constructs this record (env.h): forced kernels, experiments, test knobs
+  int device = 0;
+  hipStream_t stream = nullptr;
+  DView v = {};                     // global view over all G slots (start / move / hooks)
+  DParams p = {};
   // slot groups: num_workers / batch_size interleaved half-batches, each with its own stream, so the
   // tree kernels of one group run under the network of another (the device form of the reference's
   // num_workers = 2 x batch_size, games/connect-four/params.jl:18-19)
-  int ngroups;
-  DView gv[AZ_MAX_GROUPS];
-  hipStream_t gs[AZ_MAX_GROUPS];      // tree-kernel stream of the group (high priority when ngroups > 1)
-  hipStream_t gt[AZ_MAX_GROUPS];      // network stream of the group
-  hipEvent_t ev_tree[AZ_MAX_GROUPS], ev_net[AZ_MAX_GROUPS];
-  float* g_hfeat[AZ_MAX_GROUPS];
+  int ngroups = 0;
+  DView gv[AZ_MAX_GROUPS] = {};
+  hipStream_t gs[AZ_MAX_GROUPS] = {};      // tree-kernel stream of the group (high priority when ngroups > 1)
+  hipStream_t gt[AZ_MAX_GROUPS] = {};      // network stream of the group
+  hipEvent_t ev_tree[AZ_MAX_GROUPS] = {}, ev_net[AZ_MAX_GROUPS] = {};
+  float* g_hfeat[AZ_MAX_GROUPS] = {};
   // k_tower16s (split tower, 128 filters): publish areas per feature buffer (slot g = group g, AZ_MAX_GROUPS = d_hfeat), launch epoch
-  unsigned long long* xch[AZ_MAX_GROUPS + 1]; unsigned long long xch_epoch;
+  unsigned long long* xch[AZ_MAX_GROUPS + 1] = {}; unsigned long long xch_epoch = 0;   // (first epoch: env.xch_epoch0)
   // (r4) a split tower whose exchange gives up degrades instead of failing the phase (azhip.hip recover_split)
-  int* d_xerr; int* d_skipped;   // [AZ_MAX_GROUPS + 1] exchange words, [..][2] counters of idle k_tree launches (DView::xerr / skipped)
-  int* h_needy; int* d_needy;    // [AZ_MAX_GROUPS] host-mapped: slots each group's previous wave launch left to the background search (tree.h DView::needy_host)
-  int* h_nleaf; int* d_nleaf;    // [AZ_MAX_GROUPS] host-mapped: network batch of each group's previous wave (k_tree writes, pick_tower's estimate reads)
-  int* h_xflag; int* d_xflag;    // host-mapped word the kernel sets when an exchange gives up; looked at before every launch
-  bool split_off;                // the split is disabled for this engine after the first time
-  long long xch_fail_at, xch_launches;   // AZHIP_XCH_FAIL_AT = n: the n-th split launch loses a partner (fault injection for the tests)
-  int split_registered;          // streams this engine contributes to the device's count of split-tower users
+  int* d_xerr = nullptr; int* d_skipped = nullptr;   // [AZ_MAX_GROUPS + 1] exchange words, [..][2] counters of idle k_tree launches (DView::xerr / skipped)
+  int* h_needy = nullptr; int* d_needy = nullptr;    // [AZ_MAX_GROUPS] host-mapped: slots each group's previous wave launch left to the background search (tree.h DView::needy_host)
+  int* h_nleaf = nullptr; int* d_nleaf = nullptr;    // [AZ_MAX_GROUPS] host-mapped: network batch of each group's previous wave (k_tree writes, pick_tower's estimate reads); -1 = nothing reported yet
+  int* h_xflag = nullptr; int* d_xflag = nullptr;    // host-mapped word the kernel sets when an exchange gives up; looked at before every launch
+  bool split_off = false;        // the split is disabled for this engine after the first time
+  long long xch_launches = 0;    // split launches so far (env.xch_fail_at: the n-th loses a partner)
+  int split_registered = 0;      // streams this engine contributes to the device's count of split-tower users
   std::vector<void*> allocs;
-  size_t alloc_bytes;              // device bytes behind `allocs` (az_engine_device_bytes)
+  size_t alloc_bytes = 0;          // device bytes behind `allocs` (az_engine_device_bytes)
+  std::vector<void*> host_allocs;  // hipHostMalloc'ed: the host-mapped words (halloc_mapped) and the pinned staging buffers (halloc_pinned)
   // node pool mapped on demand (azhip.hip "node pool"): a virtual range of rows x G chunks of 2 MB; chunk (row r, slot s) is
   // backed when slot s is about to need it.  vm_rows = 0: plain hipMalloc pool.
-  char* vm_base; size_t vm_bytes, vm_chunk; int vm_rows, vm_chunk_nodes;
+  char* vm_base = nullptr; size_t vm_bytes = 0, vm_chunk = 0; int vm_rows = 0, vm_chunk_nodes = 0;
   std::vector<hipMemGenericAllocationHandle_t> vm_handles; std::vector<char*> vm_at;
-  std::vector<int> h_slot_cap, h_node_count; int* d_slot_cap; int* d_node_count; size_t vm_budget, vm_mapped;
+  std::vector<int> h_slot_cap, h_node_count; int* d_slot_cap = nullptr; int* d_node_count = nullptr; size_t vm_budget = 0, vm_mapped = 0;
   // (r5) the side records of a mapped-on-demand pool follow the node chunks: a second virtual range of rows x G pieces of
   // vm_chunk_nodes x 32 B, backed by 2 MB granules (vmk_granule[i] = granule i is mapped); vmk_base = NULL: dense [G][cap][4] array
-  char* vmk_base; size_t vmk_bytes, vmk_piece; std::vector<uint8_t> vmk_granule;
-  // (r5 experiments) AZHIP_TREE_SORT: slot order of k_tree by the depth of the last explore! (d_perm [G] order | [G] keys,
-  // d_perm_prev [G][2] totals at the last move step); AZHIP_TREE_ATOMIC: DView::bk_mode
-  int tree_sort; int* d_perm; long long* d_perm_prev;
+  char* vmk_base = nullptr; size_t vmk_bytes = 0, vmk_piece = 0; std::vector<uint8_t> vmk_granule;
+  // (r5 experiments) env.tree_sort: slot order of k_tree by the depth of the last explore! (d_perm [G] order | [G] keys,
+  // d_perm_prev [G][2] totals at the last move step)
+  int* d_perm = nullptr; long long* d_perm_prev = nullptr;
   // evaluation cache (tree.h ECEnt): one table per engine = per network; az_net_set_params empties it
-  ECEnt* d_ec; uint32_t ec_mask; uint32_t ec_seq; int* d_ec_claim; float* d_Phit; float* d_Vhit;
-  size_t stat_words; std::vector<long long> h_stat;   // per-workgroup statistics accumulators of k_tree (DView::stat), summed on request
+  ECEnt* d_ec = nullptr; uint32_t ec_mask = 0; uint32_t ec_seq = 0; int* d_ec_claim = nullptr; float* d_Phit = nullptr; float* d_Vhit = nullptr;
+  size_t stat_words = 0; std::vector<long long> h_stat;   // per-workgroup statistics accumulators of k_tree (DView::stat), summed on request
   std::vector<int32_t> aborted_ids;   // games retired because their slot ran out of nodes / move records (az_selfplay_aborted)
   std::vector<void*> net_allocs;   // device copies of the packed network (replaced by az_net_set_params)
   // network
-  bool net_loaded;
+  bool net_loaded = false;
   std::vector<float> blob;
-  NetDev net;
-  Net16bDev net16b;              // bf16 fragments (cfg.net_bf16)
-  Net16Dev net16;                // k_tower16 fragments (64 filters)
-  uint16_t* d_geo[GEO_COUNT];    // Geo16 tables by GeoSlot (resnet16.h); GEO_NTM is NULL where the game has no exact-fit variant
-  long long tower_hist[4];       // network launches served by: the split tower, the 3-row-tile form, the packed 11 / 21-tile forms, others (AZHIP_TRACE_ARENA)
-  char last_tower[96];           // name of the tower kernel that served the most recent network launch (az_net_last_kernel)
-  int heads_pick;                // AZHIP_HEADS=16|32 forces k_heads16 / k_heads_mfma; 0 = by launch size
-  int tower_pick;                // AZHIP_TOWER = a TowerForm value (2 | 3 | 7 | 16 | 19 | 20 | 21 | 22 | 32) forces that form where it exists; 0 = choose per launch
-  bool tower_mixed;              // AZHIP_TOWER_MIXED=1: a free-running wave of 15 .. 16 boards per CU goes out as one k_tower16x2m launch (measured slower: wave_net_f)
-  int num_cu;
-  int nn_cap;
-  float* d_hfeat; float* d_X; float* d_A; float* d_P; float* d_V; float* d_Pinv;
-  GEnv* d_tmp_env; int* d_iota; int* d_ntmp;
+  NetDev net = {};
+  Net16bDev net16b = {};         // bf16 fragments (cfg.net_bf16)
+  Net16Dev net16 = {};           // k_tower16 fragments (64 filters)
+  uint16_t* d_geo[GEO_COUNT] = {};   // Geo16 tables by GeoSlot (resnet16.h); GEO_NTM is NULL where the game has no exact-fit variant
+  long long tower_hist[4] = {};  // network launches served by: the split tower, the 3-row-tile form, the packed 11 / 21-tile forms, others (AZHIP_TRACE_ARENA)
+  char last_tower[96] = {};      // name of the tower kernel that served the most recent network launch (az_net_last_kernel)
+  int num_cu = 0;
+  int nn_cap = 0;
+  float* d_hfeat = nullptr; float* d_X = nullptr; float* d_A = nullptr; float* d_P = nullptr; float* d_V = nullptr; float* d_Pinv = nullptr;
+  GEnv* d_tmp_env = nullptr; int* d_iota = nullptr; int* d_ntmp = nullptr;
   // pinned staging of the key-based network seam (az_net_evaluate_keys): states + count in, P / V out -- pageable copies were most of a call
-  GEnv* h_env; int* h_n; float* h_pv;
+  GEnv* h_env = nullptr; int* h_n = nullptr; float* h_pv = nullptr;
   // staging
-  int* d_slots; uint32_t* d_gids; GEnv* d_roots; uint32_t* d_moves; double* d_eta; int* d_offsets;
-  az_move_rec* d_stage; unsigned long long* d_keys; int* d_actions; unsigned long long* d_next; signed char* d_term; float* d_reward;
-  char* d_nodebuf;
-  int* d_visits;
-  int io_cap;
+  int* d_slots = nullptr; uint32_t* d_gids = nullptr; GEnv* d_roots = nullptr; uint32_t* d_moves = nullptr; double* d_eta = nullptr; int* d_offsets = nullptr;
+  az_move_rec* d_stage = nullptr; unsigned long long* d_keys = nullptr; int* d_actions = nullptr; unsigned long long* d_next = nullptr; signed char* d_term = nullptr; float* d_reward = nullptr;
+  char* d_nodebuf = nullptr;
+  int* d_visits = nullptr;
+  int io_cap = 0;
   // self-play state
-  bool running;
-  int total_games, next_game, first_game_id, games_done, wave_in_move, active_slots;
-  // hipGraphs of wave pairs (one slot group only): key = upper bound of the leaves of a launch (decides the tower kernel and
-  // its grid); rebuilt after az_net_set_params (new device pointers)
-  std::map<int, hipGraphExec_t> wave_graphs; int use_graphs;
-  bool pending[AZ_MAX_GROUPS];       // the group's last wave awaits its expand + backup (flush_pending)
-  int wave_par[AZ_MAX_GROUPS];       // parity of the group's last wave: which of its two leaf counters is current
-  int group_active[AZ_MAX_GROUPS];   // active slots per slot group (host count; bounds the leaves of a network launch)
+  bool running = false;
+  int total_games = 0, next_game = 0, first_game_id = 0, games_done = 0, wave_in_move = 0, active_slots = 0;
+  // hipGraphs of wave pairs (env.use_graphs, one slot group only): key = upper bound of the leaves of a launch (decides the tower
+  // kernel and its grid); rebuilt after az_net_set_params (new device pointers)
+  std::map<int, hipGraphExec_t> wave_graphs;
+  bool pending[AZ_MAX_GROUPS] = {};       // the group's last wave awaits its expand + backup (flush_pending)
+  int wave_par[AZ_MAX_GROUPS] = {};       // parity of the group's last wave: which of its two leaf counters is current
+  int group_active[AZ_MAX_GROUPS] = {};   // active slots per slot group (host count; bounds the leaves of a network launch)
   // (r6) free-running phases (az_engine_cfg.lock_step = 0; tree.h k_tree / k_move_fr): the device hands out game ids and writes
   // finished games into the phase buffer itself; the host looks every fr_round_waves waves (fr_round, azhip.hip)
-  bool fr_on;                        // the phase in progress is free-running
-  int fr_k, fr_kbg, fr_round_waves;  // simulations a slot may select per wave launch / per background launch (DView::run_k); waves between two looks of the host
-  hipStream_t fr_s[4]; hipEvent_t fr_ev[4];   // one slot group: the tree / network streams and events of its free-running phases (gs[0] / gt[0] / ev_* point at them meanwhile)
-  FRState* d_fr; az_game_rec* d_done; long long* d_done_off; int done_cap;
-  int* h_busy; int* d_busy;      // [AZ_MAX_GROUPS] host-mapped: slots of each group still inside an explore! that runs ahead (DView::busy_host)
-  int explore_k;                 // simulations per slot and launch inside MCTS.explore! of the hooks and the arena (AZHIP_EXPLORE_K; 0 / 1 = lock step)
-  int* d_bg_stop; int bg_seq; bool bg_signal;   // the background search's stop word: set to bg_seq on the wave's stream once its tower has run (bg_signal: this wave has one)
-  int* h_fr_words; int* d_fr_words;  // host-mapped: finished games / searching slots as of the previous wave (FRArgs::host_words)
-  int fr_prev_done, fr_since_round, fr_given_up; long long fr_prev_recs;
+  bool fr_on = false;                // the phase in progress is free-running
+  int fr_k = 0, fr_kbg = 0, fr_round_waves = 0;  // simulations a slot may select per wave launch / per background launch (DView::run_k); waves between two looks of the host
+  hipStream_t fr_s[4] = {}; hipEvent_t fr_ev[4] = {};   // one slot group: the tree / network streams and events of its free-running phases (gs[0] / gt[0] / ev_* point at them meanwhile)
+  FRState* d_fr = nullptr; az_game_rec* d_done = nullptr; long long* d_done_off = nullptr; int done_cap = 0;
+  int* h_busy = nullptr; int* d_busy = nullptr;      // [AZ_MAX_GROUPS] host-mapped: slots of each group still inside an explore! that runs ahead (DView::busy_host); -1 = no report
+  int* d_bg_stop = nullptr; int bg_seq = 0; bool bg_signal = false;   // the background search's stop word: set to bg_seq on the wave's stream once its tower has run (bg_signal: this wave has one)
+  int* h_fr_words = nullptr; int* d_fr_words = nullptr;  // host-mapped: finished games / searching slots as of the previous wave (FRArgs::host_words)
+  int fr_prev_done = 0, fr_since_round = 0, fr_given_up = 0; long long fr_prev_recs = 0;
   std::vector<az_game_rec> h_done; std::vector<long long> h_done_off;
   std::vector<az_game_rec> q_games;
   std::vector<az_move_rec> q_moves;
   // device-resident records of the current phase (az_selfplay_run / begin with num_games > 0): the move records of every
   // finished game stay in HBM (d_phase, game after game in finishing order)
-  az_move_rec* d_phase; int64_t phase_cap, phase_n; bool host_moves;
+  az_move_rec* d_phase = nullptr; int64_t phase_cap = 0, phase_n = 0; bool host_moves = true;
   std::vector<az_game_rec> ph_games;
   std::vector<int64_t> ph_off;       // offset of each ph_games entry's first move record in d_phase
-  az_selfplay_stats stats;
+  az_selfplay_stats stats = {};
   std::chrono::steady_clock::time_point t_begin;
   // profiling
-  bool prof_on;
-  int prof_mask;                 // 0 = every kernel class, else bit per az_kernel_class
+  bool prof_on = false;
+  int prof_mask = 0;             // 0 = every kernel class, else bit per az_kernel_class
   std::vector<ProfRec> prof_pool;
-  size_t prof_used;
-  az_prof prof;
-  double next_exec;              // executed-product fraction of the NEXT profiled launch (set by the tower launches, consumed by prof_begin)
+  size_t prof_used = 0;
+  az_prof prof = {};
+  double next_exec = 1.0;        // executed-product fraction of the NEXT profiled launch (set by the tower launches, consumed by prof_begin)
   std::vector<int> h_finished;
   std::vector<az_game_rec> h_grec;
 };
@@ -193,6 +194,20 @@ template <class T> inline int dalloc(az_engine* e, T** p, size_t n, bool zero = 
   e->alloc_bytes += bytes;
   if (zero) HIPCHK(hipMemsetAsync(q, 0, bytes, e->stream));
   *p = (T*)q;
+  return AZ_OK;
+}
+
+// pinned staging: copies from / to it are real asynchronous DMA
+template <class T> inline int halloc_pinned(az_engine* e, T** h, size_t n, unsigned flags = hipHostMallocDefault) {
+  HIPCHK(hipHostMalloc((void**)h, sizeof(T) * n, flags));
+  e->host_allocs.push_back(*h);
+  return AZ_OK;
+}
+// `n` host-mapped words the kernels write (or read) and the host polls without a sync, all set to `fill`; *d = their device address
+inline int halloc_mapped(az_engine* e, int** h, int** d, int n, int fill) {
+  AZCHK(halloc_pinned(e, h, (size_t)n, hipHostMallocMapped));
+  std::fill_n(*h, n, fill);
+  HIPCHK(hipHostGetDevicePointer((void**)d, *h, 0));
   return AZ_OK;
 }
 

@@ -146,13 +146,13 @@ template <class Gm, int F> static int pick_tower(const az_engine* e, int n, int 
   // slots in two groups 0.62 vs 0.71 M sims/s); its kernel arguments change per launch (epoch): not under hipGraph replay
   // (r4) the count runs over ALL engines of the process on this device that may launch split towers side by side (an arena has
   // two); an engine whose exchange has given up once (another process, a trainer: work this count cannot see) stays unsplit
-  const bool can_split = F == 128 && !e->cfg.net_bf16 && !e->use_graphs && e->cfg.num_blocks <= 127 && !e->split_off &&
+  const bool can_split = F == 128 && !e->cfg.net_bf16 && !e->env.use_graphs && e->cfg.num_blocks <= 127 && !e->split_off &&
                          2 * std::max(std::max(1, e->ngroups), split_streams_on_device(e->device)) * ((nb + T16<Gm, F, NTS<Gm>>::TB - 1) / T16<Gm, F, NTS<Gm>>::TB) <= (e->num_cu > 0 ? e->num_cu : 256);
-  if (e->tower_pick == TW_SPLIT && can_split) return TW_SPLIT;
-  if (!e->cfg.net_bf16 && (e->tower_pick == TW_11 || e->tower_pick == TW_32 || e->tower_pick == TW_NTS || ((e->tower_pick == TW_P21 || e->tower_pick == TW_P19 || e->tower_pick == TW_P21C) && F == 64) || (e->tower_pick == TW_NTM && NTM<Gm> > 0))) return e->tower_pick;
+  if (e->env.tower_pick == TW_SPLIT && can_split) return TW_SPLIT;
+  if (!e->cfg.net_bf16 && (e->env.tower_pick == TW_11 || e->env.tower_pick == TW_32 || e->env.tower_pick == TW_NTS || ((e->env.tower_pick == TW_P21 || e->env.tower_pick == TW_P19 || e->env.tower_pick == TW_P21C) && F == 64) || (e->env.tower_pick == TW_NTM && NTM<Gm> > 0))) return e->env.tower_pick;
   if (e->cfg.net_bf16) {                                           // k_tower16b: 22 (128 filters), 11 or 3 row tiles
-    if (e->tower_pick == TW_NTS || e->tower_pick == TW_11) return e->tower_pick;
-    if (e->tower_pick == TW_B22 && F == 128) return TW_B22;
+    if (e->env.tower_pick == TW_NTS || e->env.tower_pick == TW_11) return e->env.tower_pick;
+    if (e->env.tower_pick == TW_B22 && F == 128) return TW_B22;
     const long cu2 = e->num_cu > 0 ? e->num_cu : 256;
     const long a16 = (n + T16B<Gm, F>::TB - 1) / T16B<Gm, F>::TB, a3 = (n + T16B<Gm, F, NTS<Gm>>::TB - 1) / T16B<Gm, F, NTS<Gm>>::TB;
     const long per = F == 64 ? 2 : 1;                               // workgroups per CU
@@ -179,7 +179,7 @@ template <class Gm, int F> static int pick_tower(const az_engine* e, int n, int 
   const double c16 = (double)((b16 + cu - 1) / cu) * T16<Gm, F>::RPAD * f16;
   const double c32 = (double)((b32 + cu - 1) / cu) * TOWER_ROWS;     // k_tower (32x32x2) computes every tap
   const double c3 = 1.1 * (double)((b3 + cu - 1) / cu) * T16<Gm, F, NTS<Gm>>::RPAD * f3;
-  if (c3 <= c16 && c3 <= c32) return can_split && e->tower_pick != TW_NTS ? TW_SPLIT : TW_NTS;
+  if (c3 <= c16 && c3 <= c32) return can_split && e->env.tower_pick != TW_NTS ? TW_SPLIT : TW_NTS;
   // (r4) the exact-fit variant (NTM tiles: whole boards, no padding rows): where its workgroups fill the CUs evenly it beats
   // the 11-tile form by the padding rows and by the last, partly filled round of workgroups
   if constexpr (NTM<Gm> > 0) {
@@ -224,7 +224,7 @@ template <class Gm> static int xch_slot(az_engine* e, const float* hfeat, unsign
   }
   *xch = e->xch[slot];
   *epoch = ++e->xch_epoch;
-  if (e->xch_fail_at > 0 && ++e->xch_launches == e->xch_fail_at) *epoch |= 1ull << 63;   // tests: this launch loses a partner (AZHIP_XCH_FAIL_AT)
+  if (e->env.xch_fail_at > 0 && ++e->xch_launches == e->env.xch_fail_at) *epoch |= 1ull << 63;   // tests: this launch loses a partner (AZHIP_XCH_FAIL_AT)
   return AZ_OK;
 }
 // Dense heads of n_max boards: 16-board tiles (k_heads16: a quarter of the chain latency, 23 instead of 43 us per launch
@@ -236,7 +236,7 @@ static constexpr int HEADS16_MAX_BOARDS = 1024;
 template <class Gm, int F>
 static int launch_heads(az_engine* e, hipStream_t st, const float* hfeat, const GEnv* envs, const int* eslots, const int* n_ptr, int n_max,
                         const float* Amask, float* Pout, float* Vout, float* Pinv, int pstride) {
-  const bool small = e->heads_pick == 16 || (e->heads_pick != 32 && (n_max <= HEADS16_MAX_BOARDS || e->ngroups == 1));
+  const bool small = e->env.heads_pick == 16 || (e->env.heads_pick != 32 && (n_max <= HEADS16_MAX_BOARDS || e->ngroups == 1));
   const int tiles = (n_max + 15) / 16;
   if (e->net.hd16_ok && small && 2 * tiles <= (e->num_cu > 0 ? e->num_cu : 256))    // value and policy tiles in two workgroups, features staged in LDS
     LAUNCH_ON(e, st, AZ_K_HEADS, n_max, (k_heads16<Gm, F, true>), 2 * tiles, (H16<Gm, F, true>::THREADS), (H16<Gm, F, true>::BYTES), e->net, envs, eslots, n_ptr, n_max, Amask, hfeat, Pout, Vout, Pinv, pstride);
@@ -317,7 +317,7 @@ template <class Gm, int F> static int wave_net_f(az_engine* e, int g, bool split
   int npick = N;
   if (v.nleaf_host) { const int seen = ((volatile int*)e->h_nleaf)[g]; if (seen >= 0) npick = std::max(1, std::min(N, seen + seen / 8 + 8)); }
   int tw = pick_tower<Gm, F>(e, npick, N);
-  if (tw == TW_P21 && e->fr_on && e->ngroups == 1 && e->tower_pick == 0 && e->fr_kbg > 0 && v.nleaf_host && v.needy_host) {
+  if (tw == TW_P21 && e->fr_on && e->ngroups == 1 && e->env.tower_pick == 0 && e->fr_kbg > 0 && v.nleaf_host && v.needy_host) {
     // The paired tower beside the side streams' kernels (resnet16.h k_tower16x2c): a CU that holds a workgroup of the background search
     // (256 threads = 32 Connect-Four slots of the needy list) takes no workgroup of the 198-register form for as long as that search
     // runs.  Measured: in the steady state (~8 such workgroups on average, more in some waves) the launch gains a round of workgroups
@@ -343,7 +343,7 @@ template <class Gm, int F> static int wave_net_f(az_engine* e, int g, bool split
     using T8 = typename M::T; using T7 = typename M::T7;
     const int cu = e->num_cu > 0 ? e->num_cu : 256, first = cu * T8::TB;
     const int seen = v.nleaf_host ? ((volatile int*)e->h_nleaf)[g] : -1;
-    if (tw == TW_P21 && e->tower_mixed && e->tower_pick == 0 && N > first && seen > first && seen + 16 <= first + cu * T7::TB) {
+    if (tw == TW_P21 && e->env.tower_mixed && e->env.tower_pick == 0 && N > first && seen > first && seen + 16 <= first + cu * T7::TB) {
       mixed = true;
       M::name(e->last_tower, sizeof e->last_tower, game_name(e));
       e->tower_hist[M::HIST]++;

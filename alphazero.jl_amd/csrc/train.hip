@@ -358,7 +358,7 @@ struct az_trainer {
   az_train_cfg cfg;
   int game, device; GameInfo gi;
   hipStream_t stream;
-  bool one_stream, wg_late;
+  EnvTrainer env;                                                            // the AZHIP_TRAIN_* overrides, read when az_trainer_create constructs this record (env.h)
   hipStream_t side;                                                          // the weight gradients of the tower run here, beside the batch-norm backward passes of the next layer
   std::vector<hipEvent_t> ev_dg, ev_wg;                                     // per tower layer: output gradient ready / weight gradient done
   float* gemm_ws; size_t gemm_ws_floats;                                     // split-reduction workspace of gemm_f32
@@ -378,8 +378,6 @@ struct az_trainer {
   float* wg_part; int wg_splits, wg_bpw;                       // k_wgrad16: partial dW per row split, boards per workgroup
   double *part, *sums, *terms, *bsums;
   float* bn_mf;                                                              // [2][C] the batch-norm backward means of the layer in flight
-  bool conv_nt6;                                                             // AZHIP_TRAIN_NT6=0 switches the 6-tile layer kernel off (A/B)
-  bool fin_inside;                                                           // AZHIP_TRAIN_FINISH_INSIDE=1: second stage of the column sums in the producer's last workgroup (measured slower: off)
   int* fin_counter;                                                          // tr_finish: counter of the workgroups that have left their partial sums
   std::vector<void*> allocs;
   std::vector<int> perm; int64_t perm_pos, epoch; int64_t step;
@@ -528,8 +526,6 @@ static int trainer_build(az_trainer* t) {
   const int nchunks = (int)((R + TR_CHUNK - 1) / TR_CHUNK);
   AZCHK(tr_alloc(t, &t->part, (size_t)std::max(nchunks, B + 1) * 2 * std::max(F, 64)));   // chunks of k_tr_colsum or workgroups of k_conv16_layer
   AZCHK(tr_alloc(t, &t->sums, (size_t)2 * std::max(F, 64))); AZCHK(tr_alloc(t, &t->bn_mf, (size_t)2 * std::max(F, 64)));
-  { const char* fi = getenv("AZHIP_TRAIN_FINISH_INSIDE"); t->fin_inside = fi && atoi(fi) != 0; }
-  { const char* n6 = getenv("AZHIP_TRAIN_NT6"); t->conv_nt6 = !(n6 && atoi(n6) == 0); }
   AZCHK(tr_alloc(t, &t->fin_counter, 4, true));                       // tr_finish: workgroups done (every launch leaves it at zero)
   AZCHK(tr_alloc(t, &t->terms, (size_t)4 * B)); AZCHK(tr_alloc(t, &t->bsums, 8 + 1024));
   // k_wgrad16: one round of workgroups over the chip
@@ -562,7 +558,7 @@ static int tr_conv16(az_trainer* t, const float* in, const float* frag, float* o
     using T6 = T16<Gm, 64, 6>;
     // (r4) 64 filters and a batch that gives the 11-tile form at most one workgroup per CU: the 6-tile form (half the boards per
     // workgroup, two workgroups per CU) overlaps one workgroup's fill and epilogue with the other's products
-    const bool small = t->F == 64 && t->conv_nt6 && (t->B + T::TB - 1) / T::TB <= (t->e->num_cu > 0 ? t->e->num_cu : 256);
+    const bool small = t->F == 64 && t->env.conv_nt6 && (t->B + T::TB - 1) / T::TB <= (t->e->num_cu > 0 ? t->e->num_cu : 256);
     if (nparts) *nparts = small ? (t->B + T6::TB - 1) / T6::TB : (t->B + T::TB - 1) / T::TB;
     if (t->F == 128) { if (stats) AZCHK((tr_conv16_f<Gm, 128, true, 11>(t, in, frag, out, addend, bn, fin))); else AZCHK((tr_conv16_f<Gm, 128, false, 11>(t, in, frag, out, addend, bn, fin))); }
     else if (small) { if (stats) AZCHK((tr_conv16_f<Gm, 64, true, 6>(t, in, frag, out, addend, bn, fin))); else AZCHK((tr_conv16_f<Gm, 64, false, 6>(t, in, frag, out, addend, bn, fin))); }
@@ -600,7 +596,7 @@ static int tr_colsum(az_trainer* t, const float* x, const float* out_act, const 
                      TrFinal fin = TrFinal{}) {
   const int nchunks = (int)((R + TR_CHUNK - 1) / TR_CHUNK);
   // (tr_finish -- the second stage in the producer's last workgroup -- is off: measured slower, see k_tr_colsum_final)
-  const bool inside = t->fin_inside && C <= 128;
+  const bool inside = t->env.fin_inside && C <= 128;
   fin.counter = inside ? t->fin_counter : nullptr;
   if (MODE == 1 && C % 4 == 0 && C <= 128 && 256 % (C / 4) == 0)
     hipLaunchKernelGGL(k_tr_colsum1v, dim3(nchunks), dim3(256), 0, t->stream, x, out_act, g, mean, invstd, R, C, t->part, fin);
@@ -641,7 +637,7 @@ static int tr_forward_backward(az_trainer* t, const int* idx_host, double* d_sum
     fin.run_mean = blob + c.off_bn + 2 * c.cout; fin.run_var = blob + c.off_bn + 3 * c.cout;
     if (c.mfma) {
       int nparts = 0;
-      fin.counter = t->fin_inside ? t->fin_counter : nullptr;
+      fin.counter = t->env.fin_inside ? t->fin_counter : nullptr;
       AZCHK(tr_conv16(t, nullptr, t->work + c.wk_ffwd, c.g, true, &nparts, nullptr, bn_of(l - 1), fin));
       if (!fin.counter) hipLaunchKernelGGL(k_tr_colsum_final, dim3(c.cout), dim3(64), 0, st, t->part, nparts, c.cout, t->sums, fin);
     } else {                                                          // the stem: K = 9 C, im2col + GEMM
@@ -727,7 +723,7 @@ static int tr_forward_backward(az_trainer* t, const int* idx_host, double* d_sum
     // dg overwrites da; for conv2 the masked gradient dy also flows to the block input (dact2)
     tr_bn_bwd(t, da, c.a, c.g, c.mean, c.invstd, blob + c.off_bn, R * c.cout, c.cout, da, second ? t->dact2 : nullptr);
     if (!c.mfma) AZCHK(tr_gemm(t, true, false, 9 * c.cin, c.cout, (int)R, 1.f, c.col, 9 * c.cin, da, c.cout, 0.f, gw + c.wk_wm, c.cout));
-    if (c.mfma && !t->wg_late) HIPCHK(hipEventRecord(t->ev_dg[l], st));    // dg(l) is ready: the weight gradient may start beside the data gradient
+    if (c.mfma && !t->env.wg_late) HIPCHK(hipEventRecord(t->ev_dg[l], st));    // dg(l) is ready: the weight gradient may start beside the data gradient
     if (l > 0) {
       // data gradient da_prev = conv(dg, mirrored taps, ci <-> co): the same MFMA layer kernel with the wk_fdg fragments, out of place
       const bool first_of_block = (l % 2) == 1;                    // conv1: its input is the block input, which also gets the skip share
@@ -739,10 +735,10 @@ static int tr_forward_backward(az_trainer* t, const int* idx_host, double* d_sum
     if (c.mfma) {
       // the weight gradient starts when the data gradient of its layer is done: two MFMA kernels side by side only halve each
       // other's share of the chip (measured), while the HBM-bound passes of layer l-1 do fit beside k_wgrad16
-      if (t->wg_late) HIPCHK(hipEventRecord(t->ev_dg[l], st));
-      if (!t->one_stream) HIPCHK(hipStreamWaitEvent(t->side, t->ev_dg[l], 0));
-      AZCHK(tr_wgrad16(t, t->convs[l - 1].a, da, gw + c.wk_wm, t->one_stream ? st : t->side));
-      HIPCHK(hipEventRecord(t->ev_wg[l], t->one_stream ? st : t->side));
+      if (t->env.wg_late) HIPCHK(hipEventRecord(t->ev_dg[l], st));
+      if (!t->env.one_stream) HIPCHK(hipStreamWaitEvent(t->side, t->ev_dg[l], 0));
+      AZCHK(tr_wgrad16(t, t->convs[l - 1].a, da, gw + c.wk_wm, t->env.one_stream ? st : t->side));
+      HIPCHK(hipEventRecord(t->ev_wg[l], t->env.one_stream ? st : t->side));
     }
   }
   for (int l = 1; l < ntower && l <= 2; ++l) if (t->convs[l].mfma) HIPCHK(hipStreamWaitEvent(st, t->ev_wg[l], 0));   // the side stream is in order: its last two launches
@@ -807,8 +803,6 @@ extern "C" int az_trainer_create(az_engine* e, az_dataset* d, const az_train_cfg
     HIPCHK(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
     HIPCHK(hipStreamCreateWithPriority(&t->stream, hipStreamDefault, pr_greatest));
     HIPCHK(hipStreamCreateWithPriority(&t->side, hipStreamNonBlocking, pr_least));
-    { const char* one = getenv("AZHIP_TRAIN_ONE_STREAM"); t->one_stream = one && atoi(one) != 0; }
-    { const char* la = getenv("AZHIP_TRAIN_WG_LATE"); t->wg_late = la && atoi(la) != 0; }   // diagnosis: k_wgrad16(l) only after the data gradient of layer l   // diagnosis: the weight gradients in line with everything else
     t->gemm_ws_floats = (size_t)4 << 20;                            // 16 MB: partial tiles of the split weight-gradient reductions
     AZCHK(tr_alloc(t, &t->gemm_ws, t->gemm_ws_floats));
     AZCHK(trainer_build(t));

@@ -39,12 +39,11 @@
  * az_numerics.h.  The reference (Flux/NNlib/cuDNN) defines no summation order; any order
  * is within the 1e-5 tolerance BASELINE.json states, this one is also reproducible.
  *
- * Environment (diagnostics and tests; the product path sets none of them): AZHIP_TOWER / AZHIP_HEADS force a tower / heads kernel
- * and AZHIP_TOWER_MIXED=1 allows the mixed paired tower launch (all read at az_engine_create), AZHIP_GRAPH=1 replays wave pairs as hipGraphs, AZHIP_VMM=0|1 forces the plain / mapped-on-demand
- * node pool and AZHIP_POOL_GB bounds the physical memory of the latter, AZHIP_RCCL_LIB=<path> substitutes the library az_comm_*
- * loads (tests/rccl_stub: several ranks on one GPU), AZHIP_TRAIN_ONE_STREAM=1 keeps the trainer's weight gradients on the
- * step's own stream and AZHIP_TRAIN_WG_LATE=1 starts them after the data gradient of their layer instead of beside it (same values
- * either way, read at az_trainer_create).
+ * Environment: the product path sets no variable.  The library reads AZHIP_* overrides for diagnostics, A/B runs and tests; the
+ * ones a host may meet are AZHIP_FREE_RUN=0|1 (lock-step / free-running phases whatever az_engine_cfg.lock_step says, read at
+ * az_selfplay_begin), AZHIP_EVAL_CACHE=0 (no evaluation cache), AZHIP_VMM=0|1 and AZHIP_POOL_GB (form and physical bound of the
+ * node pool; all three read at az_engine_create) and AZHIP_RCCL_LIB=<path> (the library az_comm_* loads).  DESIGN.md
+ * "Environment overrides" lists every one with its values, default and the moment it is read; csrc/env.h reads them.
  *
  * RNG contract: include/az_numerics.h (philox4x32-10 keyed by seed, counter = game id,
  * move index, purpose, draw index).

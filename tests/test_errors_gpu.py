@@ -60,3 +60,36 @@ def test_game_too_long_is_reported():
         g, m, ng, nm, st = e.selfplay_run(4)
         # every game and its one replacement (id | bit 30) outgrow the record: all given up, all eight reported, the call returns
         assert ng == 0 and st.aborted_games == 8 and sorted(e.selfplay_aborted()) == [0, 1, 2, 3] + [0x40000000 + i for i in range(4)]
+
+
+_SMALL = dict(game=1, oracle=0, num_workers=8, batch_size=8, num_iters_per_turn=16, reset_every=1, seed=11, lock_step=1)
+
+
+def _phase_records(**kw):
+    """the records of a 4-game phase of a new engine, as bytes (hex)"""
+    import azhip
+    with azhip.Engine(**dict(_SMALL, **kw)) as e:
+        games, moves, ng, nm, _ = e.selfplay_run(4)
+        return "%d %d %s %s" % (ng, nm, b"".join(bytes(games[i]) for i in range(ng)).hex(), b"".join(bytes(moves[i]) for i in range(nm)).hex())
+
+
+def test_failed_create_leaves_the_next_engine_a_clean_start():
+    """az_engine_create refuses max_nodes_per_slot > 2^30 AFTER the engine's stream exists: az_engine_destroy takes a partly built
+    engine apart.  The engine created right after it plays what a fresh process's first engine plays (lock step: the records are
+    a function of the arguments)."""
+    import os
+    import subprocess
+    import sys
+    import azhip
+    from azhip import _lib as L
+    assert _SMALL["oracle"] == azhip.ORACLE_UNIFORM and _SMALL["game"] == azhip.GAME_TICTACTOE
+    with pytest.raises(azhip.AzError) as ei:
+        azhip.Engine(**dict(_SMALL, max_nodes_per_slot=(1 << 30) + 1))
+    assert ei.value.status == L.AZ_ERR_BAD_ARG and "max_nodes_per_slot too large" in str(ei.value)
+    here = _phase_records()
+    code = "import sys; sys.path[:0] = %r; import test_errors_gpu as T; print('RECORDS', T._phase_records())" % (
+        [os.path.dirname(os.path.abspath(__file__))] + [p for p in sys.path if p],)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    fresh = [l for l in r.stdout.splitlines() if l.startswith("RECORDS ")]
+    assert len(fresh) == 1 and fresh[0] == "RECORDS " + here and here.startswith("4 ")

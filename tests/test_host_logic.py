@@ -248,5 +248,10 @@ def test_engine_cache_policy(monkeypatch):
     assert sum(1 for f in Fake.made if not f.closed) == len(E._cache)
     a.close()                                                                              # a closed engine in the cache is rebuilt, not handed out
     assert E.cached_engine("white", num_workers=100) is not a
+    monkeypatch.setenv("AZHIP_EXPLORE_K", "1")                                             # read at az_engine_create like AZHIP_TOWER: its own engine
+    k1 = E.cached_engine("white", num_workers=100)
+    assert E.cached_engine("white", num_workers=100) is k1
+    monkeypatch.delenv("AZHIP_EXPLORE_K")
+    assert E.cached_engine("white", num_workers=100) is not k1 and not k1.closed
     E.clear_engine_cache()
     assert not E._cache and all(f.closed for f in Fake.made)
