@@ -147,8 +147,13 @@ __global__ void k_iota(int* p, int n) {
 // Mancala at BASELINE configs[3] (8192 slots x 800 simulations x 128 plies) that is 107 GB of which a phase touches a
 // fraction.  Pools above VM_THRESHOLD therefore live in a VIRTUAL address range (hipMemAddressReserve) laid out
 // [chunk row][slot][2 MB]: the kernels' address arithmetic is a shift and a mask (node_at, tree.h), and the host backs chunk
-// (row, slot) with physical memory (hipMemCreate + hipMemMap, ~30 us each) at the move step before slot s can reach it --
-// a slot adds at most one node per wave, so one look at the node counts every num_iters_per_turn waves is enough.
+// (row, slot) with physical memory (hipMemCreate + hipMemMap, ~30 us each) before slot s can reach it: at every look the host reads
+// the node counts and maps what a slot can reach before the next look (vm_grow).  Who looks when, and how far ahead:
+//   lock step           a slot adds at most one node per wave; the move step looks every num_iters_per_turn waves: nsims + 2
+//   free-running phase  fr_round looks every fr_round_waves waves, fr_look in between where that is too far apart; a wave's launch adds
+//                       up to run_k + 1 nodes (the pending leaf and run_k answers of the evaluation cache), the background launch
+//                       behind it up to fr_kbg more; without a cache only the pending leaf's node: fr_ahead
+//   hooks, arena        an explore! of nsims simulations adds at most nsims nodes however far it runs ahead: nsims + 2 before its waves
 // tools/probes/vmm_probe.hip: the runtime hands out physical memory in 2 MB units whatever size is asked for; handles above a
 // few MB crashed it, so every mapping is one 2 MB handle.  If the device runs out of memory (or AZHIP_POOL_GB is reached)
 // a slot simply stops growing and is retired when it fills up (DParams::retire).
@@ -185,7 +190,7 @@ static int vm_map(az_engine* e, int row, int slot) {
   return vm_map_at(e, e->vm_base + ((size_t)row * e->v.G + slot) * VM_CHUNK);
 }
 // backs the chunks the slots will need before the host looks again (`ahead` nodes from now); uploads the new capacities
-static int vm_grow(az_engine* e, int ahead) {
+static int vm_grow(az_engine* e, long long ahead) {
   if (!e->vm_rows) return AZ_OK;
   const int G = e->v.G;
   hipLaunchKernelGGL(k_node_counts, dim3((G + 255) / 256), dim3(256), 0, e->stream, e->v, e->d_node_count);
@@ -193,7 +198,7 @@ static int vm_grow(az_engine* e, int ahead) {
   HIPCHK(hipStreamSynchronize(e->stream));
   bool changed = false;
   for (int s = 0; s < G; ++s) {
-    const long long want = std::min<long long>((long long)e->h_node_count[s] + ahead, e->v.cap_nodes);
+    const long long want = std::min<long long>((long long)e->h_node_count[s] + std::min<long long>(ahead, e->v.cap_nodes), e->v.cap_nodes);
     while (e->h_slot_cap[s] < want) {
       const int row = e->h_slot_cap[s] / e->vm_chunk_nodes;
       if (row >= e->vm_rows) break;
@@ -208,6 +213,39 @@ static int vm_grow(az_engine* e, int ahead) {
     HIPCHK(hipMemcpyAsync(e->d_slot_cap, e->h_slot_cap.data(), sizeof(int) * G, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
   }
+  return AZ_OK;
+}
+// the most nodes a slot of a free-running phase can add in one wave: the pending leaf's node and, with an evaluation cache, one per
+// simulation the cache answers -- up to run_k in the wave's launch, up to fr_kbg in the background launch behind it
+static long long fr_per_wave(const az_engine* e) { return e->d_ec ? (long long)e->fr_k + 1 + (long long)e->fr_kbg : 1; }
+// waves between two looks of the host at the node counts: fr_round's, every fr_round_waves waves -- and, where a slot can add so much per
+// wave that a round's worth would map a good part of a chunk ahead of every slot (8192 Mancala slots: 9 GB), looks of their own in
+// between (fr_look), so that a slot is provisioned about an eighth of a chunk ahead
+static int fr_look_interval(const az_engine* e) {
+  if (!e->vm_rows) return e->fr_round_waves;
+  return (int)std::max<long long>(1, std::min<long long>(e->fr_round_waves, (e->vm_chunk_nodes / 8) / fr_per_wave(e)));
+}
+// the most nodes a slot of a free-running phase can add between two looks (64-bit: AZHIP_RUN_K, AZHIP_RUN_KBG, AZHIP_FR_ROUND go up to INT_MAX)
+static long long fr_ahead(const az_engine* e) {
+  const long long cap = e->v.cap_nodes;
+  return std::min<long long>(std::min<long long>(e->fr_look_waves, cap) * std::min(fr_per_wave(e), cap) + 2, cap);
+}
+// a look at the node counts alone, between two rounds
+static int fr_look(az_engine* e) {
+  e->fr_since_look = 0;
+  AZCHK(sync_groups(e));
+  return vm_grow(e, fr_ahead(e));
+}
+// test seam (not in azhip.h, no environment switch): every slot's node count and the nodes of it that are backed by memory
+extern "C" int az_debug_slot_caps(az_engine* e, int* node_count, int* slot_cap) {
+  ENGINE(e);
+  if (!node_count || !slot_cap) return fail(AZ_ERR_BAD_ARG, "NULL buffer");
+  const int G = e->v.G;
+  AZCHK(sync_groups(e));
+  hipLaunchKernelGGL(k_node_counts, dim3((G + 255) / 256), dim3(256), 0, e->stream, e->v, e->d_node_count);
+  HIPCHK(hipMemcpyAsync(node_count, e->d_node_count, sizeof(int) * G, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  for (int s = 0; s < G; ++s) slot_cap[s] = e->vm_rows ? e->h_slot_cap[s] : e->v.cap_nodes;
   return AZ_OK;
 }
 
@@ -1205,8 +1243,13 @@ template <class Gm> static int explore_waves(az_engine* e, int nga, int nsims) {
   }
   return AZ_OK;
 }
+// takes back what explore_begin set on the engine (idempotent): explore_end on every path, and the callers' error paths before it
+struct ExploreGuard {
+  az_engine* e;
+  ~ExploreGuard() { if (!e) return; split_register(e, 0); for (int g = 0; g < e->ngroups; ++g) { e->gv[g].run_k = 0; e->gv[g].busy_host = nullptr; } }
+};
 template <class Gm> static int explore_end(az_engine* e, int nga) {
-  struct Unreg { az_engine* e; ~Unreg() { split_register(e, 0); for (int g = 0; g < e->ngroups; ++g) { e->gv[g].run_k = 0; e->gv[g].busy_host = nullptr; } } } unreg{e};
+  ExploreGuard unreg{e};
   if (!nga) return AZ_OK;
   AZCHK(flush_pending<Gm>(e));                                     // the last simulation's expand + backup
   AZCHK(sync_groups(e));
@@ -1221,8 +1264,9 @@ template <class Gm>
 static int explore_slots(az_engine* e, const std::vector<int>& slots, const std::vector<GEnv>& roots,
                          const std::vector<uint32_t>& gids, const std::vector<uint32_t>& mv, const double* eta, int nsims) {
   int nga = 0;
+  ExploreGuard guard{e};                                           // a failure below leaves no run_k / busy word / registration behind
   AZCHK(explore_begin<Gm>(e, slots, roots, gids, mv, eta, &nga));
-  AZCHK(vm_grow(e, nsims + 2));                                    // mapped-on-demand pool: room for this explore! (a no-op for plain pools)
+  AZCHK(vm_grow(e, (long long)nsims + 2));                         // mapped-on-demand pool: room for this explore! (a no-op for plain pools)
   struct Sims { az_engine* e; int keep; ~Sims() { e->p.nsims = keep; } } sims{e, e->p.nsims};   // the kernel counts a slot's simulations against DParams::nsims
   e->p.nsims = nsims;
   if (nga) AZCHK(explore_waves<Gm>(e, nga, nsims));
@@ -1371,6 +1415,8 @@ extern "C" int az_selfplay_begin(az_engine* e, int32_t num_games, int32_t first_
     // background launch: one slot group -- up to 32 more, or until the tower has run (the stop word); several groups -- a few (it runs on
     // the group's tree stream, ahead of the next wave's launch).  profiles/r6/README.md has the sweeps.
     e->fr_k = ph.run_k; e->fr_kbg = ph.run_kbg >= 0 ? ph.run_kbg : (e->ngroups == 1 ? 32 : 8); e->fr_round_waves = ph.round_waves;
+    e->fr_look_waves = fr_look_interval(e); e->fr_since_look = 0;
+    if (on) AZCHK(vm_grow(e, fr_ahead(e)));                          // mapped-on-demand pool: the host's first look comes fr_look_waves waves from now
     if (on) {
       const int want_cap = num_games > 0 ? num_games : G;
       if (want_cap > e->done_cap) {
@@ -1507,7 +1553,7 @@ template <class Gm> static int move_round(az_engine* e) {
 // deal with retired slots (replacement games), back the node-pool chunks the slots will reach before the next look.
 template <class Gm> static int fr_round(az_engine* e) {
   const int G = e->v.G;
-  e->fr_since_round = 0;
+  e->fr_since_round = 0; e->fr_since_look = 0;
   AZCHK(sync_groups(e));
   if (e->xch_epoch && !e->split_off) {                              // split towers have run: did one give up? (the word is only valid once the device is idle)
     AZCHK(sync_all(e));
@@ -1587,7 +1633,7 @@ template <class Gm> static int fr_round(az_engine* e) {
   e->active_slots = 0;
   for (int g = 0; g < AZ_MAX_GROUPS; ++g) { e->group_active[g] = g < e->ngroups ? std::max(0, fs.active[g]) : 0; e->active_slots += e->group_active[g]; }
   e->h_fr_words[0] = e->fr_prev_done; e->h_fr_words[1] = e->active_slots;
-  return vm_grow(e, e->fr_round_waves * e->fr_k + 2);               // a slot adds at most run_k nodes per wave
+  return vm_grow(e, fr_ahead(e));                                   // what a slot can add before the next look
 }
 template <class Gm> static int fr_step(az_engine* e, int nwaves) {
   for (int w = 0; w < nwaves; ++w) {
@@ -1596,7 +1642,9 @@ template <class Gm> static int fr_step(az_engine* e, int nwaves) {
     const int seen_done = ((volatile int*)e->h_fr_words)[0], seen_active = ((volatile int*)e->h_fr_words)[1];
     if (seen_active == 0 || (e->total_games > 0 && e->d_phase && seen_done + e->fr_given_up >= e->total_games)) break;
     AZCHK(wave<Gm>(e, e->ngroups, 0));
+    ++e->fr_since_look;
     if (++e->fr_since_round >= e->fr_round_waves) AZCHK(fr_round<Gm>(e));
+    else if (e->fr_since_look >= e->fr_look_waves) AZCHK(fr_look(e));
   }
   return fr_round<Gm>(e);                                           // the call returns with the device idle and every finished game collectable
 }
@@ -1816,7 +1864,13 @@ static int arena_run(az_engine* ec, az_engine* eb, int num_games, int first_game
     // think (play.jl:196-206): the two engines' waves are enqueued alternately on their own streams, so the
     // contender's and the baseline's searches overlap on the GPU (each has only part of the workers)
     int nga[2] = {0, 0};
-    for (int k = 0; k < 2; ++k) if (eng[k]->p.nsims > 0) { HIPCHK(hipSetDevice(eng[k]->device)); AZCHK(explore_begin<Gm>(eng[k], slots[k], roots[k], gids[k], mvs[k], nullptr, &nga[k])); }
+    ExploreGuard guard[2] = {{nullptr}, {nullptr}};                // a failure below leaves no run_k / busy word / registration behind
+    for (int k = 0; k < 2; ++k) if (eng[k]->p.nsims > 0) {
+      HIPCHK(hipSetDevice(eng[k]->device));
+      guard[k].e = eng[k];
+      AZCHK(explore_begin<Gm>(eng[k], slots[k], roots[k], gids[k], mvs[k], nullptr, &nga[k]));
+      AZCHK(vm_grow(eng[k], (long long)eng[k]->p.nsims + 2));       // mapped-on-demand pool: room for this ply's explore! (a no-op for plain pools)
+    }
     // (round 6: the explores run ahead -- explore_begin -- and a player is done when its device reports no busy slot: looked at every 16 waves)
     bool done[2] = {nga[0] == 0, nga[1] == 0};
     for (int i = 0; i < std::max(ec->p.nsims, eb->p.nsims) + 1 && !(done[0] && done[1]); ++i) {

@@ -164,6 +164,7 @@ struct az_engine {
   int* d_bg_stop = nullptr; int bg_seq = 0; bool bg_signal = false;   // the background search's stop word: set to bg_seq on the wave's stream once its tower has run (bg_signal: this wave has one)
   int* h_fr_words = nullptr; int* d_fr_words = nullptr;  // host-mapped: finished games / searching slots as of the previous wave (FRArgs::host_words)
   int fr_prev_done = 0, fr_since_round = 0, fr_given_up = 0; long long fr_prev_recs = 0;
+  int fr_look_waves = 0, fr_since_look = 0;      // mapped-on-demand pool: waves between two looks at the node counts (fr_look, azhip.hip; <= fr_round_waves) / since the last one
   std::vector<az_game_rec> h_done; std::vector<long long> h_done_off;
   std::vector<az_game_rec> q_games;
   std::vector<az_move_rec> q_moves;

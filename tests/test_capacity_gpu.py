@@ -68,15 +68,19 @@ def test_mapped_on_demand_pool_gives_the_plain_pool_s_games_and_holds_less_memor
     kw = dict(game=R.MANCALA, oracle=azhip.ORACLE_HASH, num_workers=6, batch_size=3, num_iters_per_turn=600, cpuct=2.0, dirichlet_noise_eps=0.25,
               reset_every=1, seed=5, max_moves_per_game=256, temperature=((0, 10), (1.0, 0.5)))
     out = {}
-    for vmm in ("0", "1", "1 dense side records"):
+    for vmm in ("0", "1", "1 dense side records", "1 cache on"):
         monkeypatch.setenv("AZHIP_VMM", vmm[0])
-        if len(vmm) > 1:
+        monkeypatch.delenv("AZHIP_VMM_KEYS", raising=False)
+        monkeypatch.delenv("AZHIP_EVAL_CACHE", raising=False)
+        if vmm.endswith("dense side records"):
             monkeypatch.setenv("AZHIP_VMM_KEYS", "0")                # round 4's form: nodes mapped on demand, [G][cap] side records beside them
+        if vmm.endswith("cache on"):
+            monkeypatch.setenv("AZHIP_EVAL_CACHE", "1")              # a wave then adds more than one node to a slot (tests/test_mapped_pool_gpu.py)
         with azhip.Engine(**kw) as e:
             g, m, ng, nm, st = e.selfplay_run(8)
             out[vmm] = (_records(g, m, ng), st.aborted_games, e.device_bytes(), max(g[i].nodes for i in range(ng)))
-    monkeypatch.delenv("AZHIP_VMM_KEYS")
-    assert out["0"][0] == out["1"][0] == out["1 dense side records"][0] and out["0"][1] == out["1"][1] == 0
+    assert out["0"][0] == out["1"][0] == out["1 dense side records"][0] == out["1 cache on"][0]
+    assert out["0"][1] == out["1"][1] == out["1 cache on"][1] == 0
     # (r5) the side records follow the node chunks: 32 B per node of the chunks that exist instead of 32 B x the worst case
     # (dense: 6 x 600 x 128 x 32 B = 14.7 MB; mapped: 2 MB granules of four 16 384-record pieces, as far as the six trees grew)
     assert out["1 dense side records"][2] > out["1"][2], (out["1 dense side records"][2], out["1"][2])
@@ -91,11 +95,17 @@ def test_mapped_on_demand_pool_gives_the_plain_pool_s_games_and_holds_less_memor
     assert out["1"][0] == ref
 
 
-def test_explore_on_a_mapped_pool_grows_past_its_first_chunk(monkeypatch):
+@pytest.mark.parametrize("cache", [None, "1"], ids=["cache_default", "cache_on"])
+def test_explore_on_a_mapped_pool_grows_past_its_first_chunk(monkeypatch, cache):
     """MCTS.explore! through the hook (az_mcts_explore) on a mapped-on-demand pool: 30 000 simulations from one root need more
-    nodes than the 16 384 of the first 2 MB chunk -- the chunks are mapped before the waves run, the tree equals the plain pool's"""
+    nodes than the 16 384 of the first 2 MB chunk -- the chunks are mapped before the waves run, the tree equals the plain pool's.
+    cache_on (AZHIP_EVAL_CACHE=1): both slots explore the same root, slot 1 hits what slot 0 filled and runs ahead of the waves."""
     import azhip
     out = {}
+    if cache is None:
+        monkeypatch.delenv("AZHIP_EVAL_CACHE", raising=False)
+    else:
+        monkeypatch.setenv("AZHIP_EVAL_CACHE", cache)
     for vmm in ("0", "1"):
         monkeypatch.setenv("AZHIP_VMM", vmm)
         with azhip.Engine(game=R.C4, oracle=azhip.ORACLE_HASH, num_workers=2, batch_size=2, num_iters_per_turn=8, cpuct=2.0,
