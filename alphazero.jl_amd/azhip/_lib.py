@@ -95,6 +95,15 @@ class TrainCfg(C.Structure):
                 ("l2_regularization", C.c_double), ("nonvalidity_penalty", C.c_double), ("rewards_renormalization", C.c_double),
                 ("batch_size", C.c_int32), ("batch_norm_momentum", C.c_float), ("seed", C.c_uint64)]
 
+MINMAX_MAX_DEPTH = 9
+
+
+class MinMaxCfg(C.Structure):
+    """az_minmax_cfg = MinMax.Player(depth, amplify_rewards, τ, γ), src/minmax.jl:77-85"""
+    _fields_ = [("struct_size", C.c_int32), ("depth", C.c_int32), ("amplify_rewards", C.c_int32), ("reserved", C.c_int32),
+                ("tau", C.c_double), ("gamma", C.c_double)]
+
+
 PROGRESS_CB = C.CFUNCTYPE(None, C.c_void_p)
 
 # every symbol include/azhip.h declares: name -> argtypes (restype is int unless noted)
@@ -171,12 +180,18 @@ SYMBOLS = {
     "az_engine_release_phase": [_VP],
     "az_comm_gather_push": [_VP, _VP, _VP, C.c_double, C.POINTER(GatherStats)],
     "az_comm_broadcast_params": [_VP, _VP, _I32],
+    "az_minmax_cfg_init": [C.POINTER(MinMaxCfg)],
+    "az_game_heuristic": [_VP, _VP, _I32, _VP],
+    "az_minmax_qvalues": [_VP, C.POINTER(MinMaxCfg), _VP, _I32, _VP, _VP],
+    "az_minmax_policy": [_VP, _I32, C.c_double, _VP],
+    "az_engine_set_minmax": [_VP, C.POINTER(MinMaxCfg)],
 }
 
 # az_struct_id order of include/azhip.h
 STRUCTS = [("az_engine_cfg", EngineCfg), ("az_move_rec", MoveRec), ("az_game_rec", GameRec), ("az_trace_buf", TraceBuf),
            ("az_selfplay_stats", SelfplayStats), ("az_sample", Sample), ("az_dataset_info", DatasetInfo),
-           ("az_learning_status_t", LearningStatusRec), ("az_train_cfg", TrainCfg), ("az_gather_stats", GatherStats), ("az_prof", Prof)]
+           ("az_learning_status_t", LearningStatusRec), ("az_train_cfg", TrainCfg), ("az_gather_stats", GatherStats), ("az_prof", Prof),
+           ("az_minmax_cfg", MinMaxCfg)]
 _lib = None
 
 

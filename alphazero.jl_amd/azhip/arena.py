@@ -13,6 +13,7 @@ import numpy as np
 
 from . import _lib as L
 from .engine import cached_engine
+from . import minmax as MinMax
 from .mcts import oracle_kind
 from .network import copy as network_copy
 from .params import ArenaParams, ConstSchedule, MctsParams, engine_options
@@ -34,8 +35,16 @@ class Evaluation:
 
 
 def _engine(gspec, player, sim, device, seed, role):
-    """one engine per player: MctsPlayer (any device oracle) or PlayerWithTemperature(NetworkPlayer(nn), schedule)
-    -- the latter is an engine without search (num_iters_per_turn = 0)."""
+    """one engine per player: MctsPlayer (any device oracle), PlayerWithTemperature(NetworkPlayer(nn), schedule)
+    -- an engine without search (num_iters_per_turn = 0) -- or MinMax.Player: an engine that only carries the workers and
+    the seed (uniform oracle, the smallest valid search) and is told to play MinMax (az_engine_set_minmax).  cached_engine
+    hands engines out again by role and configuration, so EVERY call sets or clears the MinMax state."""
+    if isinstance(player, MinMax.Player):
+        params = MctsParams(num_iters_per_turn=2, dirichlet_noise_ϵ=0.0, dirichlet_noise_α=1.0, temperature=ConstSchedule(1.0))
+        e = cached_engine(role, game=gspec.game_id, oracle=L.ORACLE_UNIFORM, device=device,
+                          **engine_options(params, sim, seed=seed, arena=True))
+        e.set_minmax(player.cfg())
+        return e
     if isinstance(player, MctsPlayer):
         oracle, params = player.oracle, player.params
     elif isinstance(player, PlayerWithTemperature) and isinstance(player.player, NetworkPlayer):
@@ -45,12 +54,13 @@ def _engine(gspec, player, sim, device, seed, role):
         oracle = player.network
         params = MctsParams(num_iters_per_turn=0, dirichlet_noise_ϵ=0.0, dirichlet_noise_α=1.0, temperature=ConstSchedule(1.0))
     else:
-        raise TypeError("the device arena pits MctsPlayers and NetworkPlayers (MinMax / Human players stay on the host)")
+        raise TypeError("the device arena pits MctsPlayers, NetworkPlayers and MinMax players (Human players stay on the host)")
     kind = oracle_kind(oracle)
     kw = engine_options(params, sim, seed=seed, arena=True)
     if kind == L.ORACLE_RESNET:
         kw.update(oracle.engine_options())
     e = cached_engine(role, game=gspec.game_id, oracle=kind, device=device, **kw)   # kept across checkpoints (engine.py)
+    e.set_minmax(None)
     if kind == L.ORACLE_RESNET:
         e.net_set_params(oracle.params())
     return e
@@ -67,7 +77,7 @@ def arena_traces(games, moves, ngames, num_actions):
         for k in range(g.num_moves):
             m = moves[g.first_move + k]
             n = np.array(m.N[:num_actions], dtype=np.int32)
-            n = n.view(np.float32).astype(np.float64) if m.N[L.MAX_ACTIONS] & 0x100 else n.astype(np.float64)   # NetworkPlayer: f32 policy bits
+            n = n.view(np.float32).astype(np.float64) if m.N[L.MAX_ACTIONS] & 0x100 else n.astype(np.float64)   # NetworkPlayer / MinMax: f32 policy bits
             nxt = (int(moves[g.first_move + k + 1].key[0]), int(moves[g.first_move + k + 1].key[1])) \
                 if k + 1 < g.num_moves else (int(g.final_key[0]), int(g.final_key[1]))
             t.push(n / n.sum(), float(m.reward), nxt)

@@ -1,14 +1,15 @@
 """Benchmark mirror (src/benchmark.jl): Duel / Single evaluations between standard players, on the device arena.
 
 Players (benchmark.jl:124-192): Full(params) = MctsPlayer + the network, MctsRollouts(params) = MctsPlayer +
-MCTS.RolloutOracle, NetworkOnly(τ) = PlayerWithTemperature(NetworkPlayer(nn), ConstSchedule(τ)).  MinMaxTS needs
-the host-side minmax player (src/minmax.jl) and is not provided."""
+MCTS.RolloutOracle, NetworkOnly(τ) = PlayerWithTemperature(NetworkPlayer(nn), ConstSchedule(τ)), MinMaxTS(depth, amplify_rewards, τ) =
+MinMax.Player (src/minmax.jl), whose exhaustive walk runs on the device too (azhip/minmax.py, csrc/minmax.hip)."""
 import time
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import mcts as MCTS
+from . import minmax as MinMax
 from .arena import Evaluation, pit_players
 from .network import copy as network_copy
 from .params import ConstSchedule, MctsParams, SimParams
@@ -43,6 +44,21 @@ class NetworkOnly:
 
     def instantiate(self, gspec, nn):
         return PlayerWithTemperature(NetworkPlayer(nn), ConstSchedule(self.τ))
+
+
+@dataclass
+class MinMaxTS:
+    """Benchmark.MinMaxTS(depth, amplify_rewards, τ=0.), benchmark.jl:179-194"""
+    depth: int
+    amplify_rewards: bool
+    τ: float = 0.0
+
+    @property
+    def name(self):
+        return "MinMax (depth %d)" % self.depth
+
+    def instantiate(self, gspec, nn):
+        return MinMax.Player(depth=self.depth, amplify_rewards=self.amplify_rewards, τ=self.τ)
 
 
 @dataclass

@@ -256,6 +256,27 @@ class Engine:
         check(lib().az_selfplay_aborted(self._h, ids, n.value, C.byref(n)))
         return [ids[i] for i in range(n.value)]
 
+    # ---- MinMax player (src/minmax.jl) --------------------------------------------------------------
+    def heuristic(self, keys):
+        """GI.heuristic_value for an (n, 2) uint64 key array -> (n,) float64"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, 2)
+        h = np.zeros(keys.shape[0], dtype=np.float64)
+        check(lib().az_game_heuristic(self._h, _vp(keys), keys.shape[0], _vp(h)))
+        return h
+
+    def minmax_qvalues(self, cfg, keys, policy=True):
+        """qvalue of every action (NaN where unavailable) and think()'s π (0 there) for non-terminal states -> Q, π (n, nA)"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, 2)
+        n = keys.shape[0]
+        Q = np.zeros((n, self.num_actions), dtype=np.float64)
+        pi = np.zeros((n, self.num_actions), dtype=np.float64) if policy else None
+        check(lib().az_minmax_qvalues(self._h, C.byref(cfg), _vp(keys), n, _vp(Q), _vp(pi) if policy else None))
+        return Q, pi
+
+    def set_minmax(self, cfg):
+        """az_arena_run treats this engine as MinMax.Player(cfg) from now on; None = an MCTS / network player again"""
+        check(lib().az_engine_set_minmax(self._h, C.byref(cfg) if cfg is not None else None))
+
     # ---- arena ----------------------------------------------------------------------------------
     def arena_run(self, baseline, num_games, first_game_id=0, alternate_colors=False, progress=None, traces=True):
         """pit_networks: self = contender's engine, baseline = the other player's engine.

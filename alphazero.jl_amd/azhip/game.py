@@ -115,6 +115,10 @@ class GameEnv:
     def white_reward(self):
         return self._reward
 
+    def heuristic_value(self):
+        """GI.heuristic_value (the MinMax baseline's leaf value), on the device like the other rules"""
+        return float(self._spec._eng().heuristic([self._state])[0])
+
     def actions_mask(self):
         _, A = self._spec._eng().encode([self._state])
         return A[0] > 0

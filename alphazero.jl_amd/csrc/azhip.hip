@@ -5,6 +5,7 @@
 // MCTS.explore!/policy/reset! (src/mcts.jl:239-281) -> az_mcts_*; Network.forward_normalized /
 // evaluate_batch (src/networks/network.jl:264-315) -> az_net_*; GameInterface -> az_game_*.
 #include "engine.h"
+#include "minmax.h"
 
 // ------------------------------------------------------------------------------- errors
 static thread_local std::string g_err;
@@ -32,6 +33,7 @@ extern "C" int az_abi_struct_size(int32_t which) {
     case AZ_STRUCT_TRAIN_CFG: return (int)sizeof(az_train_cfg);
     case AZ_STRUCT_GATHER_STATS: return (int)sizeof(az_gather_stats);
     case AZ_STRUCT_PROF: return (int)sizeof(az_prof);
+    case AZ_STRUCT_MINMAX_CFG: return (int)sizeof(az_minmax_cfg);
   }
   return -1;
 }
@@ -1277,6 +1279,7 @@ extern "C" int az_mcts_explore(az_engine* e, const uint64_t* root_keys, int32_t 
                                const double* eta, const uint32_t* game_ids, const uint32_t* moves) {
   ENGINE(e);
   if (e->running) return fail(AZ_ERR_STATE, "self-play in progress");
+  if (e->mm_on) return fail(AZ_ERR_STATE, "the engine is a MinMax player (az_engine_set_minmax): it has no search to explore");
   if (!root_keys || nslots < 1 || nslots > e->v.G) return fail(AZ_ERR_BAD_ARG, "nslots must be in 1..num_workers");
   if (nsims < 1) return fail(AZ_ERR_BAD_ARG, "nsims must be >= 1");
   if (e->cfg.oracle == AZ_ORACLE_RESNET && !e->net_loaded) return fail(AZ_ERR_STATE, "az_net_set_params has not been called");
@@ -1361,6 +1364,7 @@ extern "C" int az_mcts_counters(az_engine* e, int32_t slot, int64_t* ts, int64_t
 extern "C" int az_selfplay_begin(az_engine* e, int32_t num_games, int32_t first_game_id) {
   ENGINE(e);
   if (e->running) return fail(AZ_ERR_STATE, "self-play already in progress");
+  if (e->mm_on) return fail(AZ_ERR_STATE, "the engine is a MinMax player (az_engine_set_minmax): self-play needs an MCTS player");
   if (num_games == 0) return fail(AZ_ERR_BAD_ARG, "num_games must be != 0");
   if (e->p.nsims < 2) return fail(AZ_ERR_BAD_ARG, "num_iters_per_turn = 0 (NetworkPlayer) is for az_arena_run only");
   // ids with bit 30 set are replacement games (an id that already had it would be given up at its first overflow, and its RNG
@@ -1784,9 +1788,13 @@ extern "C" int az_selfplay_run(az_engine* e, int32_t num_games, int32_t first_ga
 // keep separate trees (one engine each); every ply the slots are split by the player to move,
 // each engine explores its share (MCTS.explore! on a slot list), and the host applies
 // play_game's loop body (flip, temperature, sample, play!, play.jl:305-313) with the same
-// select_action / Gm::play code the device self-play uses.
+// select_action / Gm::play code the device self-play uses.  A player is one of three kinds: MctsPlayer (nsims > 0), NetworkPlayer
+// (nsims == 0) or MinMax.Player (az_engine_set_minmax; minmax.hip): no tree, its walk of the ply's roots is enqueued on its engine's
+// stream before the other player's waves and fetched after them.
 // =========================================================================================
 namespace {
+enum ArenaKind { PL_MCTS = 0, PL_NET = 1, PL_MINMAX = 2 };
+inline ArenaKind arena_kind(const az_engine* e) { return e->mm_on ? PL_MINMAX : e->p.nsims > 0 ? PL_MCTS : PL_NET; }
 struct ArenaSlot {
   GEnv env;
   uint32_t gid = 0;
@@ -1837,6 +1845,8 @@ static int arena_run(az_engine* ec, az_engine* eb, int num_games, int first_game
   std::vector<GEnv> roots[2];
   std::vector<uint32_t> gids[2], mvs[2];
   az_engine* eng[2] = {ec, eb};
+  const ArenaKind kind[2] = {arena_kind(ec), arena_kind(eb)};
+  std::vector<double> mmQ[2];
   while (finished < num_games) {
     for (int k = 0; k < 2; ++k) { slots[k].clear(); roots[k].clear(); gids[k].clear(); mvs[k].clear(); }
     for (int s = 0; s < G; ++s) {
@@ -1865,7 +1875,8 @@ static int arena_run(az_engine* ec, az_engine* eb, int num_games, int first_game
     // contender's and the baseline's searches overlap on the GPU (each has only part of the workers)
     int nga[2] = {0, 0};
     ExploreGuard guard[2] = {{nullptr}, {nullptr}};                // a failure below leaves no run_k / busy word / registration behind
-    for (int k = 0; k < 2; ++k) if (eng[k]->p.nsims > 0) {
+    for (int k = 0; k < 2; ++k) if (kind[k] == PL_MINMAX) { HIPCHK(hipSetDevice(eng[k]->device)); AZCHK(minmax_launch(eng[k], roots[k])); }
+    for (int k = 0; k < 2; ++k) if (kind[k] == PL_MCTS) {
       HIPCHK(hipSetDevice(eng[k]->device));
       guard[k].e = eng[k];
       AZCHK(explore_begin<Gm>(eng[k], slots[k], roots[k], gids[k], mvs[k], nullptr, &nga[k]));
@@ -1873,7 +1884,8 @@ static int arena_run(az_engine* ec, az_engine* eb, int num_games, int first_game
     }
     // (round 6: the explores run ahead -- explore_begin -- and a player is done when its device reports no busy slot: looked at every 16 waves)
     bool done[2] = {nga[0] == 0, nga[1] == 0};
-    for (int i = 0; i < std::max(ec->p.nsims, eb->p.nsims) + 1 && !(done[0] && done[1]); ++i) {
+    const int nsims_k[2] = {kind[0] == PL_MCTS ? ec->p.nsims : 0, kind[1] == PL_MCTS ? eb->p.nsims : 0};
+    for (int i = 0; i < std::max(nsims_k[0], nsims_k[1]) + 1 && !(done[0] && done[1]); ++i) {
       for (int k = 0; k < 2; ++k) if (!done[k]) {
         const bool ahead = eng[k]->gv[0].run_k > 0;
         if (i >= eng[k]->p.nsims + (ahead ? 1 : 0)) { done[k] = true; continue; }
@@ -1889,7 +1901,9 @@ static int arena_run(az_engine* ec, az_engine* eb, int num_games, int first_game
     }
     for (int k = 0; k < 2; ++k) {
       HIPCHK(hipSetDevice(eng[k]->device));
-      if (eng[k]->p.nsims > 0) {
+      if (kind[k] == PL_MINMAX) {
+        AZCHK(minmax_fetch(eng[k], (int)roots[k].size(), mmQ[k]));  // MinMax.Player's qvalues (minmax.jl:90)
+      } else if (kind[k] == PL_MCTS) {
         AZCHK(explore_end<Gm>(eng[k], nga[k]));
         AZCHK(root_visits<Gm>(eng[k], slots[k], roots[k], visits[k]));
       } else {
@@ -1901,7 +1915,15 @@ static int arena_run(az_engine* ec, az_engine* eb, int num_games, int first_game
       az_move_rec& rec = a.moves.back();
       const uint32_t m = Gm::mask(a.env);
       int act;
-      if (eng[k]->p.nsims > 0) {
+      if (kind[k] == PL_MINMAX) {                                   // think (minmax.jl:87-114) + the default select_move (play.jl:48-53)
+        int acts[AZ_MAX_ACTIONS], n = 0;
+        double q[AZ_MAX_ACTIONS], pi[AZ_MAX_ACTIONS];
+        for (int x = 0; x < Gm::A; ++x) if ((m >> x) & 1) { q[n] = mmQ[k][i * AZ_MAX_ACTIONS + x]; acts[n++] = x; }
+        minmax_policy(q, n, eng[k]->mm.tau, pi);
+        for (int j = 0; j < n; ++j) { const float pf = (float)pi[j]; memcpy(&rec.N[acts[j]], &pf, 4); }   // pi's Float32 bits
+        rec.N[AZ_MAX_ACTIONS] |= 0x300;
+        act = sample_policy_tau(eng[k]->p.seed, acts, pi, n, 1.0, (uint32_t)a.nmoves, a.gid);
+      } else if (kind[k] == PL_MCTS) {
         const int* vis = &visits[k][i * (AZ_MAX_ACTIONS + 1)];
         if (!vis[0]) return fail(AZ_ERR_STATE, "root of slot %d missing after explore", slots[k][i]);
         for (int x = 0; x < AZ_MAX_ACTIONS; ++x) rec.N[x] = vis[1 + x];

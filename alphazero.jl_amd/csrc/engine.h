@@ -184,6 +184,10 @@ struct az_engine {
   double next_exec = 1.0;        // executed-product fraction of the NEXT profiled launch (set by the tower launches, consumed by prof_begin)
   std::vector<int> h_finished;
   std::vector<az_game_rec> h_grec;
+  // MinMax player (minmax.hip): mm_on = az_arena_run treats this engine as MinMax.Player(mm); staging for mm_cap roots
+  bool mm_on = false;
+  az_minmax_cfg mm = {};
+  GEnv* d_mm_roots = nullptr; double* d_mm_q = nullptr; int mm_cap = 0;
 };
 
 template <class T> inline int dalloc(az_engine* e, T** p, size_t n, bool zero = true) {
@@ -271,6 +275,11 @@ int check_device_error(az_engine* e);
 
 // azhip.hip: how many streams of this process may launch split towers on `device` at the same time (all engines with 128 filters)
 int split_streams_on_device(int device);
+
+// ---- minmax.hip: the MinMax player's think for the arena.  minmax_launch enqueues the walk of `roots` on the engine's stream (so it
+// runs beside the other player's search), minmax_fetch waits for it: Q [n][AZ_MAX_ACTIONS] by full action index (NaN: unavailable)
+int minmax_launch(az_engine* e, const std::vector<GEnv>& roots);
+int minmax_fetch(az_engine* e, int n, std::vector<double>& Q);
 
 // ---- net.hip: every instantiation of the tower / heads kernels lives there ----------------------------------
 int net_set_kernel_attrs(az_engine* e);   // + uploads the row permutation tables of the tower kernels (e->d_geo)

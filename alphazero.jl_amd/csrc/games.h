@@ -79,6 +79,38 @@ struct ConnectFour {
     uint32_t wn = g.fin >> 1;
     return (g.fin & 1) ? (wn == 1 ? 1.f : wn == 2 ? -1.f : 0.f) : 0.f;
   }
+  // GI.heuristic_value, game.jl:174-220 (MinMax baseline; the contract is in include/azhip.h "MinMax player"): mine - yours, each
+  // side the left-to-right Float64 sum over the 69 alignments in the reference's order -- axes (1,1), (1,-1), (0,1), (1,0), per axis
+  // x outer, y inner -- of 0.1^(3 - N), or 0. where the other side has a stone in the alignment.
+  AZ_GHD static double align_value(uint64_t me, uint64_t op, uint64_t m) {
+    const int n = az_popc64(me & m);
+    const double v = n == 0 ? (0.1 * 0.1) * 0.1 : n == 1 ? 0.1 * 0.1 : n == 2 ? 0.1 : n == 3 ? 1.0 : 10.0;
+    return (op & m) ? 0.0 : v;
+  }
+  // the loops stay rolled (one alignment in flight: unrolled, the 138 independent terms of a leaf cost 500 registers); the mask of
+  // an alignment is the axis' four-cell pattern shifted to its first cell
+  AZ_GHD static double axis_value(double s, uint64_t me, uint64_t op, uint64_t pattern, int xmax, int ymin, int ymax) {
+#pragma unroll 1
+    for (int x = 0; x <= xmax; ++x)
+#pragma unroll 1
+      for (int y = ymin; y <= ymax; ++y) s = s + align_value(me, op, pattern << (x * 7 + y - ymin));
+    return s;
+  }
+  AZ_GHD static double side_value(uint64_t me, uint64_t op) {
+    double s = 0.0;
+    s = axis_value(s, me, op, (1ULL << 0) | (1ULL << 8) | (1ULL << 16) | (1ULL << 24), 3, 0, 2);          // (1,1)
+    s = axis_value(s, me, op, (1ULL << 3) | (1ULL << 9) | (1ULL << 15) | (1ULL << 21), 3, 3, 5);          // (1,-1): from (x, y >= 3) down
+    s = axis_value(s, me, op, 0xfULL, 6, 0, 2);                                                           // (0,1)
+    s = axis_value(s, me, op, (1ULL << 0) | (1ULL << 7) | (1ULL << 14) | (1ULL << 21), 3, 0, 5);          // (1,0)
+    return s;
+  }
+  AZ_GHD static double heuristic(const GEnv& g) {
+    const uint64_t w = g.a & ~AZ_BLACK_BIT;
+    const bool wp = white_playing(g);
+    const uint64_t me = wp ? w : g.b, op = wp ? g.b : w;
+    const double mine = side_value(me, op), yours = side_value(op, me);
+    return mine - yours;
+  }
   // GI.symmetries, game.jl:243-257: ONE symmetry, the column mirror (sigma = 7..1)
   static constexpr int NSYM = 1;
   AZ_GHD static uint64_t mirror(uint64_t x) {
@@ -133,6 +165,26 @@ struct TicTacToe {
   AZ_GHD static float white_reward(const GEnv& g) {
     uint32_t wn = g.fin >> 1;
     return (g.fin & 1) ? (wn == 1 ? 1.f : wn == 2 ? -1.f : 0.f) : 0.f;
+  }
+  // GI.heuristic_value, game.jl:43-51,98-120: as Connect Four's with 0.3^(2 - N) over the 8 alignments in the order of ALIGNMENTS
+  // (the columns (0,3,6) (1,4,7) (2,5,8), the rows, the two diagonals)
+  AZ_GHD static double align_value(uint32_t me, uint32_t op, uint32_t m) {
+    const int n = __builtin_popcount(me & m);
+    const double v = n == 0 ? 0.3 * 0.3 : n == 1 ? 0.3 : n == 2 ? 1.0 : 1.0 / 0.3;
+    return (op & m) ? 0.0 : v;
+  }
+  AZ_GHD static double side_value(uint32_t me, uint32_t op) {
+    double s = 0.0;
+    s = s + align_value(me, op, 0x049); s = s + align_value(me, op, 0x092); s = s + align_value(me, op, 0x124);
+    s = s + align_value(me, op, 0x007); s = s + align_value(me, op, 0x038); s = s + align_value(me, op, 0x1C0);
+    s = s + align_value(me, op, 0x111); s = s + align_value(me, op, 0x054);
+    return s;
+  }
+  AZ_GHD static double heuristic(const GEnv& g) {
+    const uint32_t w = (uint32_t)g.a & 0x1ff, k = (uint32_t)g.b & 0x1ff;
+    const bool wp = white_playing(g);
+    const double mine = side_value(wp ? w : k, wp ? k : w), yours = side_value(wp ? k : w, wp ? w : k);
+    return mine - yours;
   }
   // GI.symmetries, game.jl:149-168: the 7 non-trivial dihedral maps in the reference's order
   // (rot, rot2, rot3, flip, flip.rot, flip.rot2, flip.rot3); new board[p] = board[src(k, p)], where
@@ -236,6 +288,10 @@ struct Mancala {
     if (!(g.fin & 1)) return 0.f;
     uint32_t nw = byte_at(g.a, 6), nb = byte_at(g.b, 6);
     return nw > nb ? 1.f : nw < nb ? -1.f : 0.f;
+  }
+  AZ_GHD static double heuristic(const GEnv& g) {       // GI.heuristic_value, game.jl:213-218: store difference from the mover's side
+    const int v = (int)byte_at(g.a, 6) - (int)byte_at(g.b, 6);
+    return (double)(white_playing(g) ? v : -v);
   }
   static constexpr int NSYM = 0;                        // no GI.symmetries method: apply_random_symmetry! asserts
   AZ_GHD static GEnv sym(const GEnv& g, int) { return g; }

@@ -856,10 +856,9 @@ __device__ inline const char* find_node(const DView& v, int slot, unsigned long 
 // (util.jl:68-90) for one root: Nn = visit counts by full action index, m = availability mask, mv = number of
 // moves already played (temperature index, play.jl:309).  Shared by k_move and the arena's host loop, so the
 // device and the host draw the same action from the same counts.
-// apply_temperature + sampling of a policy pi over the n available actions acts[]
-__host__ __device__ inline int sample_policy(const DParams& p, const int* acts, const double* pi, int n, uint32_t mv, uint32_t game_id) {
+// apply_temperature(pi, tau) + sampling of a policy pi over the n available actions acts[] with the (seed, game id, move) stream
+__host__ __device__ inline int sample_policy_tau(uint64_t seed, const int* acts, const double* pi, int n, double tau, uint32_t mv, uint32_t game_id) {
   double pis[AZ_MAX_ACTIONS];
-  const double tau = pl_schedule(p, (int)mv);
   if (tau == 1.0) for (int i = 0; i < n; ++i) pis[i] = pi[i];
   else if (tau == 0.0) {
     int am = 0;
@@ -880,8 +879,12 @@ __host__ __device__ inline int sample_policy(const DParams& p, const int* acts, 
     if (fs == 0.0f) for (int i = 0; i < n; ++i) pf[i] = 1.0f / (float)n;
     else for (int i = 0; i < n; ++i) pf[i] = pf[i] / fs;
   }
-  az_rng r = az_rng_make(p.seed, game_id, mv, AZ_RNG_MOVE);
+  az_rng r = az_rng_make(seed, game_id, mv, AZ_RNG_MOVE);
   return acts[az_categorical_f32(pf, n, az_rng_f32(&r))];
+}
+// the same under the engine's temperature schedule (player_temperature of MctsPlayer / PlayerWithTemperature, play.jl:136-150,208-210)
+__host__ __device__ inline int sample_policy(const DParams& p, const int* acts, const double* pi, int n, uint32_t mv, uint32_t game_id) {
+  return sample_policy_tau(p.seed, acts, pi, n, pl_schedule(p, (int)mv), mv, game_id);
 }
 template <class Gm>
 __host__ __device__ inline int select_action(const DParams& p, const int* Nn, uint32_t m, uint32_t mv, uint32_t game_id) {

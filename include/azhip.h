@@ -151,7 +151,7 @@ int az_abi_version(void);
 typedef enum {
   AZ_STRUCT_ENGINE_CFG = 0, AZ_STRUCT_MOVE_REC = 1, AZ_STRUCT_GAME_REC = 2, AZ_STRUCT_TRACE_BUF = 3, AZ_STRUCT_SELFPLAY_STATS = 4,
   AZ_STRUCT_SAMPLE = 5, AZ_STRUCT_DATASET_INFO = 6, AZ_STRUCT_LEARNING_STATUS = 7, AZ_STRUCT_TRAIN_CFG = 8, AZ_STRUCT_GATHER_STATS = 9,
-  AZ_STRUCT_PROF = 10
+  AZ_STRUCT_PROF = 10, AZ_STRUCT_MINMAX_CFG = 11
 } az_struct_id;
 int az_abi_struct_size(int32_t which);
 
@@ -303,10 +303,66 @@ int az_selfplay_end(az_engine* e);
  * Benchmark.Duel players (src/benchmark.jl:124-192): Full = ResNet oracle, MctsRollouts = AZ_ORACLE_ROLLOUT,
  * NetworkOnly(tau) = an engine with num_iters_per_turn = 0 (NetworkPlayer, src/play.jl:226-235, under
  * PlayerWithTemperature(ConstSchedule(tau))): its moves carry the policy's Float32 bits in N[0..A) and
- * bit 8 of N[AZ_MAX_ACTIONS]. */
+ * bit 8 of N[AZ_MAX_ACTIONS].  MinMaxTS = an engine after az_engine_set_minmax (below): no search, think()'s pi as Float32
+ * bits in N[0..A), bits 8 and 9 (0x300) of N[AZ_MAX_ACTIONS] beside the symmetry index; either side may be one. */
 int az_arena_run(az_engine* contender, az_engine* baseline, int32_t num_games, int32_t first_game_id,
                  int32_t alternate_colors, az_trace_buf* out, double* rewards, double* redundancy,
                  az_progress_cb cb, void* user);
+
+/* ---- MinMax player (Benchmark.MinMaxTS, src/benchmark.jl:179-194 -> MinMax.Player, src/minmax.jl:14-114) ------------------
+ * The baseline that needs neither a network nor MCTS: an exhaustive depth-limited tree walk on the device (csrc/minmax.hip).
+ * Contract, operation by operation; every Float64 step is ONE IEEE operation (no contraction), so results are defined bit
+ * for bit.  As with every other "bit-exact" of this project this is parity with THIS restatement and its CPU twin
+ * (tests/minmax_ref.py): the reference itself has never been run against it (no Julia where this was written) -- unpinned.
+ *   value(game, d)       (minmax.jl:17-26)  0. if game_terminated; heuristic_value(game) if d == 0; else maximum of
+ *                        qvalue(game, a, d) over the available actions (Julia's max: -0.0 < 0.0).
+ *   qvalue(game, a, d)   (minmax.jl:28-42)  next = play!(clone(game), a); wr = white_reward(next); r = white_playing(game) ? wr :
+ *                        -wr (so a BLACK mover's zero reward is -0.0); with amplify_rewards a non-zero r becomes Inf * sign(r)
+ *                        (minmax.jl:14); nextv = value(next, d - 1), negated ONLY IF the player to move changed (Mancala's
+ *                        extra turns do not negate; negating a terminal child's 0. gives -0.0 and that is what is added);
+ *                        q = r + gamma * nextv: one multiplication, one addition.
+ *   heuristic_value      Connect Four (games/connect-four/game.jl:174-220): mine - yours; each side the sequential
+ *                        left-to-right sum, from the first term, over the 69 alignments in the order axes (1,1), (1,-1), (0,1),
+ *                        (1,0), within an axis x outer 1..7, y inner 1..6 (alignments that leave the board dropped); an alignment
+ *                        holding a stone of the other side gives 0., else 0.1^(3 - N) for N own stones, from the table {1.0, 0.1,
+ *                        0.1*0.1, (0.1*0.1)*0.1} (= the correctly rounded powers 0.010000000000000002, 0.0010000000000000002).
+ *                        Tic-tac-toe (games/tictactoe/game.jl:43-51,98-120): the same with 0.3^(2 - N), table {1.0, 0.3,
+ *                        0.3*0.3}, alignments (0,3,6) (1,4,7) (2,5,8), (0,1,2) (3,4,5) (6,7,8), (0,4,8), (2,4,6).
+ *                        Mancala (games/mancala/game.jl:213-218): Float64(store of the mover - store of the other side).
+ *                        The order shows in the last bits (Connect-Four opening, depth 5: 0.27000000000000013 for columns 3 and
+ *                        4 counted from 1, 0.27 for column 5) and those bits decide ties at tau = 0.
+ *   think                (minmax.jl:87-114) pi over the available actions: some q == +Inf -> 1 on those, 0 elsewhere; else every
+ *                        q == -Inf -> all 1; else tau == 0 -> 1 on every q == the maximum; else C = max |q| over the q > -Inf +
+ *                        eps(Float64), pi = az_exp((q - qmax) / C) with an explicit 0 for q == -Inf, then az_pow(pi, 1 / tau);
+ *                        finally every entry divided by the sequential sum.
+ *   move                 the default select_move (src/play.jl:48-53): player_temperature is 1.0 whatever the engine's temperature
+ *                        schedule says, then fix_probvec + rand_categorical with the AZ_RNG_MOVE stream of (seed, game id, move).
+ * The walk is exhaustive like the reference's (no pruning): max and negation are exact, so only the leaf heuristic and
+ * r + gamma * v round and the result does not depend on how the tree is split over the device. */
+#define AZ_MINMAX_MAX_DEPTH 9          /* 9 solves Tic-tac-toe */
+typedef struct {
+  int32_t struct_size;        /* sizeof(az_minmax_cfg), set by az_minmax_cfg_init */
+  int32_t depth;              /* 1..AZ_MINMAX_MAX_DEPTH */
+  int32_t amplify_rewards;
+  int32_t reserved;           /* 0 */
+  double tau;                 /* >= 0, finite */
+  double gamma;               /* > 0, finite */
+} az_minmax_cfg;
+int az_minmax_cfg_init(az_minmax_cfg* cfg);                 /* depth 5, amplify 0, tau 0, gamma 1 */
+/* GI.heuristic_value(GI.init(gspec, s)) for n states, on the device */
+int az_game_heuristic(az_engine* e, const uint64_t* keys, int32_t n, double* h);
+/* [qvalue(p, game, a, p.depth) for a] by FULL action index (Q: n*num_actions, unavailable: NaN) and, if pi != NULL, think()'s pi
+ * (n*num_actions, unavailable: 0) for n non-terminal states, on the device; a terminated state is AZ_ERR_BAD_ARG naming its
+ * index and nothing is launched.  The configuration is checked before the engine; n = 0 is AZ_OK. */
+int az_minmax_qvalues(az_engine* e, const az_minmax_cfg* cfg, const uint64_t* keys, int32_t n, double* Q, double* pi);
+/* think()'s pi from the n q-values of the available actions: pure host, no engine (the function az_arena_run and
+ * az_minmax_qvalues use); 1 <= n <= AZ_MAX_ACTIONS, no NaN */
+int az_minmax_policy(const double* q, int32_t n, double tau, double* pi);
+/* From now on az_arena_run treats this engine as MinMax.Player(cfg) (its oracle, search parameters and temperature schedule are
+ * not consulted); NULL = an MCTS / network player again.  While it is one, az_selfplay_begin / az_selfplay_run and
+ * az_mcts_explore return AZ_ERR_STATE.  AZ_ERR_BAD_ARG for a depth outside 1..AZ_MINMAX_MAX_DEPTH, tau < 0 or not finite,
+ * gamma <= 0 or not finite, a wrong struct_size, and AZ_GAME_GO9_PLANES (no device twin). */
+int az_engine_set_minmax(az_engine* e, const az_minmax_cfg* cfg);
 
 /* push_trace! (src/memory.jl:74-87): z (discounted, side relative) and t per move record. */
 int az_push_trace(const az_move_rec* moves, int32_t n, double gamma, double* z, double* t);

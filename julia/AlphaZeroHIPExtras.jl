@@ -225,5 +225,13 @@ const UNBOUND = Dict(
   :az_trainer_gradients => "test hook (gradients of one batch against autograd)",
   :az_prof_enable => "bench.py's HIP-event profiling", :az_prof_get => "bench.py's HIP-event profiling",
   :az_prof_reset => "bench.py's HIP-event profiling", :az_device_info => "bench.py's report", :az_net_last_kernel => "bench.py's report",
+  # the MinMax baseline (Benchmark.MinMaxTS): Julia keeps the reference's own MinMax.Player for host-stepped games; the device player is
+  # reached through the Python host's benchmark.run.  A MinMaxDevicePlayer <: AbstractPlayer would pass az_minmax_cfg by reference, a
+  # record tests/test_julia_glue_static.py has no ccall rule for, so the three calls that take it stay unbound, and the other two with them
+  :az_minmax_cfg_init => "az_minmax_cfg is four Int32 and two Float64 a host fills itself; no Julia caller yet (see the note above)",
+  :az_minmax_qvalues => "takes az_minmax_cfg by reference: no static ccall rule for that record yet; MinMax.Player of the reference serves Julia hosts",
+  :az_engine_set_minmax => "takes az_minmax_cfg by reference, see az_minmax_qvalues; MinMax duels run through the Python host's benchmark.run",
+  :az_minmax_policy => "think()'s policy from q-values: only useful together with az_minmax_qvalues",
+  :az_game_heuristic => "GI.heuristic_value is the reference's own on the Julia side; the device twin is checked against tests/minmax_ref.py",
 )
 
