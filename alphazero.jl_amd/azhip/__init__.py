@@ -14,6 +14,8 @@ from .game import ConnectFourSpec, GameEnv, GameSpec, MancalaSpec, TicTacToeSpec
 from .network import ResNet, ResNetHP
 from . import mcts as MCTS
 from . import minmax as MinMax
+from . import solver as Solver
+from . import pons as Pons
 from .play import MctsPlayer, NetworkPlayer, PlayerWithTemperature, TwoPlayers, flipped_colors, play_game
 from .trace import Trace
 from .memory import Dataset, MemoryBuffer, TrainingSample, push_trace

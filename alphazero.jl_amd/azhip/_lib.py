@@ -104,6 +104,15 @@ class MinMaxCfg(C.Structure):
                 ("tau", C.c_double), ("gamma", C.c_double)]
 
 
+SOLVER_NA, SOLVER_UNSOLVED = -128, 127      # include/azhip.h AZ_SOLVER_NA / AZ_SOLVER_UNSOLVED
+SOLVER_DEFAULT_BUDGET = 1 << 20             # AZ_SOLVER_DEFAULT_BUDGET (what az_solver_cfg_init sets)
+
+
+class SolverCfg(C.Structure):
+    """az_solver_cfg: weak (sign only) or strong (exact score), nodes per (state, action) query"""
+    _fields_ = [("struct_size", C.c_int32), ("weak", C.c_int32), ("node_budget", C.c_int64)]
+
+
 PROGRESS_CB = C.CFUNCTYPE(None, C.c_void_p)
 
 # every symbol include/azhip.h declares: name -> argtypes (restype is int unless noted)
@@ -185,13 +194,16 @@ SYMBOLS = {
     "az_minmax_qvalues": [_VP, C.POINTER(MinMaxCfg), _VP, _I32, _VP, _VP],
     "az_minmax_policy": [_VP, _I32, C.c_double, _VP],
     "az_engine_set_minmax": [_VP, C.POINTER(MinMaxCfg)],
+    "az_solver_cfg_init": [C.POINTER(SolverCfg)],
+    "az_c4_solve": [_VP, C.POINTER(SolverCfg), _VP, _I32, _VP, _VP, _VP],
+    "az_solver_policy": [_VP, _I32, _VP],
 }
 
 # az_struct_id order of include/azhip.h
 STRUCTS = [("az_engine_cfg", EngineCfg), ("az_move_rec", MoveRec), ("az_game_rec", GameRec), ("az_trace_buf", TraceBuf),
            ("az_selfplay_stats", SelfplayStats), ("az_sample", Sample), ("az_dataset_info", DatasetInfo),
            ("az_learning_status_t", LearningStatusRec), ("az_train_cfg", TrainCfg), ("az_gather_stats", GatherStats), ("az_prof", Prof),
-           ("az_minmax_cfg", MinMaxCfg)]
+           ("az_minmax_cfg", MinMaxCfg), ("az_solver_cfg", SolverCfg)]
 _lib = None
 
 

@@ -2,7 +2,8 @@
 
 Players (benchmark.jl:124-192): Full(params) = MctsPlayer + the network, MctsRollouts(params) = MctsPlayer +
 MCTS.RolloutOracle, NetworkOnly(τ) = PlayerWithTemperature(NetworkPlayer(nn), ConstSchedule(τ)), MinMaxTS(depth, amplify_rewards, τ) =
-MinMax.Player (src/minmax.jl), whose exhaustive walk runs on the device too (azhip/minmax.py, csrc/minmax.hip)."""
+MinMax.Player (src/minmax.jl), whose exhaustive walk runs on the device too (azhip/minmax.py, csrc/minmax.hip).  Solver = the exact
+Connect-Four player of games/connect-four/solver.jl (azhip/solver.py, csrc/solver.hip), for host-stepped games."""
 import time
 from dataclasses import dataclass
 
@@ -10,6 +11,7 @@ import numpy as np
 
 from . import mcts as MCTS
 from . import minmax as MinMax
+from . import solver as SolverMod
 from .arena import Evaluation, pit_players
 from .network import copy as network_copy
 from .params import ConstSchedule, MctsParams, SimParams
@@ -59,6 +61,17 @@ class MinMaxTS:
 
     def instantiate(self, gspec, nn):
         return MinMax.Player(depth=self.depth, amplify_rewards=self.amplify_rewards, τ=self.τ)
+
+
+@dataclass
+class Solver:
+    """The perfect Connect-Four player (Solver.Player, games/connect-four/solver.jl) as a player description: host-stepped play only
+    (play.play_game, scripts of the Pons benchmark); the device arena does not seat it (include/azhip.h "Connect Four solver")."""
+    node_budget: object = None
+    name = "Solver"
+
+    def instantiate(self, gspec, nn):
+        return SolverMod.Player(node_budget=self.node_budget)
 
 
 @dataclass

@@ -277,6 +277,23 @@ class Engine:
         """az_arena_run treats this engine as MinMax.Player(cfg) from now on; None = an MCTS / network player again"""
         check(lib().az_engine_set_minmax(self._h, C.byref(cfg) if cfg is not None else None))
 
+    # ---- Connect Four solver (games/connect-four/solver.jl) ------------------------------------------
+    def c4_solve(self, keys, weak=False, node_budget=None):
+        """Solver.value / Solver.qvalue for an (n, 2) uint64 key array -> value (n,) int8, q (n, 7) int8 by full action index
+        (SOLVER_NA: full column, SOLVER_UNSOLVED: the query needs more than node_budget nodes), nodes (n,) int64"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, 2)
+        n = keys.shape[0]
+        cfg = L.SolverCfg()
+        check(lib().az_solver_cfg_init(C.byref(cfg)))
+        cfg.weak = 1 if weak else 0
+        if node_budget is not None:
+            cfg.node_budget = int(node_budget)
+        value = np.zeros(n, dtype=np.int8)
+        q = np.zeros((n, 7), dtype=np.int8)
+        nodes = np.zeros(n, dtype=np.int64)
+        check(lib().az_c4_solve(self._h, C.byref(cfg), _vp(keys), n, _vp(value), _vp(q), _vp(nodes)))
+        return value, q, nodes
+
     # ---- arena ----------------------------------------------------------------------------------
     def arena_run(self, baseline, num_games, first_game_id=0, alternate_colors=False, progress=None, traces=True):
         """pit_networks: self = contender's engine, baseline = the other player's engine.

@@ -34,6 +34,7 @@ extern "C" int az_abi_struct_size(int32_t which) {
     case AZ_STRUCT_GATHER_STATS: return (int)sizeof(az_gather_stats);
     case AZ_STRUCT_PROF: return (int)sizeof(az_prof);
     case AZ_STRUCT_MINMAX_CFG: return (int)sizeof(az_minmax_cfg);
+    case AZ_STRUCT_SOLVER_CFG: return (int)sizeof(az_solver_cfg);
   }
   return -1;
 }

@@ -188,6 +188,8 @@ struct az_engine {
   bool mm_on = false;
   az_minmax_cfg mm = {};
   GEnv* d_mm_roots = nullptr; double* d_mm_q = nullptr; int mm_cap = 0;
+  // Connect Four solver (solver.hip): staging for sv_cap states -- keys in, 7 q-values and 7 node counts per state out
+  unsigned long long* d_sv_keys = nullptr; int8_t* d_sv_q = nullptr; long long* d_sv_nodes = nullptr; int sv_cap = 0;
 };
 
 template <class T> inline int dalloc(az_engine* e, T** p, size_t n, bool zero = true) {

@@ -151,7 +151,7 @@ int az_abi_version(void);
 typedef enum {
   AZ_STRUCT_ENGINE_CFG = 0, AZ_STRUCT_MOVE_REC = 1, AZ_STRUCT_GAME_REC = 2, AZ_STRUCT_TRACE_BUF = 3, AZ_STRUCT_SELFPLAY_STATS = 4,
   AZ_STRUCT_SAMPLE = 5, AZ_STRUCT_DATASET_INFO = 6, AZ_STRUCT_LEARNING_STATUS = 7, AZ_STRUCT_TRAIN_CFG = 8, AZ_STRUCT_GATHER_STATS = 9,
-  AZ_STRUCT_PROF = 10, AZ_STRUCT_MINMAX_CFG = 11
+  AZ_STRUCT_PROF = 10, AZ_STRUCT_MINMAX_CFG = 11, AZ_STRUCT_SOLVER_CFG = 12
 } az_struct_id;
 int az_abi_struct_size(int32_t which);
 
@@ -363,6 +363,66 @@ int az_minmax_policy(const double* q, int32_t n, double tau, double* pi);
  * az_mcts_explore return AZ_ERR_STATE.  AZ_ERR_BAD_ARG for a depth outside 1..AZ_MINMAX_MAX_DEPTH, tau < 0 or not finite,
  * gamma <= 0 or not finite, a wrong struct_size, and AZ_GAME_GO9_PLANES (no device twin). */
 int az_engine_set_minmax(az_engine* e, const az_minmax_cfg* cfg);
+
+/* ---- Connect Four solver (Solver.Player, games/connect-four/solver.jl:17-99; the judge of scripts/pons_benchmark.jl) --------
+ * The reference pipes every position to an external program (Pascal Pons' solver) that it does not ship.  Here the exact search
+ * runs on the device (csrc/solver.hip): alpha-beta to the end of the game over bitboards, one query per lane.  This is parity
+ * with the scores the reference ships (the second column of games/connect-four/benchmark/Test_L*_R*), not with a run of the
+ * reference: its solver has never been executed against this one.
+ *   score                (solver.jl:58-89) Pons' convention, seen from the player to move: 0 a draw, +k he wins with his k-th stone
+ *                        counted from his last (22 - the stones he has played when he connects four), -k the opponent does.
+ *   value(game)          a terminal game: 0 for a full board, else remaining_stones(winner) + 1 = 22 - the winner's stones,
+ *                        negated because the side to move is the one that lost; otherwise the maximum of qvalue over the available
+ *                        actions (what the external solver answers).
+ *   qvalue(game, a)      next = play!(clone(game), a); -value(next) (the turn always changes).  A child that ends the game takes
+ *                        value's terminal branch: 0 for a full board, 21 - nstones / 2 (integer division, = (43 - nstones) / 2) for
+ *                        the mover who connects four with nstones on the board before his move.
+ *   query                one (state, action); a state is at most 7 of them, searched independently, each with its own node_budget.
+ *   strong / weak        weak = 0: exact scores.  weak != 0: only their sign, -1 / 0 / 1 (all the Pons benchmark needs): the same
+ *                        null-window passes, stopped as soon as the sign is known.
+ *   node_budget          nodes one search may enter.  A child that is terminal, or whose mover wins with his next stone, is
+ *                        decided without a node.  Every other child is searched: a position counts as a node each time it is
+ *                        entered (only once its mover is known to have no winning move; it returns at once where every move
+ *                        loses to the opponent's next stone or two cells are left), and the search closes in on the score with
+ *                        null-window passes from the child, so the child itself is entered once per pass.  A query whose search
+ *                        would enter more than node_budget nodes comes back AZ_SOLVER_UNSOLVED.  A solved query is exact,
+ *                        whatever the budget: a number that might be wrong is never returned.
+ *   value with unsolved  the maximum of the solved q is still the state's value if every unsolved move is PROVEN to be no better.
+ *   moves                In weak mode a solved +1 proves that.  Otherwise each unsolved query gets a second search that only asks
+ *                        whether its q exceeds the best solved one, again with node_budget nodes: the expensive moves are mostly
+ *                        the bad ones beside a quick win, whose exact score nobody needs.  The q of such a move stays
+ *                        AZ_SOLVER_UNSOLVED; only value[] profits.
+ *   determinism          the outputs for a state depend on (state, cfg) alone -- not on the rest of the batch, on earlier calls or
+ *                        on timing: there is no transposition table, no state is kept between calls, and what the lanes of a
+ *                        state exchange is that state's own results.  Node counts are reported for information and are not part
+ *                        of the contract.
+ *   think                (solver.jl:91-99) pi uniform over the available actions whose q equals the maximum, 0 elsewhere.
+ * The solver is not an arena player (no az_engine_set_solver): a duel starts on the empty board, which no per-move search reaches
+ * without an opening book -- the reference's own solver needs minutes there. */
+#define AZ_SOLVER_NA (-128)            /* q of a full column, and every q of a terminal state */
+#define AZ_SOLVER_UNSOLVED 127         /* the query needs more than node_budget nodes */
+/* Default budget, chosen from tools/solver_bench.py on an MI355X (profiles/solver/): at 2^20 nodes per query a call
+ * over 1000 positions takes at most about 3 s whichever Pons set it is, the end / easy and middle / easy sets get every value, and
+ * the others as far as a search without a transposition table goes (middle / medium 75 %, beginning / easy 96 %, beginning /
+ * medium 6 %, beginning / hard 0 % of the values).  2^16 is 16 times quicker but loses half of middle / medium; 2^23 costs 11-23 s
+ * a call for a few per cent more. */
+#define AZ_SOLVER_DEFAULT_BUDGET (1LL << 20)
+typedef struct {
+  int32_t struct_size;        /* sizeof(az_solver_cfg), set by az_solver_cfg_init */
+  int32_t weak;               /* 0: exact scores, else their sign */
+  int64_t node_budget;        /* > 0, per query */
+} az_solver_cfg;
+int az_solver_cfg_init(az_solver_cfg* cfg);                 /* strong, AZ_SOLVER_DEFAULT_BUDGET */
+/* Solver.value and Solver.qvalue of n Connect-Four states, on the device.  q: n*7 by FULL action index, AZ_SOLVER_NA for a full
+ * column, AZ_SOLVER_UNSOLVED for a query over budget.  value[i]: the maximum of q[i], or AZ_SOLVER_UNSOLVED if one of them is
+ * unsolved -- unless the solved ones already prove the maximum ("value with unsolved moves" above).  A terminal state gets value's terminal
+ * branch and q all AZ_SOLVER_NA.  nodes (n, or NULL): nodes searched below the state's queries.  The configuration is checked
+ * before the engine; AZ_ERR_BAD_ARG for a NULL cfg or buffer, a wrong struct_size, node_budget <= 0, n < 0 and an engine of
+ * another game (the message names it); n = 0 is AZ_OK. */
+int az_c4_solve(az_engine* e, const az_solver_cfg* cfg, const uint64_t* keys, int32_t n, int8_t* value, int8_t* q, int64_t* nodes);
+/* think()'s pi from the q-values by FULL action index (AZ_SOLVER_NA: unavailable, pi 0): pure host, no engine.
+ * AZ_ERR_BAD_ARG if an entry is AZ_SOLVER_UNSOLVED, or n_actions outside 1..AZ_MAX_ACTIONS. */
+int az_solver_policy(const int8_t* q, int32_t n_actions, double* pi);
 
 /* push_trace! (src/memory.jl:74-87): z (discounted, side relative) and t per move record. */
 int az_push_trace(const az_move_rec* moves, int32_t n, double gamma, double* z, double* t);

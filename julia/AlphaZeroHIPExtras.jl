@@ -233,5 +233,10 @@ const UNBOUND = Dict(
   :az_engine_set_minmax => "takes az_minmax_cfg by reference, see az_minmax_qvalues; MinMax duels run through the Python host's benchmark.run",
   :az_minmax_policy => "think()'s policy from q-values: only useful together with az_minmax_qvalues",
   :az_game_heuristic => "GI.heuristic_value is the reference's own on the Julia side; the device twin is checked against tests/minmax_ref.py",
+  # the Connect Four solver (games/connect-four/solver.jl): the Pons benchmark runs from the Python host (azhip/pons.py, tools/pons_benchmark.py);
+  # az_solver_cfg goes by reference like az_minmax_cfg, so the calls stay unbound for the same reason
+  :az_solver_cfg_init => "az_solver_cfg is two Int32 and one Int64 a host fills itself; no Julia caller yet (see the note above)",
+  :az_c4_solve => "takes az_solver_cfg by reference: no static ccall rule for that record yet; the Pons benchmark runs through the Python host",
+  :az_solver_policy => "think()'s policy from the solver's q-values: only useful together with az_c4_solve",
 )
 
