@@ -197,6 +197,11 @@ SYMBOLS = {
     "az_solver_cfg_init": [C.POINTER(SolverCfg)],
     "az_c4_solve": [_VP, C.POINTER(SolverCfg), _VP, _I32, _VP, _VP, _VP],
     "az_solver_policy": [_VP, _I32, _VP],
+    "az_solver_table_create": [_I32, _I32, C.POINTER(_VP)],
+    "az_solver_table_destroy": [_VP],
+    "az_solver_table_clear": [_VP],
+    "az_solver_table_info": [_VP, C.POINTER(_I32), C.POINTER(_I64), C.POINTER(_I64)],
+    "az_c4_solve_table": [_VP, C.POINTER(SolverCfg), _VP, _VP, _I32, _VP, _VP, _VP],
 }
 
 # az_struct_id order of include/azhip.h

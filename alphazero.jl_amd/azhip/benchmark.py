@@ -68,10 +68,11 @@ class Solver:
     """The perfect Connect-Four player (Solver.Player, games/connect-four/solver.jl) as a player description: host-stepped play only
     (play.play_game, scripts of the Pons benchmark); the device arena does not seat it (include/azhip.h "Connect Four solver")."""
     node_budget: object = None
+    table: object = None
     name = "Solver"
 
     def instantiate(self, gspec, nn):
-        return SolverMod.Player(node_budget=self.node_budget)
+        return SolverMod.Player(node_budget=self.node_budget, table=self.table)
 
 
 @dataclass

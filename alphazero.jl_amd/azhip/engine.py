@@ -278,9 +278,11 @@ class Engine:
         check(lib().az_engine_set_minmax(self._h, C.byref(cfg) if cfg is not None else None))
 
     # ---- Connect Four solver (games/connect-four/solver.jl) ------------------------------------------
-    def c4_solve(self, keys, weak=False, node_budget=None):
+    def c4_solve(self, keys, weak=False, node_budget=None, table=None):
         """Solver.value / Solver.qvalue for an (n, 2) uint64 key array -> value (n,) int8, q (n, 7) int8 by full action index
-        (SOLVER_NA: full column, SOLVER_UNSOLVED: the query needs more than node_budget nodes), nodes (n,) int64"""
+        (SOLVER_NA: full column, SOLVER_UNSOLVED: the query needs more than node_budget nodes), nodes (n,) int64.
+        table: a Solver.Table of this engine's device (az_c4_solve_table: exact or unsolved as without one, but which queries
+        finish depends on what the table holds); None = az_c4_solve"""
         keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, 2)
         n = keys.shape[0]
         cfg = L.SolverCfg()
@@ -291,7 +293,10 @@ class Engine:
         value = np.zeros(n, dtype=np.int8)
         q = np.zeros((n, 7), dtype=np.int8)
         nodes = np.zeros(n, dtype=np.int64)
-        check(lib().az_c4_solve(self._h, C.byref(cfg), _vp(keys), n, _vp(value), _vp(q), _vp(nodes)))
+        if table is None:
+            check(lib().az_c4_solve(self._h, C.byref(cfg), _vp(keys), n, _vp(value), _vp(q), _vp(nodes)))
+        else:
+            check(lib().az_c4_solve_table(self._h, C.byref(cfg), table._h, _vp(keys), n, _vp(value), _vp(q), _vp(nodes)))
         return value, q, nodes
 
     # ---- arena ----------------------------------------------------------------------------------

@@ -109,8 +109,8 @@ def _first_argmax(pi, avail):
 class _Thinker:
     """think + argmax(π) for a batch of states, by the kind of player: the chosen FULL action index per state (-1: no answer)"""
 
-    def __init__(self, player, gspec, num_workers):
-        self.player, self.gspec, self.W, self.engine, self.done = player, gspec, num_workers, None, 0
+    def __init__(self, player, gspec, num_workers, table=None):
+        self.player, self.gspec, self.W, self.engine, self.done, self.table = player, gspec, num_workers, None, 0, table
         p = player.player if isinstance(player, PlayerWithTemperature) else player
         self.core = p
         if isinstance(p, MctsPlayer):
@@ -150,7 +150,7 @@ class _Thinker:
             P, _ = p.network._eng().net_evaluate_keys(keys)
             return [_first_argmax(P[i], avail[i]) for i in range(n)]
         if isinstance(p, Solver.Player):
-            _, q, _ = self.gspec._eng().c4_solve(keys, node_budget=p.node_budget)
+            _, q, _ = self.gspec._eng().c4_solve(keys, node_budget=p.node_budget, table=self.table if self.table is not None else p.table)
             return [-1 if (q[i] == Solver.UNSOLVED).any() else _first_argmax(Solver.policy(q[i]), avail[i]) for i in range(n)]
         out = []                                            # any other AbstractPlayer: its own think, a position at a time
         for i in range(n):
@@ -159,16 +159,20 @@ class _Thinker:
         return out
 
 
-def test_player_on(make_player, gspec, bench, oracle=None, num_workers=NUM_WORKERS, node_budget=None, progress=None, cache=None):
+def test_player_on(make_player, gspec, bench, oracle=None, num_workers=NUM_WORKERS, node_budget=None, progress=None, cache=None, table=None):
     """one benchmark set -> dict(stage, difficulty, error_rate over the solved entries (None without one), solved, unsolved, entries, seconds).
-    cache: a dict that keeps the set's keys and solver answers for the next player tested on it with the same budget"""
+    cache: a dict that keeps the set's keys and solver answers for the next player tested on it with the same budget, apart for runs
+    with and without a table.  table: a Solver.Table for the judging call (and for the thinking of a Solver.Player under test); it
+    is meant to serve every set of a run"""
     t0 = time.perf_counter()
     ck = (bench.stage, bench.difficulty, len(bench.entries), node_budget)
+    if table is not None:
+        ck += ("table",)
     if cache is not None and ck in cache:
         keys, value, q = cache[ck]
     else:
         keys = states_of_strings([s for s, _ in bench.entries], gspec)
-        value, q, _ = gspec._eng().c4_solve(keys, weak=True, node_budget=node_budget)       # the whole set in one launch
+        value, q, _ = gspec._eng().c4_solve(keys, weak=True, node_budget=node_budget, table=table)   # the whole set in one launch
         if cache is not None:
             cache[ck] = keys, value, q
     if len(bench.entries) and (q == Solver.NA).all(axis=1).any():
@@ -177,7 +181,7 @@ def test_player_on(make_player, gspec, bench, oracle=None, num_workers=NUM_WORKE
         if v != Solver.UNSOLVED and int(v) != int(np.sign(score)):
             raise SolverMismatch("position %s (%s, %s): the solver's value has sign %d, the recorded score is %d"
                                  % (s, bench.stage, bench.difficulty, int(v), score))
-    thinker = _Thinker(make_player(oracle), gspec, num_workers)
+    thinker = _Thinker(make_player(oracle), gspec, num_workers, table)
     errs = unsolved = 0
     try:
         for off in range(0, len(bench.entries), num_workers):
@@ -200,9 +204,9 @@ def test_player_on(make_player, gspec, bench, oracle=None, num_workers=NUM_WORKE
                 unsolved=unsolved, entries=n, seconds=time.perf_counter() - t0)
 
 
-def test_player(make_player, gspec, benchmarks, oracle=None, num_workers=NUM_WORKERS, node_budget=None, progress=None, cache=None):
-    """pons_benchmark.jl:135-145: make_player(oracle) is tested on every set, in the order of `benchmarks`"""
-    return [test_player_on(make_player, gspec, b, oracle, num_workers, node_budget, progress, cache) for b in benchmarks]
+def test_player(make_player, gspec, benchmarks, oracle=None, num_workers=NUM_WORKERS, node_budget=None, progress=None, cache=None, table=None):
+    """pons_benchmark.jl:135-145: make_player(oracle) is tested on every set, in the order of `benchmarks`; one table serves them all"""
+    return [test_player_on(make_player, gspec, b, oracle, num_workers, node_budget, progress, cache, table) for b in benchmarks]
 
 
 def test_alphazero(gspec, nn, arena_mcts, benchmarks, **kw):

@@ -20,17 +20,51 @@ def policy(q):
     return pi
 
 
-class Player:
-    """Solver.Player(), solver.jl:17-31; node_budget: nodes per (state, action) query, None = the library's default"""
+class Table:
+    """The solver's transposition table (az_solver_table, include/azhip.h "Connect Four solver"): 2^log2_entries entries of 8 bytes
+    in the memory of `device` (23: 64 MB).  It belongs to whoever made it: hand it to any c4_solve call, Player or Pons run of that
+    device, strong or weak, and what one call learns the next one finds.  A context manager; close() frees it."""
 
-    def __init__(self, node_budget=None):
-        self.node_budget = node_budget
+    def __init__(self, log2_entries=23, device=0):
+        h = C.c_void_p()
+        L.check(L.lib().az_solver_table_create(int(device), int(log2_entries), C.byref(h)))
+        self._h, self.log2_entries, self.device = h, int(log2_entries), int(device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib().az_solver_table_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def clear(self):
+        L.check(L.lib().az_solver_table_clear(self._h))
+
+    def info(self):
+        """dict(log2_entries, bytes, occupied); occupied is counted on the device by this call"""
+        lg, nbytes, occ = C.c_int32(), C.c_int64(), C.c_int64()
+        L.check(L.lib().az_solver_table_info(self._h, C.byref(lg), C.byref(nbytes), C.byref(occ)))
+        return dict(log2_entries=lg.value, bytes=nbytes.value, occupied=occ.value)
+
+
+class Player:
+    """Solver.Player(), solver.jl:17-31; node_budget: nodes per (state, action) query, None = the library's default; table: a
+    Table its searches share (None: the tableless search)"""
+
+    def __init__(self, node_budget=None, table=None):
+        self.node_budget, self.table = node_budget, table
 
     def _solve(self, game, weak=False):
         spec = game.spec()
         if spec.game_id != L.GAME_CONNECT_FOUR:
             raise TypeError("Solver.Player plays Connect Four, not %s" % spec.name)
-        value, q, _ = spec._eng().c4_solve([game.current_state()], weak=weak, node_budget=self.node_budget)
+        value, q, _ = spec._eng().c4_solve([game.current_state()], weak=weak, node_budget=self.node_budget, table=self.table)
         return int(value[0]), q[0]
 
     def value(self, game):

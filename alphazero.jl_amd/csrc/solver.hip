@@ -1,5 +1,5 @@
 // solver.hip -- host side of the Connect Four solver (Solver.Player, games/connect-four/solver.jl): the entry points az_solver_cfg_init /
-// az_c4_solve / az_solver_policy of include/azhip.h.  Kernel: solver.h.
+// az_c4_solve / az_solver_policy and the transposition table az_solver_table_* / az_c4_solve_table of include/azhip.h.  Kernels: solver.h.
 #include "solver.h"
 
 static int check_solver_cfg(const az_solver_cfg* c) {
@@ -49,13 +49,88 @@ static int sv_reserve(az_engine* e, int n) {
   return AZ_OK;
 }
 
-extern "C" int az_c4_solve(az_engine* e, const az_solver_cfg* cfg, const uint64_t* keys, int32_t n, int8_t* value, int8_t* q, int64_t* nodes) {
+// az_solver_table: 2^log2 entries of 8 bytes in the HBM of one device (sv_entry, solver_search.h).  It belongs to its caller and
+// knows no engine: every az_c4_solve_table call of that device may be given it.
+struct az_solver_table {
+  int device = 0, log2 = 0;
+  unsigned long long* d_words = nullptr;
+  unsigned long long* d_count = nullptr;                             // az_solver_table_info's counter
+};
+#define TABLE(t) if (!(t)) return fail(AZ_ERR_BAD_ARG, "solver table is NULL"); HIPCHK(hipSetDevice((t)->device))
+
+extern "C" int az_solver_table_create(int32_t device, int32_t log2_entries, az_solver_table** out) {
+  if (!out) return fail(AZ_ERR_BAD_ARG, "out is NULL");
+  *out = nullptr;
+  if (log2_entries < 0 || log2_entries > 30) return fail(AZ_ERR_BAD_ARG, "solver table log2_entries = %d outside 0..30", (int)log2_entries);
+  int ndev = 0;
+  HIPCHK(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return fail(AZ_ERR_BAD_ARG, "device %d outside 0..%d", (int)device, ndev - 1);
+  HIPCHK(hipSetDevice(device));
+  az_solver_table* t = new (std::nothrow) az_solver_table();
+  if (!t) return fail(AZ_ERR_HIP, "out of host memory");
+  t->device = device; t->log2 = log2_entries;
+  const size_t bytes = sizeof(unsigned long long) << log2_entries;
+  hipError_t err = hipMalloc((void**)&t->d_words, bytes);
+  if (err == hipSuccess) err = hipMalloc((void**)&t->d_count, sizeof(unsigned long long));
+  if (err == hipSuccess) err = hipMemset(t->d_words, 0, bytes);
+  if (err == hipSuccess) err = hipDeviceSynchronize();
+  if (err != hipSuccess) {
+    if (t->d_words) (void)hipFree(t->d_words);
+    if (t->d_count) (void)hipFree(t->d_count);
+    delete t;
+    return fail(AZ_ERR_HIP, "a solver table of 2^%d entries (%zu bytes) on device %d: %s", (int)log2_entries, bytes, (int)device, hipGetErrorString(err));
+  }
+  *out = t;
+  return AZ_OK;
+}
+
+extern "C" int az_solver_table_destroy(az_solver_table* t) {
+  if (!t) return AZ_OK;
+  (void)hipSetDevice(t->device);
+  (void)hipDeviceSynchronize();                                      // no call that was given the table is still running
+  if (t->d_words) (void)hipFree(t->d_words);
+  if (t->d_count) (void)hipFree(t->d_count);
+  delete t;
+  return AZ_OK;
+}
+
+extern "C" int az_solver_table_clear(az_solver_table* t) {
+  TABLE(t);
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemset(t->d_words, 0, sizeof(unsigned long long) << t->log2));
+  HIPCHK(hipDeviceSynchronize());
+  return AZ_OK;
+}
+
+extern "C" int az_solver_table_info(az_solver_table* t, int32_t* log2_entries, int64_t* bytes, int64_t* occupied) {
+  TABLE(t);
+  if (log2_entries) *log2_entries = t->log2;
+  if (bytes) *bytes = (int64_t)sizeof(unsigned long long) << t->log2;
+  if (occupied) {                                                    // counted now, on the device
+    const long long entries = 1LL << t->log2;
+    unsigned long long cnt = 0;
+    HIPCHK(hipMemset(t->d_count, 0, sizeof cnt));
+    hipLaunchKernelGGL(k_sv_table_count, dim3((unsigned)std::min<long long>((entries + 255) / 256, 4096)), dim3(256), 0, 0,
+                       (const unsigned long long*)t->d_words, entries, t->d_count);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(&cnt, t->d_count, sizeof cnt, hipMemcpyDeviceToHost));
+    *occupied = (int64_t)cnt;
+  }
+  return AZ_OK;
+}
+
+// az_c4_solve (t == NULL, with_table false) and az_c4_solve_table
+static int c4_solve(az_engine* e, const az_solver_cfg* cfg, bool with_table, az_solver_table* t, const uint64_t* keys, int32_t n, int8_t* value, int8_t* q, int64_t* nodes) {
   AZCHK(check_solver_cfg(cfg));
   ENGINE(e);
   if (e->cfg.game != AZ_GAME_CONNECT_FOUR) {
     static const char* const names[] = {"Connect Four", "Tic-tac-toe", "Mancala", "the 9x9x4 plane geometry"};
     const int gid = (int)e->cfg.game;
     return fail(AZ_ERR_BAD_ARG, "the solver solves Connect Four; this engine plays %s (game %d)", gid >= 0 && gid < 4 ? names[gid] : "another game", gid);
+  }
+  if (with_table) {
+    if (!t) return fail(AZ_ERR_BAD_ARG, "solver table is NULL");
+    if (t->device != e->device) return fail(AZ_ERR_BAD_ARG, "the solver table lives on device %d, the engine on device %d", t->device, e->device);
   }
   if (n < 0) return fail(AZ_ERR_BAD_ARG, "n = %d states", (int)n);
   if (n == 0) return AZ_OK;
@@ -65,8 +140,13 @@ extern "C" int az_c4_solve(az_engine* e, const az_solver_cfg* cfg, const uint64_
   AZCHK(sv_reserve(e, n));
   HIPCHK(hipMemcpyAsync(e->d_sv_keys, keys, sizeof(uint64_t) * 2 * (size_t)n, hipMemcpyHostToDevice, e->stream));
   signed char* d_bounded = (signed char*)e->d_sv_q + (size_t)e->sv_cap * 7;
-  hipLaunchKernelGGL(k_c4_solve, dim3((unsigned)((n + SV_STATES - 1) / SV_STATES)), dim3(SV_LANES), 0, e->stream,
-                     (const unsigned long long*)e->d_sv_keys, (int)n, (int)(cfg->weak != 0), (long long)cfg->node_budget, (signed char*)e->d_sv_q, d_bounded, e->d_sv_nodes);
+  const dim3 grid((unsigned)((n + SV_STATES - 1) / SV_STATES));
+  if (with_table)
+    hipLaunchKernelGGL(k_c4_solve_table, grid, dim3(SV_LANES), 0, e->stream, t->d_words, t->log2,
+                       (const unsigned long long*)e->d_sv_keys, (int)n, (int)(cfg->weak != 0), (long long)cfg->node_budget, (signed char*)e->d_sv_q, d_bounded, e->d_sv_nodes);
+  else
+    hipLaunchKernelGGL(k_c4_solve, grid, dim3(SV_LANES), 0, e->stream,
+                       (const unsigned long long*)e->d_sv_keys, (int)n, (int)(cfg->weak != 0), (long long)cfg->node_budget, (signed char*)e->d_sv_q, d_bounded, e->d_sv_nodes);
   HIPCHK(hipGetLastError());
   std::vector<long long> qn(nodes ? nq : 0);
   std::vector<int8_t> bounded(nq);
@@ -75,20 +155,7 @@ extern "C" int az_c4_solve(az_engine* e, const az_solver_cfg* cfg, const uint64_
   if (nodes) HIPCHK(hipMemcpyAsync(qn.data(), e->d_sv_nodes, sizeof(long long) * nq, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   for (int i = 0; i < n; ++i) {
-    const int8_t* qi = q + (size_t)i * 7;
-    const GEnv g = ConnectFour::from_key(keys[2 * (size_t)i], keys[2 * (size_t)i + 1]);
-    if (g.fin & 1) {                                                 // Solver.value's terminal branch (solver.jl:69-77): the side to move has lost, or a draw
-      const int stones = az_popc64((g.a | g.b) & ~AZ_BLACK_BIT);
-      value[i] = (g.fin >> 1) ? (int8_t)-(22 - (stones + 1) / 2) : (int8_t)0;
-    } else {
-      int best = AZ_SOLVER_NA;
-      bool open = false;                                             // an unsolved q that is not known to be <= the best solved one
-      for (int a = 0; a < 7; ++a) {
-        if (qi[a] == AZ_SOLVER_UNSOLVED) open = open || !bounded[(size_t)i * 7 + a];
-        else if (qi[a] != AZ_SOLVER_NA && qi[a] > best) best = qi[a];
-      }
-      value[i] = (open || best == AZ_SOLVER_NA) ? (int8_t)AZ_SOLVER_UNSOLVED : (int8_t)best;
-    }
+    value[i] = (int8_t)sv_state_value(keys[2 * (size_t)i], keys[2 * (size_t)i + 1], q + (size_t)i * 7, bounded.data() + (size_t)i * 7);
     if (nodes) {
       long long s = 0;
       for (int a = 0; a < 7; ++a) s += qn[(size_t)i * 7 + a];
@@ -96,4 +163,12 @@ extern "C" int az_c4_solve(az_engine* e, const az_solver_cfg* cfg, const uint64_
     }
   }
   return AZ_OK;
+}
+
+extern "C" int az_c4_solve(az_engine* e, const az_solver_cfg* cfg, const uint64_t* keys, int32_t n, int8_t* value, int8_t* q, int64_t* nodes) {
+  return c4_solve(e, cfg, false, nullptr, keys, n, value, q, nodes);
+}
+
+extern "C" int az_c4_solve_table(az_engine* e, const az_solver_cfg* cfg, az_solver_table* t, const uint64_t* keys, int32_t n, int8_t* value, int8_t* q, int64_t* nodes) {
+  return c4_solve(e, cfg, true, t, keys, n, value, q, nodes);
 }

@@ -366,7 +366,8 @@ int az_engine_set_minmax(az_engine* e, const az_minmax_cfg* cfg);
 
 /* ---- Connect Four solver (Solver.Player, games/connect-four/solver.jl:17-99; the judge of scripts/pons_benchmark.jl) --------
  * The reference pipes every position to an external program (Pascal Pons' solver) that it does not ship.  Here the exact search
- * runs on the device (csrc/solver.hip): alpha-beta to the end of the game over bitboards, one query per lane.  This is parity
+ * runs on the device (csrc/solver.hip): alpha-beta to the end of the game over bitboards, one query per lane, without
+ * (az_c4_solve) or with (az_c4_solve_table) a transposition table.  This is parity
  * with the scores the reference ships (the second column of games/connect-four/benchmark/Test_L*_R*), not with a run of the
  * reference: its solver has never been executed against this one.
  *   score                (solver.jl:58-89) Pons' convention, seen from the player to move: 0 a draw, +k he wins with his k-th stone
@@ -392,10 +393,21 @@ int az_engine_set_minmax(az_engine* e, const az_minmax_cfg* cfg);
  *                        whether its q exceeds the best solved one, again with node_budget nodes: the expensive moves are mostly
  *                        the bad ones beside a quick win, whose exact score nobody needs.  The q of such a move stays
  *                        AZ_SOLVER_UNSOLVED; only value[] profits.
- *   determinism          the outputs for a state depend on (state, cfg) alone -- not on the rest of the batch, on earlier calls or
- *                        on timing: there is no transposition table, no state is kept between calls, and what the lanes of a
- *                        state exchange is that state's own results.  Node counts are reported for information and are not part
- *                        of the contract.
+ *   determinism          az_c4_solve ONLY: the outputs for a state depend on (state, cfg) alone -- not on the rest of the batch, on
+ *                        earlier calls or on timing: it has no transposition table, no state is kept between calls, and what the
+ *                        lanes of a state exchange is that state's own results.  Node counts are reported for information and are
+ *                        not part of the contract.  az_c4_solve_table gives this up for reach: see "table" below.
+ *   table                az_c4_solve_table searches with a transposition table (az_solver_table) that every lane of the call reads
+ *                        and writes, and that stays filled for the next call, and tries the moves in the order of the threats
+ *                        they create.  EXACT OR UNSOLVED holds as it does without one: a solved q or value is exact whatever the
+ *                        table held when the call began and whoever else was writing to it meanwhile (an entry carries the whole
+ *                        key of its position, says something that is true of that position alone -- for any window, mode, budget
+ *                        and caller -- and is read and written as one 64-bit word); AZ_SOLVER_UNSOLVED otherwise.  WHICH queries
+ *                        come in under node_budget, and the node counts, are no longer fixed: they depend on the table's contents
+ *                        (its size, earlier calls, the rest of the batch) and on timing.  A position that was solved may, with
+ *                        another table or at another time, come back unsolved and the other way round; two solved answers for
+ *                        one position never differ.  Terminal states, children decided without a node, AZ_SOLVER_NA and the
+ *                        argument checks are those of az_c4_solve.
  *   think                (solver.jl:91-99) pi uniform over the available actions whose q equals the maximum, 0 elsewhere.
  * The solver is not an arena player (no az_engine_set_solver): a duel starts on the empty board, which no per-move search reaches
  * without an opening book -- the reference's own solver needs minutes there. */
@@ -405,7 +417,9 @@ int az_engine_set_minmax(az_engine* e, const az_minmax_cfg* cfg);
  * over 1000 positions takes at most about 3 s whichever Pons set it is, the end / easy and middle / easy sets get every value, and
  * the others as far as a search without a transposition table goes (middle / medium 75 %, beginning / easy 96 %, beginning /
  * medium 6 %, beginning / hard 0 % of the values).  2^16 is 16 times quicker but loses half of middle / medium; 2^23 costs 11-23 s
- * a call for a few per cent more. */
+ * a call for a few per cent more.  az_c4_solve_table takes the same default: with a table of 2^23 entries it gets every value of
+ * middle / medium and beginning / easy and 66 % of beginning / medium's (profiles/solver/solver_sets_table.json), at 11-28 s a call
+ * where lanes run out of budget, because a node costs more there; the budget still is what bounds a call. */
 #define AZ_SOLVER_DEFAULT_BUDGET (1LL << 20)
 typedef struct {
   int32_t struct_size;        /* sizeof(az_solver_cfg), set by az_solver_cfg_init */
@@ -420,6 +434,23 @@ int az_solver_cfg_init(az_solver_cfg* cfg);                 /* strong, AZ_SOLVER
  * before the engine; AZ_ERR_BAD_ARG for a NULL cfg or buffer, a wrong struct_size, node_budget <= 0, n < 0 and an engine of
  * another game (the message names it); n = 0 is AZ_OK. */
 int az_c4_solve(az_engine* e, const az_solver_cfg* cfg, const uint64_t* keys, int32_t n, int8_t* value, int8_t* q, int64_t* nodes);
+/* The transposition table of az_c4_solve_table: 2^log2_entries entries of 8 bytes in the memory of `device`, zeroed (empty).  It
+ * belongs to the caller, as an az_memory does, and is tied to no engine, call or mode: any engine of its device may be given it, in
+ * strong and weak calls in any order, and what one call learns the next one finds -- the 7000 queries of a Pons set are positions of
+ * the same few openings.  log2_entries 0..30 (AZ_ERR_BAD_ARG outside; 23 = 64 MB is what the Python host takes); a table of one
+ * entry is legal and merely replaces on every store.  clear empties it.  info: any of the three pointers may be NULL; occupied =
+ * the entries that are not empty, counted on the device when asked for.  destroy(NULL) is AZ_OK.  No call that uses a table may
+ * run while it is cleared or destroyed. */
+typedef struct az_solver_table az_solver_table;
+int az_solver_table_create(int32_t device, int32_t log2_entries, az_solver_table** out);
+int az_solver_table_destroy(az_solver_table* t);
+int az_solver_table_clear(az_solver_table* t);
+int az_solver_table_info(az_solver_table* t, int32_t* log2_entries, int64_t* bytes, int64_t* occupied);
+/* az_c4_solve with the table `t` ("table" above): the same outputs, the same argument checks in the same order, and after the
+ * engine's game AZ_ERR_BAD_ARG for a NULL table and for a table of another device than the engine's (the message names both).
+ * Exact or unsolved as az_c4_solve; which queries finish within node_budget, and nodes[], depend on the table and on timing. */
+int az_c4_solve_table(az_engine* e, const az_solver_cfg* cfg, az_solver_table* t, const uint64_t* keys, int32_t n, int8_t* value, int8_t* q,
+                      int64_t* nodes);
 /* think()'s pi from the q-values by FULL action index (AZ_SOLVER_NA: unavailable, pi 0): pure host, no engine.
  * AZ_ERR_BAD_ARG if an entry is AZ_SOLVER_UNSOLVED, or n_actions outside 1..AZ_MAX_ACTIONS. */
 int az_solver_policy(const int8_t* q, int32_t n_actions, double* pi);

@@ -238,5 +238,11 @@ const UNBOUND = Dict(
   :az_solver_cfg_init => "az_solver_cfg is two Int32 and one Int64 a host fills itself; no Julia caller yet (see the note above)",
   :az_c4_solve => "takes az_solver_cfg by reference: no static ccall rule for that record yet; the Pons benchmark runs through the Python host",
   :az_solver_policy => "think()'s policy from the solver's q-values: only useful together with az_c4_solve",
+  # the solver's transposition table: it only serves az_c4_solve_table, which stays unbound as az_c4_solve does
+  :az_solver_table_create => "the table of az_c4_solve_table, which is unbound; the Python host owns it (azhip.Solver.Table)",
+  :az_solver_table_destroy => "see az_solver_table_create",
+  :az_solver_table_clear => "see az_solver_table_create",
+  :az_solver_table_info => "see az_solver_table_create",
+  :az_c4_solve_table => "takes az_solver_cfg by reference, as az_c4_solve: no static ccall rule for that record yet; the Pons benchmark runs through the Python host",
 )
 

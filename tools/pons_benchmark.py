@@ -7,7 +7,12 @@ the best network after each of --iters iterations of examples/iteration.py's tra
 reference's documentation, in miniature).  Positions the solver cannot judge within its node budget are left out and counted.
 
     python tools/pons_benchmark.py [--dir tests/golden/pons] [--params FILE] [--iters 3] [--games 256] [--sims 100] [--workers 128]
-                                   [--budget N] [--out profiles/solver/pons_benchmark.json]
+                                   [--budget N] [--out profiles/solver/pons_benchmark.json] [--table-bits N] [--players minmax,network_only]
+
+--table-bits N > 0: the solver judges with one transposition table of 2^N entries (azhip.Solver.Table) that serves all six sets
+and every player of the run; --out defaults to profiles/solver/pons_benchmark_table.json then, and beside each row's `unsolved`
+(the positions left out) stands `unsolved_tableless`, the same figure of the tableless run in profiles/solver/pons_benchmark.json.
+--players: which kinds of player to test (default: minmax, network_only and alphazero).
 """
 import argparse
 import json
@@ -37,24 +42,39 @@ def main():
     ap.add_argument("--sims", type=int, default=100)
     ap.add_argument("--workers", type=int, default=128)
     ap.add_argument("--budget", type=int, default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "solver", "pons_benchmark.json"))
+    ap.add_argument("--table-bits", type=int, default=0)
+    ap.add_argument("--players", default="minmax,network_only,alphazero")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    tableless = os.path.join(ROOT, "profiles", "solver", "pons_benchmark.json")
+    a.out = a.out or (os.path.join(ROOT, "profiles", "solver", "pons_benchmark_table.json") if a.table_bits > 0 else tableless)
+    players = set(a.players.split(","))
+    table = azhip.Solver.Table(a.table_bits) if a.table_bits > 0 else None
+    before = json.load(open(tableless)) if table is not None and os.path.exists(tableless) else {}
     gspec = azhip.ConnectFourSpec()
     benchmarks = Pons.load_benchmarks(a.dir)
-    cache, kw = {}, dict(num_workers=a.workers, node_budget=a.budget)
+    cache, kw = {}, dict(num_workers=a.workers, node_budget=a.budget, table=table)
     out = {"node_budget": a.budget or azhip._lib.SOLVER_DEFAULT_BUDGET, "sets": [[b.stage, b.difficulty, len(b.entries)] for b in benchmarks]}
+    if table is not None:
+        out["table_bits"] = a.table_bits
 
     def emit(name, res):
         out[name] = rows_of(res)
+        if before.get("node_budget") == out["node_budget"]:
+            for r, r0 in zip(out[name], before.get(name, [])):
+                r["unsolved_tableless"] = r0["unsolved"]
         print(json.dumps({"player": name, "sets": out[name]}), flush=True)
 
-    emit("minmax", Pons.test_player(lambda _: MinMax.Player(depth=5, amplify_rewards=True, τ=0), gspec, benchmarks, cache=cache, **kw))
+    if "minmax" in players:
+        emit("minmax", Pons.test_player(lambda _: MinMax.Player(depth=5, amplify_rewards=True, τ=0), gspec, benchmarks, cache=cache, **kw))
     arena_mcts = azhip.MctsParams(num_iters_per_turn=a.sims, cpuct=2.0, dirichlet_noise_ϵ=0.05, dirichlet_noise_α=1.0,
                                   temperature=azhip.ConstSchedule(0.2))                         # examples/iteration.py's arena.mcts
 
     def test_network(tag, nn):
-        emit("network_only" + tag, Pons.test_player(lambda net: azhip.NetworkPlayer(net), gspec, benchmarks, oracle=nn, cache=cache, **kw))
-        emit("alphazero" + tag, Pons.test_alphazero(gspec, nn, arena_mcts, benchmarks, cache=cache, **kw))
+        if "network_only" in players:
+            emit("network_only" + tag, Pons.test_player(lambda net: azhip.NetworkPlayer(net), gspec, benchmarks, oracle=nn, cache=cache, **kw))
+        if "alphazero" in players:
+            emit("alphazero" + tag, Pons.test_alphazero(gspec, nn, arena_mcts, benchmarks, cache=cache, **kw))
 
     if a.params:
         test_network("", load_params(a.params, gspec))
@@ -84,10 +104,14 @@ def main():
                               "nn_replaced": bool(lr.checkpoints[-1].nn_replaced)}), flush=True)
             test_network("_iter%d" % (it + 1), bestnn)
         memory.close()
+    if table is not None:
+        out["table_occupied"] = table.info()["occupied"]
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
+    if table is not None:
+        table.close()
     azhip.clear_engine_cache()
 
 
