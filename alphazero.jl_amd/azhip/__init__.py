@@ -10,7 +10,7 @@ from ._lib import (AzError, GAME_CONNECT_FOUR, GAME_GO9_PLANES, GAME_MANCALA, GA
 from .engine import Engine, cached_engine, clear_engine_cache, default_cfg
 from .comm import Comm
 from .params import ArenaParams, ConstSchedule, MctsParams, PLSchedule, SimParams
-from .game import ConnectFourSpec, GameEnv, GameSpec, MancalaSpec, TicTacToeSpec
+from .game import ConnectFourSpec, GameEnv, GameSpec, Go9PlanesSpec, MancalaSpec, TicTacToeSpec
 from .network import ResNet, ResNetHP
 from . import mcts as MCTS
 from . import minmax as MinMax
@@ -18,7 +18,7 @@ from . import solver as Solver
 from . import pons as Pons
 from .play import MctsPlayer, NetworkPlayer, PlayerWithTemperature, TwoPlayers, flipped_colors, play_game
 from .trace import Trace
-from .memory import Dataset, MemoryBuffer, TrainingSample, push_trace
+from .memory import Dataset, MemoryBuffer, TensorDataset, TrainingSample, push_trace
 from .simulations import Simulator, record_trace, self_play_measurements, simulate, simulate_distributed
 from .training import SelfPlayParams, SelfPlayReport, broadcast_params, self_play_step
 from .arena import Evaluation, compare_networks, pit_networks, pit_players

@@ -14,7 +14,7 @@ ABI_VERSION = 4              # include/azhip.h AZ_ABI_VERSION: struct layouts be
 REPLACEMENT_GAME_BIT = 0x40000000
 AZ_OK, AZ_ERR_BAD_ARG, AZ_ERR_CAPACITY, AZ_ERR_HIP, AZ_ERR_STATE = 0, -1, -2, -3, -4
 GAME_CONNECT_FOUR, GAME_TICTACTOE, GAME_MANCALA = 0, 1, 2
-GAME_GO9_PLANES = 3          # network-only geometry (9, 9, 4), 82 actions: az_net_forward for host-stepped 9x9 Go
+GAME_GO9_PLANES = 3          # network-only geometry (9, 9, 4), 82 actions: az_net_forward and the trainer (on tensors) for host-stepped 9x9 Go
 ORACLE_UNIFORM, ORACLE_HASH, ORACLE_RESNET, ORACLE_ROLLOUT = 0, 1, 2, 3
 MAX_ACTIONS = 9
 SCHED_MAX = 8
@@ -165,6 +165,7 @@ SYMBOLS = {
     "az_memory_new_batch": [_VP],
     "az_memory_empty": [_VP],
     "az_dataset_create": [_VP, _I32, _I32, _I32, _I32, C.POINTER(_VP)],
+    "az_dataset_create_from_tensors": [_I32, _I32, _I64, _VP, _VP, _VP, _VP, _VP, C.POINTER(_VP)],
     "az_dataset_destroy": [_VP],
     "az_dataset_get_info": [_VP, C.POINTER(DatasetInfo)],
     "az_dataset_read": [_VP, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _VP],

@@ -32,10 +32,10 @@ class GameSpec:
         return list(range(1, self.num_actions() + 1))     # 1-based like the reference
 
     def num_actions(self):
-        return {L.GAME_CONNECT_FOUR: 7, L.GAME_TICTACTOE: 9, L.GAME_MANCALA: 6}[self.game_id]
+        return {L.GAME_CONNECT_FOUR: 7, L.GAME_TICTACTOE: 9, L.GAME_MANCALA: 6, L.GAME_GO9_PLANES: 82}[self.game_id]
 
     def state_dim(self):
-        return {L.GAME_CONNECT_FOUR: (7, 6, 3), L.GAME_TICTACTOE: (3, 3, 3), L.GAME_MANCALA: (14, 1, 5)}[self.game_id]
+        return {L.GAME_CONNECT_FOUR: (7, 6, 3), L.GAME_TICTACTOE: (3, 3, 3), L.GAME_MANCALA: (14, 1, 5), L.GAME_GO9_PLANES: (9, 9, 4)}[self.game_id]
 
     def init(self, state=None):
         return GameEnv(self, state)
@@ -76,7 +76,27 @@ class MancalaSpec(GameSpec):
     game_id, name = L.GAME_MANCALA, "mancala"
 
 
+class Go9PlanesSpec(GameSpec):
+    """The 9 x 9 x 4 plane geometry with 82 actions (BASELINE configs[4]: OpenSpiel 9x9 Go): geometry only.  The rules and the tree
+    of such a game stay on the host, so there is no environment to create; ResNet(gspec, hp), TensorDataset and Trainer take it."""
+    game_id, name = L.GAME_GO9_PLANES, "go9-planes"
+
+    def init(self, state=None):
+        raise NotImplementedError("Go9PlanesSpec carries the network geometry only: the game's rules run on the host")
+
+    def vectorize_state(self, state):
+        raise NotImplementedError("Go9PlanesSpec carries the network geometry only: the host encodes its own states")
+
+
 SPECS = {"connect-four": ConnectFourSpec, "tictactoe": TicTacToeSpec, "mancala": MancalaSpec}
+
+
+def spec_of_game_id(game_id):
+    """the GameSpec of an az_game_id, the network-only geometry included"""
+    for cls in (ConnectFourSpec, TicTacToeSpec, MancalaSpec, Go9PlanesSpec):
+        if cls.game_id == game_id:
+            return cls()
+    raise ValueError("unknown game id %r" % (game_id,))
 
 
 class GameEnv:

@@ -8,7 +8,7 @@ from dataclasses import dataclass
 
 from . import _lib as L
 from .engine import Engine
-from .memory import Dataset, MemoryBuffer
+from .memory import Dataset, MemoryBuffer, TensorDataset
 
 CONSTANT_WEIGHT, LOG_WEIGHT, LINEAR_WEIGHT = L.WEIGHT_CONSTANT, L.WEIGHT_LOG, L.WEIGHT_LINEAR
 
@@ -75,11 +75,24 @@ class Samples:
 
 class Trainer:
     """Trainer(gspec, network, samples, params; test_mode) (learning.jl:98-121) over a device MemoryBuffer:
-    merge_by_state (if use_position_averaging), convert_samples, Wmean, Hp; the network in test mode."""
+    merge_by_state (if use_position_averaging), convert_samples, Wmean, Hp; the network in test mode.
 
-    def __init__(self, gspec, network, mem: MemoryBuffer, params: LearningParams, use_symmetries=False, last_batch=False, device=0):
+    `mem` may also be a TensorDataset: samples the caller converted itself (the only way for the 9x9x4 geometry).  The trainer then
+    takes them as they are -- use_symmetries, last_batch and params.use_position_averaging act on a memory's samples and are an
+    error with tensors -- and does not own the data set: the caller closes it."""
+
+    def __init__(self, gspec, network, mem, params: LearningParams, use_symmetries=False, last_batch=False, device=0):
         self.gspec, self.params = gspec, params
-        self.data = Dataset(mem, last_batch, use_symmetries, params.use_position_averaging, params.samples_weighing_policy)
+        self._owns_data = not isinstance(mem, TensorDataset)
+        if isinstance(mem, TensorDataset):
+            for name, on in (("use_symmetries", use_symmetries), ("last_batch", last_batch), ("params.use_position_averaging", params.use_position_averaging)):
+                if on:
+                    raise ValueError("%s applies to a MemoryBuffer's samples, not to a TensorDataset: augment / select / merge before converting" % name)
+            if mem.gspec != gspec:
+                raise ValueError("the TensorDataset was made for %s" % type(mem.gspec).__name__)
+            self.data = mem
+        else:
+            self.data = Dataset(mem, last_batch, use_symmetries, params.use_position_averaging, params.samples_weighing_policy)
         self.Wmean, self.Hp = self.data.Wmean, self.data.Hp
         self._hyper = network.hyper
         kw = network.engine_options()
@@ -91,8 +104,10 @@ class Trainer:
         if getattr(self, "_tr", None):
             L.lib().az_trainer_destroy(self._tr)
             self._tr = None
-        self.data.close()
-        self._eng.close()
+        if getattr(self, "_owns_data", False):
+            self.data.close()
+        if getattr(self, "_eng", None):
+            self._eng.close()
 
     # ---- the optimiser step (learning.jl:123-141) ----
     def _trainer(self, optimiser=None, batch_norm_momentum=None, seed=1):
@@ -180,7 +195,9 @@ class Trainer:
     def samples_report(self):
         """samples_report(tr) (learning.jl:183-190); num_boards needs the merged count"""
         status = self.learning_status()
-        if self.params.use_position_averaging:
+        if isinstance(self.data, TensorDataset):
+            num_boards = len(self.data)                               # the caller's tensors, one board per sample
+        elif self.params.use_position_averaging:
             num_boards = len(self.data)
         else:
             raise NotImplementedError("num_boards of an un-merged Trainer: build a second data set with use_position_averaging")

@@ -201,3 +201,59 @@ class Dataset:
         vp = lambda a: a.ctypes.data_as(_C.c_void_p)
         _L.check(_L.lib().az_dataset_read(self._h, 0, n, None, vp(W), vp(X), vp(A), vp(P), vp(V)))
         return W, X, A, P, V
+
+
+class TensorDataset(Dataset):
+    """The data of a Trainer made from (W, X, A, P, V) tensors the caller converted itself (az_dataset_create_from_tensors):
+    W (n,), X (n, C, H, W) as Network.forward_normalized takes it, A and P (n, num_actions), V (n,).  For hosts that step their own
+    game -- the 9x9x4 geometry has no replay memory on the device -- or label positions by other means.  Same surface as Dataset,
+    but no TrainingSamples stand behind it: samples() and raw_samples() raise."""
+
+    def __init__(self, gspec_or_game_id, W, X, A, P, V, device=0):
+        gspec, arrays = self.validate(gspec_or_game_id, W, X, A, P, V)          # before the library is loaded
+        self.gspec = gspec
+        W, X, A, P, V = arrays
+        vp = lambda a: a.ctypes.data_as(_C.c_void_p)
+        h = _C.c_void_p()
+        _L.check(_L.lib().az_dataset_create_from_tensors(gspec.game_id, int(device), len(W), vp(W), vp(X), vp(A), vp(P), vp(V), _C.byref(h)))
+        self._h = h
+        info = _L.DatasetInfo()
+        _L.check(_L.lib().az_dataset_get_info(h, _C.byref(info)))
+        self.num_samples, self.sum_n, self.Wtot, self.Wmean, self.Hp = info.num_samples, info.sum_n, info.Wtot, info.Wmean, info.Hp
+
+    @staticmethod
+    def validate(gspec_or_game_id, W, X, A, P, V):
+        """(gspec, contiguous float32 arrays) or ValueError: ranks, shapes against the geometry, one sample count, float32-convertible"""
+        from .game import GameSpec, spec_of_game_id
+        gspec = gspec_or_game_id if isinstance(gspec_or_game_id, GameSpec) else spec_of_game_id(gspec_or_game_id)
+        nA = gspec.num_actions()
+        w, h, c = gspec.state_dim()
+        want = {"W": (), "X": (c, h, w), "A": (nA,), "P": (nA,), "V": ()}
+        out = []
+        n = None
+        for name, a in zip("WXAPV", (W, X, A, P, V)):
+            try:
+                a = np.asarray(a)
+                if a.dtype.kind not in "fiub":
+                    raise TypeError("dtype %s" % a.dtype)
+                a = np.ascontiguousarray(a, dtype=np.float32)
+            except (TypeError, ValueError) as e:
+                raise ValueError("%s cannot be converted to float32: %s" % (name, e)) from None
+            if a.ndim != 1 + len(want[name]):
+                raise ValueError("%s must have %d dimensions (sample index first), got shape %s" % (name, 1 + len(want[name]), a.shape))
+            if tuple(a.shape[1:]) != want[name]:
+                raise ValueError("%s must have shape (n,%s), got %s" % (name, "".join(" %d," % k for k in want[name]), a.shape))
+            if n is None:
+                n = a.shape[0]
+            elif a.shape[0] != n:
+                raise ValueError("%s holds %d samples, W holds %d" % (name, a.shape[0], n))
+            out.append(a)
+        if n < 1:
+            raise ValueError("at least one sample is needed")
+        return gspec, out
+
+    def raw_samples(self):
+        raise TypeError("a data set made from tensors holds no TrainingSamples: use tensors()")
+
+    def samples(self):
+        raise TypeError("a data set made from tensors holds no TrainingSamples: use tensors()")

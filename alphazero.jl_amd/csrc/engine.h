@@ -47,6 +47,18 @@ int fail(int code, const char* fmt, ...);   // sets az_last_error() (thread-loca
     default: return fail(AZ_ERR_BAD_ARG, "unknown game id %d", (int)(gid));    \
   }
 
+// The four NETWORK geometries: the three device twins and the 9x9x4 plane geometry, which has no rules (games.h Go9Planes).  For code
+// that reads tensors only -- the optimiser step's MFMA kernels (train.hip); the tree, the replay memory and everything else that
+// calls a game's rules stay on DISPATCH_GAME.
+#define DISPATCH_GEOMETRY(gid, ...)                               \
+  switch (gid) {                                                  \
+    case AZ_GAME_CONNECT_FOUR: { using Gm = ConnectFour; __VA_ARGS__; break; } \
+    case AZ_GAME_TICTACTOE: { using Gm = TicTacToe; __VA_ARGS__; break; }      \
+    case AZ_GAME_MANCALA: { using Gm = Mancala; __VA_ARGS__; break; }          \
+    case AZ_GAME_GO9_PLANES: { using Gm = Go9Planes; __VA_ARGS__; break; }     \
+    default: return fail(AZ_ERR_BAD_ARG, "unknown game id %d", (int)(gid));    \
+  }
+
 struct GameInfo { int A, APAD, W, H, C, P, max_plies, node_bytes; };
 inline bool game_info(int gid, GameInfo* gi) {
   switch (gid) {
@@ -310,6 +322,7 @@ struct az_dataset {
   GEnv* d_envs;
   float *d_W, *d_X, *d_A, *d_P, *d_V;
   std::vector<void*> allocs;
+  bool own_stream = false;           // az_dataset_create_from_tensors: no memory behind it whose stream it could share; d_samples and d_envs are NULL
 };
 // push_trace! (memory.jl:74-87) of ng games whose move records are ALREADY on the device: game g = d_moves[first[g] .. +cnt[g])
 int memory_push_device(az_memory* m, const az_move_rec* d_moves, const std::vector<long long>& first, const std::vector<int>& cnt, double gamma);

@@ -265,7 +265,7 @@ extern "C" int az_memory_create(int32_t game, int32_t device, int64_t capacity, 
   *out = nullptr;
   GameInfo gi;
   if (!game_info(game, &gi)) return fail(AZ_ERR_BAD_ARG, "unknown game id %d", game);
-  if (game == AZ_GAME_GO9_PLANES) return fail(AZ_ERR_BAD_ARG, "game id %d is a network-only tensor geometry (no device twin): the device replay memory needs the game's state keys", game);
+  if (game == AZ_GAME_GO9_PLANES) return fail(AZ_ERR_BAD_ARG, "game id %d is a network-only tensor geometry (no device twin): the device replay memory needs the game's state keys; az_dataset_create_from_tensors takes the converted samples of such a game", game);
   if (capacity < 1 || capacity > (1LL << 31) - 1) return fail(AZ_ERR_BAD_ARG, "capacity must be in 1..2^31-1");
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
@@ -466,6 +466,7 @@ extern "C" int az_dataset_destroy(az_dataset* d) {
   if (!d) return AZ_OK;
   (void)hipSetDevice(d->device);
   for (void* p : d->allocs) (void)hipFree(p);
+  if (d->own_stream && d->stream) (void)hipStreamDestroy(d->stream);
   delete d;
   return AZ_OK;
 }
@@ -490,6 +491,89 @@ extern "C" int az_dataset_create(az_memory* m, int32_t which, int32_t use_symmet
   *out = d;
   return AZ_OK;
 }
+// A data set made from the (W, X, A, P, V) tensors of convert_samples (learning.jl:17-51) that a host computed itself: one thread
+// per sample checks what the loss relies on and leaves the sample's terms of Wtot and of Hp = entropy_wmean(P, W) (learning.jl:63,111).
+// bad = the smallest (sample << 3 | clause) that failed, so the message does not depend on scheduling.
+enum { DS_NONFINITE = 1, DS_W = 2, DS_A01 = 3, DS_NOLEGAL = 4, DS_PNEG = 5, DS_PILLEGAL = 6 };
+__global__ void __launch_bounds__(256) k_ds_check(const float* __restrict__ W, const float* __restrict__ X, const float* __restrict__ A, const float* __restrict__ P,
+                                                  const float* __restrict__ V, long long n, int xs, int nA, unsigned long long* __restrict__ bad,
+                                                  double* __restrict__ t_w, double* __restrict__ t_hp) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float w = W[i];
+  bool finite = isfinite(w) && isfinite(V[i]);
+  for (int k = 0; k < xs; ++k) finite = finite && isfinite(X[(size_t)i * xs + k]);
+  bool a01 = true, pneg = false, pill = false;
+  int legal = 0;
+  double hp = 0.0;
+  for (int a = 0; a < nA; ++a) {
+    const float m = A[(size_t)i * nA + a], p = P[(size_t)i * nA + a];
+    finite = finite && isfinite(m) && isfinite(p);
+    a01 = a01 && (m == 0.0f || m == 1.0f);
+    legal += m == 1.0f;
+    pneg = pneg || p < 0.0f;
+    pill = pill || (p > 0.0f && m == 0.0f);
+    hp += (double)(p * az_logf(p + 1.1920929e-07f) * w);             // the term k_mem_convert leaves for a memory-made data set
+  }
+  const int code = !finite ? DS_NONFINITE : !(w > 0.0f) ? DS_W : !a01 ? DS_A01 : legal == 0 ? DS_NOLEGAL : pneg ? DS_PNEG : pill ? DS_PILLEGAL : 0;
+  if (code) atomicMin(bad, ((unsigned long long)i << 3) | (unsigned long long)code);
+  t_w[i] = (double)w; t_hp[i] = code ? 0.0 : hp;
+}
+extern "C" int az_dataset_create_from_tensors(int32_t game, int32_t device, int64_t n, const float* W, const float* X, const float* A,
+                                              const float* P, const float* V, az_dataset** out) {
+  if (!out) return fail(AZ_ERR_BAD_ARG, "NULL argument");
+  *out = nullptr;
+  GameInfo gi;
+  if (!game_info(game, &gi)) return fail(AZ_ERR_BAD_ARG, "unknown game id %d", game);
+  if (n < 1 || n > (1LL << 31) - 1) return fail(AZ_ERR_BAD_ARG, "n must be in 1..2^31-1");
+  if (!W || !X || !A || !P || !V) return fail(AZ_ERR_BAD_ARG, "NULL tensor");
+  int ndev = 0;
+  HIPCHK(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return fail(AZ_ERR_BAD_ARG, "device %d not available (%d visible)", device, ndev);
+  HIPCHK(hipSetDevice(device));
+  az_dataset* d = new (std::nothrow) az_dataset();
+  if (!d) return fail(AZ_ERR_HIP, "out of host memory");
+  d->game = game; d->device = device; d->gi = gi; d->stream = nullptr; d->own_stream = true; d->n = n; d->sum_n = n;
+  d->Wtot = 0.0; d->Wmean = 0.f; d->Hp = 0.f; d->d_samples = nullptr; d->d_envs = nullptr;
+  std::vector<void*> tmp;
+  int rc = [&]() -> int {
+    HIPCHK(hipStreamCreate(&d->stream));
+    hipStream_t st = d->stream;
+    const size_t xs = (size_t)gi.C * gi.P, nA = (size_t)gi.A, N = (size_t)n;
+    AZCHK(mem_alloc(&d->allocs, &d->d_W, N)); AZCHK(mem_alloc(&d->allocs, &d->d_V, N));
+    AZCHK(mem_alloc(&d->allocs, &d->d_A, N * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_P, N * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_X, N * xs));
+    HIPCHK(hipMemcpyAsync(d->d_W, W, sizeof(float) * N, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d->d_V, V, sizeof(float) * N, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d->d_A, A, sizeof(float) * N * nA, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d->d_P, P, sizeof(float) * N * nA, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d->d_X, X, sizeof(float) * N * xs, hipMemcpyHostToDevice, st));
+    unsigned long long* d_bad; double *tw, *thp;
+    AZCHK(mem_alloc(&tmp, &d_bad, 1)); AZCHK(mem_alloc(&tmp, &tw, N)); AZCHK(mem_alloc(&tmp, &thp, N));
+    HIPCHK(hipMemsetAsync(d_bad, 0xff, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_ds_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d->d_W, d->d_X, d->d_A, d->d_P, d->d_V, (long long)n, (int)xs, (int)nA, d_bad, tw, thp);
+    unsigned long long bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    if (bad != ~0ull) {
+      static const char* const what[] = {"", "a non-finite value", "W <= 0", "an entry of A outside {0, 1}", "no legal action (a row of A without a 1)",
+                                         "P < 0", "P > 0 where A == 0 (the loss takes the logarithm of the masked policy there)"};
+      return fail(AZ_ERR_BAD_ARG, "sample %lld: %s", (long long)(bad >> 3), what[bad & 7]);
+    }
+    DevReducer red;                                                  // the reducer of dataset_build: the same tiles and tree for the same n
+    AZCHK(red.init(n, st));
+    double sw, shp;
+    AZCHK(red.sum(tw, n, st, &sw)); AZCHK(red.sum(thp, n, st, &shp));
+    d->Wtot = sw;
+    d->Wmean = (float)(sw / (double)n);                              // mean(W), learning.jl:110
+    d->Hp = (float)(-shp / sw);                                      // entropy_wmean(P, W), learning.jl:111
+    return AZ_OK;
+  }();
+  for (void* p : tmp) (void)hipFree(p);
+  if (rc != AZ_OK) { az_dataset_destroy(d); return rc; }
+  *out = d;
+  return AZ_OK;
+}
 extern "C" int az_dataset_get_info(az_dataset* d, az_dataset_info* out) {
   if (!d || !out) return fail(AZ_ERR_BAD_ARG, "NULL argument");
   out->num_samples = d->n; out->sum_n = d->sum_n; out->Wtot = d->Wtot; out->Wmean = d->Wmean; out->Hp = d->Hp;
@@ -500,6 +584,7 @@ extern "C" int az_dataset_read(az_dataset* d, int64_t first, int64_t count, az_s
   if (!d) return fail(AZ_ERR_BAD_ARG, "dataset is NULL");
   HIPCHK(hipSetDevice(d->device));
   if (first < 0 || count < 0 || first + count > d->n) return fail(AZ_ERR_BAD_ARG, "range [%lld, %lld) outside the %lld samples", (long long)first, (long long)(first + count), (long long)d->n);
+  if (samples && !d->d_samples) return fail(AZ_ERR_BAD_ARG, "a data set made from tensors holds no az_sample records: read W, X, A, P, V");
   if (!count) return AZ_OK;
   const GameInfo& gi = d->gi;
   const size_t xs = (size_t)gi.C * gi.P;
@@ -528,15 +613,18 @@ static double reg_sum_trainable(const az_engine* e) {
   return s;
 }
 
-template <class Gm>
+// Reads the data set's tensors only (the network launch dispatches on the engine's geometry, net.hip), so it serves all four
+// network geometries: a memory-made data set hands the tower its device-twin states, one made from tensors its planes and masks.
 static int learning_status_run(az_engine* e, az_dataset* d, double l2, double cinv, double renorm, int64_t batch, az_learning_status_t* out) {
   const int64_t n = d->n;
+  const int nA = d->gi.A;
+  const size_t xs = (size_t)d->gi.C * d->gi.P;
   hipStream_t st = e->stream;
   std::vector<void*> tmp;
   auto cleanup = [&]() { for (void* p : tmp) (void)hipFree(p); };
   int rc = [&]() -> int {
     float *Ph, *Vh, *Pinv; double *tkl, *thn, *tmse, *tinv, *tw;
-    AZCHK(mem_alloc(&tmp, &Ph, (size_t)n * Gm::A)); AZCHK(mem_alloc(&tmp, &Vh, (size_t)n)); AZCHK(mem_alloc(&tmp, &Pinv, (size_t)n));
+    AZCHK(mem_alloc(&tmp, &Ph, (size_t)n * nA)); AZCHK(mem_alloc(&tmp, &Vh, (size_t)n)); AZCHK(mem_alloc(&tmp, &Pinv, (size_t)n));
     AZCHK(mem_alloc(&tmp, &tkl, (size_t)n)); AZCHK(mem_alloc(&tmp, &thn, (size_t)n)); AZCHK(mem_alloc(&tmp, &tmse, (size_t)n)); AZCHK(mem_alloc(&tmp, &tinv, (size_t)n));
     AZCHK(mem_alloc(&tmp, &tw, (size_t)n));
     HIPCHK(hipStreamSynchronize(d->stream));
@@ -549,10 +637,11 @@ static int learning_status_run(az_engine* e, az_dataset* d, double l2, double ci
     HIPCHK(hipMemcpyAsync(d_counts, counts.data(), sizeof(int) * (size_t)nchunks, hipMemcpyHostToDevice, st));
     for (int64_t c = 0; c < nchunks; ++c) {
       const int64_t off = c * e->nn_cap;
-      AZCHK(net_launch(e, st, false, e->d_hfeat, d->d_envs + off, e->d_iota, d_counts + c, counts[c], nullptr, nullptr, Ph + (size_t)off * Gm::A, Vh + off, Pinv + off, Gm::A));
+      if (d->d_envs) AZCHK(net_launch(e, st, false, e->d_hfeat, d->d_envs + off, e->d_iota, d_counts + c, counts[c], nullptr, nullptr, Ph + (size_t)off * nA, Vh + off, Pinv + off, nA));
+      else AZCHK(net_launch(e, st, true, e->d_hfeat, nullptr, nullptr, nullptr, counts[c], d->d_X + (size_t)off * xs, d->d_A + (size_t)off * nA, Ph + (size_t)off * nA, Vh + off, Pinv + off, nA));
     }
     HIPCHK(hipStreamSynchronize(st));                              // `counts` must outlive the copy
-    hipLaunchKernelGGL(k_loss_terms, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d->d_W, d->d_P, d->d_V, Ph, Vh, Pinv, (long long)n, Gm::A, (float)renorm, tkl, thn, tmse, tinv);
+    hipLaunchKernelGGL(k_loss_terms, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d->d_W, d->d_P, d->d_V, Ph, Vh, Pinv, (long long)n, nA, (float)renorm, tkl, thn, tmse, tinv);
     hipLaunchKernelGGL(k_f32_to_f64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d->d_W, (long long)n, tw);
     if (batch > n) batch = n;
     const int64_t nb = (n + batch - 1) / batch;                    // DataLoader(partial = true), learning.jl:171-176
@@ -595,6 +684,5 @@ extern "C" int az_learning_status(az_engine* e, az_dataset* d, double l2_regular
   if (loss_computation_batch_size < 1) return fail(AZ_ERR_BAD_ARG, "loss_computation_batch_size must be >= 1");
   if (!(rewards_renormalization > 0.0)) return fail(AZ_ERR_BAD_ARG, "rewards_renormalization must be > 0");
   AZCHK(sync_all(e));
-  DISPATCH_GAME(e->cfg.game, AZCHK(learning_status_run<Gm>(e, d, l2_regularization, nonvalidity_penalty, rewards_renormalization, loss_computation_batch_size, out)));
-  return AZ_OK;
+  return learning_status_run(e, d, l2_regularization, nonvalidity_penalty, rewards_renormalization, loss_computation_batch_size, out);
 }

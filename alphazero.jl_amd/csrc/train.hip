@@ -287,6 +287,48 @@ __global__ void k_tr_loss(const float* __restrict__ logits, const float* __restr
   dt[i] = 2.0f * d / rho * (1.0f - vh * vh) * w * gscale;
   t_w[i] = (double)w; t_kl[i] = kl; t_mse[i] = (double)(d * d * w); t_inv[i] = (double)((1.0f - S) * w);
 }
+// The same loss for an action set wider than AZ_MAX_ACTIONS (9x9 boards: 82): the same operations in the same order per sample, but
+// the softmax p lives in the sample's row of dlogits (which the last loop overwrites with the gradient) and u, gq, dp are computed
+// again where they are used instead of being kept in per-thread arrays -- 4 x 82 floats per thread would go to scratch memory.
+__global__ void k_tr_loss_wide(const float* __restrict__ logits, const float* __restrict__ tpre, const float* __restrict__ Am,
+                               const float* __restrict__ P, const float* __restrict__ V, const float* __restrict__ W, int B, int A,
+                               float cinv, float rho, float gscale, float* __restrict__ dlogits, float* __restrict__ dt,
+                               double* __restrict__ t_w, double* __restrict__ t_kl, double* __restrict__ t_mse, double* __restrict__ t_inv) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  const float eps = 1.1920929e-07f;
+  const float* lg = logits + (size_t)i * A;
+  const float* am = Am + (size_t)i * A;
+  const float* pt = P + (size_t)i * A;
+  float* p = dlogits + (size_t)i * A;
+  float mx = lg[0];
+  for (int a = 1; a < A; ++a) mx = lg[a] > mx ? lg[a] : mx;
+  float se = 0.0f;
+  for (int a = 0; a < A; ++a) { const float v = az_expf(lg[a] - mx); p[a] = v; se += v; }
+  float S = 0.0f;
+  for (int a = 0; a < A; ++a) { const float v = p[a] / se; p[a] = v; S += v * am[a]; }
+  const float w = W[i];
+  const float den = S + eps;
+  double kl = 0.0;
+  float gu_sum = 0.0f;
+  for (int a = 0; a < A; ++a) {
+    const float u = p[a] * am[a], q = u / den, Pa = pt[a];
+    kl += (double)(Pa * az_logf(q + eps) * w);
+    gu_sum += (-Pa / (q + eps)) * u;
+  }
+  gu_sum = gu_sum / (den * den);
+  auto dp_of = [&](int a) {
+    const float u = p[a] * am[a], q = u / den, gq = -pt[a] / (q + eps);
+    return am[a] * (gq / den - gu_sum - cinv) * w * gscale;
+  };
+  float dot = 0.0f;
+  for (int a = 0; a < A; ++a) dot += p[a] * dp_of(a);
+  for (int a = 0; a < A; ++a) p[a] = p[a] * (dp_of(a) - dot);
+  const float vh = az_tanhf(tpre[i]);
+  const float d = vh / rho - V[i] / rho;
+  dt[i] = 2.0f * d / rho * (1.0f - vh * vh) * w * gscale;
+  t_w[i] = (double)w; t_kl[i] = kl; t_mse[i] = (double)(d * d * w); t_inv[i] = (double)((1.0f - S) * w);
+}
 // the five sums of a step in one launch: out = (sum w, sum kl, sum mse, sum inv, sum of squares of the trainables)
 __global__ void __launch_bounds__(256) k_tr_step_sums(const double* __restrict__ tw, const double* __restrict__ tkl, const double* __restrict__ tmse,
                                                       const double* __restrict__ tinv, int B, const double* __restrict__ ssq_part, int nssq,
@@ -525,7 +567,7 @@ static int trainer_build(az_trainer* t) {
   AZCHK(tr_alloc(t, &t->dact, (size_t)R * F)); AZCHK(tr_alloc(t, &t->dact2, (size_t)R * F)); AZCHK(tr_alloc(t, &t->dact3, (size_t)R * F)); AZCHK(tr_alloc(t, &t->dcol, (size_t)R * F));
   const int nchunks = (int)((R + TR_CHUNK - 1) / TR_CHUNK);
   AZCHK(tr_alloc(t, &t->part, (size_t)std::max(nchunks, B + 1) * 2 * std::max(F, 64)));   // chunks of k_tr_colsum or workgroups of k_conv16_layer
-  AZCHK(tr_alloc(t, &t->sums, (size_t)2 * std::max(F, 64))); AZCHK(tr_alloc(t, &t->bn_mf, (size_t)2 * std::max(F, 64)));
+  AZCHK(tr_alloc(t, &t->sums, (size_t)2 * std::max({F, 64, A}))); AZCHK(tr_alloc(t, &t->bn_mf, (size_t)2 * std::max(F, 64)));   // sums: also the policy bias gradient, A columns (82 on a 9x9 board)
   AZCHK(tr_alloc(t, &t->fin_counter, 4, true));                       // tr_finish: workgroups done (every launch leaves it at zero)
   AZCHK(tr_alloc(t, &t->terms, (size_t)4 * B)); AZCHK(tr_alloc(t, &t->bsums, 8 + 1024));
   // k_wgrad16: one round of workgroups over the chip
@@ -553,7 +595,7 @@ template <class Gm, int F, bool STATS, int NT> static int tr_conv16_f(az_trainer
 // (sum, sum of squares) of the output in t->part, *nparts workgroup partials
 static int tr_conv16(az_trainer* t, const float* in, const float* frag, float* out, bool stats = false, int* nparts = nullptr, const float* addend = nullptr,
                      const BnIn& bn = BnIn{}, const TrFinal& fin = TrFinal{}) {
-  DISPATCH_GAME(t->game, {
+  DISPATCH_GEOMETRY(t->game, {
     using T = T16<Gm, 64, 11>;
     using T6 = T16<Gm, 64, 6>;
     // (r4) 64 filters and a batch that gives the 11-tile form at most one workgroup per CU: the 6-tile form (half the boards per
@@ -570,7 +612,11 @@ static int tr_conv16(az_trainer* t, const float* in, const float* frag, float* o
 template <class Gm, int F> static int tr_wgrad16_f(az_trainer* t, const float* a, const float* dg, float* out, hipStream_t st) {
   // 128 filters: the 4-wavefront form (half the input channels per workgroup, one board per LDS chunk, 44 KB): the same sums in
   // the same order as the 8-wavefront form, and a workgroup of it fits on a CU beside one of k_conv16_layer
-  constexpr int CS = (F == 128 && Gm::P <= 48) ? 2 : 1, RPC = CS == 2 ? 48 : 128;
+  // A board of more than 64 positions (9x9: 81) is a chunk by itself: RPC = its rows rounded up to whole tiles (96), not the 128 rows of
+  // the three-board chunk, which would carry 47 padding rows through HBM loads and LDS for every board; at 128 filters with the input
+  // channels split in two as well (86 KB of LDS; the 8-wavefront form would take 110 KB at 96 rows and 146 KB at 128).  DESIGN.md 4e.
+  constexpr bool BIG = Gm::P > 64;
+  constexpr int CS = (F == 128 && (Gm::P <= 48 || BIG)) ? 2 : 1, RPC = BIG ? (Gm::P + 15) / 16 * 16 : CS == 2 ? 48 : 128;
   using G = WG16<F, CS, RPC>;
   static bool attr_done = false;
   if (!attr_done) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad16<Gm, F, 0, CS, RPC>), hipFuncAttributeMaxDynamicSharedMemorySize, G::BYTES)); attr_done = true; }
@@ -581,7 +627,7 @@ template <class Gm, int F> static int tr_wgrad16_f(az_trainer* t, const float* a
 }
 // weight gradient of a 3x3 F -> F convolution on the MFMA kernel: out = [9][F][F] in the Wm layout
 static int tr_wgrad16(az_trainer* t, const float* a, const float* dg, float* out, hipStream_t st) {
-  DISPATCH_GAME(t->game, { if (t->F == 128) AZCHK((tr_wgrad16_f<Gm, 128>(t, a, dg, out, st))); else AZCHK((tr_wgrad16_f<Gm, 64>(t, a, dg, out, st))); });
+  DISPATCH_GEOMETRY(t->game, { if (t->F == 128) AZCHK((tr_wgrad16_f<Gm, 128>(t, a, dg, out, st))); else AZCHK((tr_wgrad16_f<Gm, 64>(t, a, dg, out, st))); });
   return AZ_OK;
 }
 
@@ -669,8 +715,12 @@ static int tr_forward_backward(az_trainer* t, const int* idx_host, double* d_sum
   // ---------------- loss ----------------
   // mean(W)/Wmean / sum(W) = 1 / (B Wmean): the gradient scale needs no reduction first (learning.jl:88)
   double *tw = t->terms, *tkl = t->terms + B, *tmse = t->terms + 2 * (size_t)B, *tinv = t->terms + 3 * (size_t)B;
-  hipLaunchKernelGGL(k_tr_loss, dim3(tr_grid(B)), dim3(256), 0, st, t->logits, t->tpre, t->bA, t->bP, t->bV, t->bW, B, A,
-                     (float)t->cfg.nonvalidity_penalty, (float)t->cfg.rewards_renormalization, 1.0f / ((float)B * d->Wmean), t->dlogits, t->dt, tw, tkl, tmse, tinv);
+  if (A <= AZ_MAX_ACTIONS)
+    hipLaunchKernelGGL(k_tr_loss, dim3(tr_grid(B)), dim3(256), 0, st, t->logits, t->tpre, t->bA, t->bP, t->bV, t->bW, B, A,
+                       (float)t->cfg.nonvalidity_penalty, (float)t->cfg.rewards_renormalization, 1.0f / ((float)B * d->Wmean), t->dlogits, t->dt, tw, tkl, tmse, tinv);
+  else                                                              // 64 threads per workgroup: the rows of a wavefront's samples are 4 A bytes apart, so more CUs share the strided reads
+    hipLaunchKernelGGL(k_tr_loss_wide, dim3((B + 63) / 64), dim3(64), 0, st, t->logits, t->tpre, t->bA, t->bP, t->bV, t->bW, B, A,
+                       (float)t->cfg.nonvalidity_penalty, (float)t->cfg.rewards_renormalization, 1.0f / ((float)B * d->Wmean), t->dlogits, t->dt, tw, tkl, tmse, tinv);
   hipLaunchKernelGGL(k_tr_sumsq, dim3(1024), dim3(256), 0, st, blob, t->trainable, (long long)t->nparams, t->bsums + 8);
   hipLaunchKernelGGL(k_tr_step_sums, dim3(1), dim3(256), 0, st, tw, tkl, tmse, tinv, B, t->bsums + 8, 1024, d_sums);
   // ---------------- backward: dense heads ----------------
@@ -786,7 +836,6 @@ extern "C" int az_trainer_create(az_engine* e, az_dataset* d, const az_train_cfg
   if (cfg->struct_size != (int32_t)sizeof(az_train_cfg)) return fail(AZ_ERR_BAD_ARG, "az_train_cfg size mismatch: call az_train_cfg_init");
   if (e->cfg.oracle != AZ_ORACLE_RESNET || !e->net_loaded) return fail(AZ_ERR_STATE, "az_net_set_params has not been called");
   if (d->game != e->cfg.game || d->device != e->device) return fail(AZ_ERR_BAD_ARG, "data set and engine differ in game or device");
-  if (e->cfg.game == AZ_GAME_GO9_PLANES) return fail(AZ_ERR_BAD_ARG, "game id %d is a network-only tensor geometry: no device trainer", e->cfg.game);
   if (cfg->optimiser != AZ_OPT_ADAM && cfg->optimiser != AZ_OPT_CYCLIC_NESTEROV) return fail(AZ_ERR_BAD_ARG, "unknown optimiser %d", cfg->optimiser);
   const int64_t B = std::min<int64_t>(cfg->batch_size, d->n);     // batchsize = min(params.batch_size, length(W)), learning.jl:113
   if (cfg->batch_size < 2 || B < 2) return fail(AZ_ERR_BAD_ARG, "batch_size and the data set must have at least 2 samples (batch statistics)");

@@ -17,6 +17,13 @@
 //   g++ -O2 -std=c++17 -Iinclude examples/host_stepped_go9.cpp -Lalphazero.jl_amd/csrc -lazhip -lpthread ...
 //       -Wl,-rpath,$PWD/alphazero.jl_amd/csrc -o examples/host_stepped_go9      (or: make -C examples)
 //   examples/host_stepped_go9 [--workers 512] [--sims 1600] [--seconds 8] [--threads 0=all usable] [--arena-gb 0=auto] [--fp32] [--blocks 10] [--filters 128]
+//                             [--train-steps 0]
+//
+// --train-steps N closes the iteration on the GPU: the positions of the games that FINISHED during play become the (W, X, A, P, V)
+// tensors of convert_samples (src/learning.jl:17-51: constant weights, the visit frequencies of the move's search, the game's
+// outcome from the mover's side), az_dataset_create_from_tensors takes them and az_trainer_batch_updates runs N Adam steps on them
+// (fp32, the engine's architecture and parameters); the losses are printed as a second JSON line.  Play goes on past --seconds
+// (at most ten times as long) until one game has finished.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -230,6 +237,9 @@ struct Worker {
   std::vector<PathEntry> path;
   std::vector<double> eta;
   std::mt19937_64 rng;
+  // --train-steps: the positions of the game in progress (planes, mask, visit frequencies, mover) and the samples of finished games
+  std::vector<float> gX, gA, gP; std::vector<int8_t> gmover;
+  std::vector<float> sX, sA, sP, sV;
   int sims_in_move = 0, leaf_kind = 0;      // 0 none, 1 new, 2 terminal
   int batch_index = -1;
   long long sims = 0, traversed = 0, games = 0, moves = 0;
@@ -244,7 +254,7 @@ struct Worker {
   }
 };
 
-struct Opt { bool dry = false; int workers = 512, sims = 1600, threads = 0, blocks = 10, filters = 128, bf16 = 1; double seconds = 8.0, cpuct = 2.0, eps = 0.25, alpha = 0.03, arena_gb = 0.0; };
+struct Opt { bool dry = false; int workers = 512, sims = 1600, threads = 0, blocks = 10, filters = 128, bf16 = 1, train_steps = 0; double seconds = 8.0, cpuct = 2.0, eps = 0.25, alpha = 0.03, arena_gb = 0.0; };
 
 // select (mcts.jl:199-217) until an unseen or a terminal state
 void descend(Worker& w, const Opt& o) {
@@ -312,10 +322,23 @@ void make_move(Worker& w, const Opt& o) {
         for (; i + 1 < n; ++i) { c += Nv[i]; if (c > x) break; }
         a = nd->acts()[i];
       } else a = nd->acts()[std::max_element(Nv, Nv + n) - Nv];
+      if (o.train_steps > 0) {                                       // a searched position: one training sample once the game is over
+        const size_t k = w.gmover.size();
+        w.gX.resize((k + 1) * C * P); w.gA.resize((k + 1) * A); w.gP.resize((k + 1) * A, 0.f);
+        w.root.planes(&w.gX[k * C * P], &w.gA[k * A]);
+        for (int i = 0; i < n; ++i) w.gP[k * A + nd->acts()[i]] = (float)((double)Nv[i] / (double)tot);
+        w.gmover.push_back(w.root.to_play);
+      }
     }
   }
   w.root.play(a);
   w.moves++;
+  if (w.root.over() && o.train_steps > 0) {
+    const double wr = w.root.white_reward();                         // from the first player's side; V is the mover's
+    w.sX.insert(w.sX.end(), w.gX.begin(), w.gX.end()); w.sA.insert(w.sA.end(), w.gA.begin(), w.gA.end()); w.sP.insert(w.sP.end(), w.gP.begin(), w.gP.end());
+    for (int8_t m : w.gmover) w.sV.push_back((float)(m == 1 ? wr : -wr));
+    w.gX.clear(); w.gA.clear(); w.gP.clear(); w.gmover.clear();
+  }
   if (w.root.over()) { w.root.reset(); w.clear_tree(); w.games++; }     // reset_every = 1
   w.new_noise(o.alpha);
   w.sims_in_move = 0;
@@ -409,6 +432,7 @@ int main(int argc, char** argv) {
     else if (is("--seconds")) o.seconds = atof(argv[++i]); else if (is("--threads")) o.threads = atoi(argv[++i]);
     else if (is("--arena-gb")) o.arena_gb = atof(argv[++i]);
     else if (is("--blocks")) o.blocks = atoi(argv[++i]); else if (is("--filters")) o.filters = atoi(argv[++i]);
+    else if (is("--train-steps")) o.train_steps = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--fp32")) o.bf16 = 0;
     else if (!strcmp(argv[i], "--dry")) o.dry = true;            // no GPU: MCTS.RandomOracle in place of the network (host ceiling, CPU tests)
     else { fprintf(stderr, "unknown option %s\n", argv[i]); return 1; }
@@ -538,7 +562,11 @@ int main(int argc, char** argv) {
       continue;
     }
     t_tree += host; t_net += wait;
-    if (t4 - t_meas0 >= o.seconds) break;
+    if (t4 - t_meas0 >= o.seconds) {
+      bool enough = o.train_steps <= 0 || t4 - t_meas0 >= 10.0 * o.seconds;
+      for (size_t i = 0; i < ws.size() && !enough; ++i) enough = ws[i].sV.size() >= 2;
+      if (enough) break;
+    }
   }
   const double wall = now() - t_meas0;
   long long sims = -sims0, trav = -trav0, games = 0, moves = 0;
@@ -554,6 +582,31 @@ int main(int argc, char** argv) {
          o.threads, W, o.sims, o.blocks, o.filters, o.bf16 ? "bf16" : "fp32", sims / wall, wall, t_tree / wall, t_net / wall, t_call / wall,
          launches ? (double)boards / launches : 0.0, launches, t_call > 0 ? boards / t_call : 0.0, sims ? (double)trav / sims : 0.0,
          games, moves, nodes, kernel, o.threads);
+  int rc = 0;
+  if (o.train_steps > 0) {
+    std::vector<float> tW, tX, tA, tP, tV;
+    for (auto& w : ws) { tX.insert(tX.end(), w.sX.begin(), w.sX.end()); tA.insert(tA.end(), w.sA.begin(), w.sA.end()); tP.insert(tP.end(), w.sP.begin(), w.sP.end()); tV.insert(tV.end(), w.sV.begin(), w.sV.end()); }
+    const int64_t ns = (int64_t)tV.size();
+    tW.assign((size_t)ns, 1.f);                                      // CONSTANT_WEIGHT
+    if (o.dry) fprintf(stderr, "--train-steps needs the GPU (--dry has no network to train)\n"), rc = 1;
+    else if (ns < 2) fprintf(stderr, "--train-steps: %lld samples -- no game finished; play longer (--seconds) or with fewer --sims\n", (long long)ns), rc = 1;
+    else {
+      az_dataset* ds = nullptr; az_trainer* tr = nullptr; az_train_cfg tc;
+      std::vector<float> losses((size_t)o.train_steps);
+      int ts = az_dataset_create_from_tensors(AZ_GAME_GO9_PLANES, cfg.device, ns, tW.data(), tX.data(), tA.data(), tP.data(), tV.data(), &ds);
+      if (ts == AZ_OK) ts = az_train_cfg_init(&tc);
+      if (ts == AZ_OK) { tc.optimiser = AZ_OPT_ADAM; tc.lr = 2e-3f; tc.batch_size = 1024; ts = az_trainer_create(e, ds, &tc, &tr); }
+      if (ts == AZ_OK) ts = az_trainer_batch_updates(tr, o.train_steps, losses.data());
+      if (ts != AZ_OK) { fprintf(stderr, "training: status %d: %s\n", ts, az_last_error()); rc = 1; }
+      else {
+        printf("{\"train_steps\": %d, \"samples\": %lld, \"batch_size\": %lld, \"optimiser\": \"Adam(2e-3)\", \"losses\": [", o.train_steps, (long long)ns, (long long)std::min<int64_t>(1024, ns));
+        for (int i = 0; i < o.train_steps; ++i) printf("%s%.6g", i ? ", " : "", (double)losses[(size_t)i]);
+        printf("]}\n");
+      }
+      if (tr) az_trainer_destroy(tr);
+      if (ds) az_dataset_destroy(ds);
+    }
+  }
   if (e) az_engine_destroy(e);
-  return 0;
+  return rc;
 }

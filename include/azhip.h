@@ -72,7 +72,9 @@ typedef enum {
   AZ_GAME_CONNECT_FOUR = 0, AZ_GAME_TICTACTOE = 1, AZ_GAME_MANCALA = 2,
   /* Network-only tensor geometry, no device twin: GI.state_dim = (9, 9, 4), 82 actions -- OpenSpiel 9x9 Go through
    * src/openspiel.jl (BASELINE configs[4]).  Rules and tree stay on the host; the engine serves az_net_set_params /
-   * az_net_forward (Network.forward_normalized) for it and rejects every search, game and key-based entry point. */
+   * az_net_forward (Network.forward_normalized) for it, trains it on a data set made from tensors
+   * (az_dataset_create_from_tensors, az_trainer_*, az_learning_status) and rejects every search, game, key-based and
+   * replay-memory entry point. */
   AZ_GAME_GO9_PLANES = 3
 } az_game_id;
 
@@ -493,6 +495,15 @@ int az_memory_empty(az_memory* m);                                              
  * convert_samples (src/learning.jl:17-51) with the weighing policy.  Everything stays on the device. */
 int az_dataset_create(az_memory* m, int32_t which, int32_t use_symmetries, int32_t use_position_averaging,
                       int32_t weighing_policy, az_dataset** out);
+/* The data of a Trainer from tensors the caller converted itself (convert_samples, src/learning.jl:17-51): a host that steps its own
+ * game -- any GameInterface game of a supported geometry, AZ_GAME_GO9_PLANES included, which has no replay memory here -- or one that
+ * labels positions by other means.  Host arrays, sample index first: W [n], X [n][C][H][W] (the layout of az_net_forward), A [n][nA],
+ * P [n][nA], V [n] (the layouts az_dataset_read writes).  AZ_ERR_BAD_ARG with the first offending sample in az_last_error() for n < 1,
+ * a NULL pointer, a non-finite value, W <= 0, an entry of A outside {0, 1}, a row of A without a legal action, P < 0, or P > 0 where
+ * A == 0 (the loss takes the logarithm of the masked network policy there).  Wtot, Wmean and Hp = entropy_wmean(P, W)
+ * (src/learning.jl:63,111) are computed on the device; num_samples = sum_n = n.  No az_sample records stand behind such a data set. */
+int az_dataset_create_from_tensors(int32_t game, int32_t device, int64_t n, const float* W, const float* X, const float* A,
+                                   const float* P, const float* V, az_dataset** out);
 int az_dataset_destroy(az_dataset* d);
 typedef struct {
   int64_t num_samples;   /* length(samples) after symmetries / merging (= num_boards when merged) */
@@ -502,7 +513,8 @@ typedef struct {
 } az_dataset_info;
 int az_dataset_get_info(az_dataset* d, az_dataset_info* out);
 /* samples / tensors [first, first+count) to host buffers (any pointer may be NULL): W [n], X [n][C][H][W]
- * (= Julia WHCN memory), A [n][nA], P [n][nA], V [n] */
+ * (= Julia WHCN memory), A [n][nA], P [n][nA], V [n].  A data set made from tensors has no samples: AZ_ERR_BAD_ARG if `samples` is
+ * not NULL. */
 int az_dataset_read(az_dataset* d, int64_t first, int64_t count, az_sample* samples, float* W, float* X, float* A,
                     float* P, float* V);
 /* learning_status(tr) (src/learning.jl:158-181): `losses` (:67-90) per batch of loss_computation_batch_size samples
@@ -526,7 +538,8 @@ typedef struct {
 } az_train_cfg;
 int az_train_cfg_init(az_train_cfg* cfg);
 /* Trainer(gspec, network, samples, params): the engine supplies the architecture and the initial parameters, the
- * data set (az_dataset_create) the converted samples, Wmean and Hp.  The engine's own network is not modified:
+ * data set (az_dataset_create or az_dataset_create_from_tensors) the converted samples, Wmean and Hp.  All four network
+ * geometries train, AZ_GAME_GO9_PLANES through a data set made from tensors.  The engine's own network is not modified:
  * fetch the result with az_trainer_get_params and install it with az_net_set_params.  The engine and the data set
  * must outlive the trainer. */
 int az_trainer_create(az_engine* e, az_dataset* d, const az_train_cfg* cfg, az_trainer** out);

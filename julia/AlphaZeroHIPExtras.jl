@@ -109,6 +109,34 @@ function device_batch_updates!(nn::HipResNet, m::DeviceMemory, lp, n; use_symmet
   return losses
 end
 
+"""
+    device_batch_updates!(nn::HipResNet, data::NamedTuple{(:W, :X, :A, :P, :V)}, lp::LearningParams, n; seed) -> losses
+
+The same on samples the HOST converted: `data = convert_samples(gspec, lp.samples_weighing_policy, samples)` (src/learning.jl:17-51;
+merge_by_state / augment_with_symmetries applied before, as `Trainer` does).  For any `GameInterface` game whose tensor geometry the
+library instantiates -- 9x9 Go through src/openspiel.jl has no device replay memory, so this is how its network learns.  Julia's
+column-major W (1 x n), X (w x h x c x n), A and P (nA x n), V (1 x n) are the sample-index-first arrays the entry point takes.
+"""
+function device_batch_updates!(nn::HipResNet, data::NamedTuple{(:W, :X, :A, :P, :V)}, lp, n; seed=1, device=0)
+  W, X, A, P, V = (Array{Float32}(x) for x in data)
+  ds = Ref{Ptr{Cvoid}}(C_NULL); tr = Ref{Ptr{Cvoid}}(C_NULL)
+  check(ccall((:az_dataset_create_from_tensors, LIB), Cint,
+    (Int32, Int32, Int64, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ref{Ptr{Cvoid}}),
+    game_id(nn.gspec), device, length(W), W, X, A, P, V, ds))
+  losses = Vector{Float32}(undef, n)
+  try
+    check(ccall((:az_trainer_create, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{TrainCfg}, Ref{Ptr{Cvoid}}),
+      engine!(nn).h, ds[], train_cfg(lp, nn.hyper; seed=seed), tr))
+    check(ccall((:az_trainer_batch_updates, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float32}), tr[], n, losses))
+    check(ccall((:az_trainer_get_params, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int64), tr[], nn.blob, length(nn.blob)))
+    check(ccall((:az_net_set_params, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int64), engine!(nn).h, nn.blob, length(nn.blob)))
+  finally
+    tr[] != C_NULL && ccall((:az_trainer_destroy, LIB), Cint, (Ptr{Cvoid},), tr[])
+    ccall((:az_dataset_destroy, LIB), Cint, (Ptr{Cvoid},), ds[])
+  end
+  return losses
+end
+
 
 """
     device_self_play_step!(gspec, bestnn::HipResNet, params::SelfPlayParams, mem::DeviceMemory, comm; seed) -> Report.SelfPlay
