@@ -165,7 +165,7 @@ __global__ void __launch_bounds__(14 * 64) k_mem_merge_long(const az_sample* __r
 // convert_samples (learning.jl:17-51) + per-sample entropy term of Hp (learning.jl:65,111)
 template <class Gm>
 __global__ void k_mem_convert(const az_sample* __restrict__ s, long long n, int policy, GEnv* envs, float* W, float* A, float* P, float* V,
-                              double* t_w, double* t_hp, double* t_n) {
+                              double* t_w, double* t_hp, long long* t_n) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const az_sample e = s[i];
@@ -182,7 +182,7 @@ __global__ void k_mem_convert(const az_sample* __restrict__ s, long long n, int 
     hp += (double)(p * az_logf(p + 1.1920929e-07f) * w);
   }
   V[i] = (float)e.z;
-  t_w[i] = (double)w; t_hp[i] = hp; t_n[i] = (double)e.n;
+  t_w[i] = (double)w; t_hp[i] = hp; t_n[i] = (long long)e.n;
 }
 template <class Gm>
 __global__ void k_mem_planes(const GEnv* __restrict__ envs, long long n, float* __restrict__ X) {
@@ -252,6 +252,13 @@ struct DevReducer {                     // deterministic sum of doubles (prims.h
     double* d_res = nullptr;
     HIPCHK(prims::sum_doubles(d_in, n, tmp, &d_res, st));
     HIPCHK(hipMemcpyAsync(out, d_res, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return AZ_OK;
+  }
+  int sum(const long long* d_in, long long n, hipStream_t st, long long* out) {       // sum(e.n) is an Int: exact, whatever its size
+    long long* d_res = nullptr;
+    HIPCHK(prims::sum_values<long long>(d_in, n, (long long*)tmp, &d_res, st));
+    HIPCHK(hipMemcpyAsync(out, d_res, sizeof(long long), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return AZ_OK;
   }
@@ -441,14 +448,14 @@ static int dataset_build(az_memory* m, az_dataset* d, int which, bool use_sym, b
     AZCHK(mem_alloc(&d->allocs, &d->d_X, (size_t)n2 * Gm::C * Gm::P));
     d->sum_n = 0; d->Wtot = 0.0; d->Wmean = 0.f; d->Hp = 0.f;
     if (n2) {
-      double *tw, *thp, *tn;
+      double *tw, *thp; long long* tn;
       AZCHK(mem_alloc(&tmp, &tw, (size_t)n2)); AZCHK(mem_alloc(&tmp, &thp, (size_t)n2)); AZCHK(mem_alloc(&tmp, &tn, (size_t)n2));
       hipLaunchKernelGGL((k_mem_convert<Gm>), dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, d->d_samples, (long long)n2, policy, d->d_envs, d->d_W, d->d_A, d->d_P, d->d_V, tw, thp, tn);
       const long long ne = (long long)n2 * Gm::C * Gm::P;
       hipLaunchKernelGGL((k_mem_planes<Gm>), dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, d->d_envs, (long long)n2, d->d_X);
       DevReducer red;
       AZCHK(red.init(n2, st));
-      double sw, shp, sn;
+      double sw, shp; long long sn;
       AZCHK(red.sum(tw, n2, st, &sw)); AZCHK(red.sum(thp, n2, st, &shp)); AZCHK(red.sum(tn, n2, st, &sn));
       d->Wtot = sw; d->sum_n = (int64_t)sn;
       d->Wmean = (float)(sw / (double)n2);                         // mean(W), learning.jl:110

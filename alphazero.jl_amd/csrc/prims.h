@@ -1,6 +1,6 @@
 // prims.h -- the three device-wide primitives memory.hip needs (merge_by_state, src/memory.jl:89-114, and the data-set sums of
 // src/learning.jl:110-111), hand-written for gfx950: a stable LSD radix sort of (u64 key, u32 value) pairs, an inclusive
-// scan of ints and a deterministic sum of doubles.  Round 2 took them from hipCUB, the last third-party device code in the
+// scan of ints and a deterministic sum of doubles (the same tiles sum 64-bit integers exactly).  Round 2 took them from hipCUB, the last third-party device code in the
 // library.  Off the hot path (a data set is built once per learning step), so the design goal is small and obviously
 // stable / deterministic rather than fastest: 8-bit digits, one workgroup per tile of 2048 pairs, and a per-tile local
 // split so that equal digits keep their order.
@@ -168,11 +168,12 @@ inline hipError_t sort_pairs(unsigned long long* keys_in, unsigned long long* ke
   return hipGetLastError();
 }
 
-// ---- deterministic sum of n doubles: fixed tiles of 2048 summed by a fixed tree, tile sums summed by one workgroup in order ------------
-static __global__ void __launch_bounds__(RS_THREADS) k_sum_tiles(const double* __restrict__ in, long long n, double* __restrict__ out) {
-  __shared__ double s[RS_THREADS];
+// ---- deterministic sum of n doubles (or 64-bit integers): fixed tiles of 2048 summed by a fixed tree, tile sums summed by one workgroup in order ----
+template <class T>
+static __global__ void __launch_bounds__(RS_THREADS) k_sum_tiles(const T* __restrict__ in, long long n, T* __restrict__ out) {
+  __shared__ T s[RS_THREADS];
   const long long base = (long long)blockIdx.x * RS_TILE;
-  double a = 0.0;
+  T a = T(0);
 #pragma unroll
   for (int i = 0; i < RS_ITEMS; ++i) {
     const long long p = base + (long long)i * RS_THREADS + threadIdx.x;
@@ -186,21 +187,26 @@ static __global__ void __launch_bounds__(RS_THREADS) k_sum_tiles(const double* _
   }
   if (threadIdx.x == 0) out[blockIdx.x] = s[0];
 }
-inline size_t sum_tmp_doubles(long long n) {
+inline size_t sum_tmp_doubles(long long n) {                      // 8-byte words of scratch, for either element type
   size_t tot = 0;
   for (long long m = (n + RS_TILE - 1) / RS_TILE; ; m = (m + RS_TILE - 1) / RS_TILE) { tot += (size_t)m; if (m <= 1) break; }
   return tot + 1;
 }
 // result in tmp[last level]; returns the device pointer of the scalar through *d_result
-inline hipError_t sum_doubles(const double* in, long long n, double* tmp, double** d_result, hipStream_t st) {
-  const double* src = in;
-  double* dst = tmp;
+template <class T>
+inline hipError_t sum_values(const T* in, long long n, T* tmp, T** d_result, hipStream_t st) {
+  static_assert(sizeof(T) == 8, "the scratch is sized in 8-byte words");
+  const T* src = in;
+  T* dst = tmp;
   long long m = n;
   for (;;) {
     const long long tiles = (m + RS_TILE - 1) / RS_TILE < 1 ? 1 : (m + RS_TILE - 1) / RS_TILE;
-    hipLaunchKernelGGL(k_sum_tiles, dim3((unsigned)tiles), dim3(RS_THREADS), 0, st, src, m, dst);
+    hipLaunchKernelGGL(k_sum_tiles<T>, dim3((unsigned)tiles), dim3(RS_THREADS), 0, st, src, m, dst);
     if (tiles == 1) { *d_result = dst; return hipGetLastError(); }
     src = dst; dst += tiles; m = tiles;
   }
+}
+inline hipError_t sum_doubles(const double* in, long long n, double* tmp, double** d_result, hipStream_t st) {
+  return sum_values<double>(in, n, tmp, d_result, st);
 }
 }  // namespace prims
