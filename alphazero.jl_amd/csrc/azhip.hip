@@ -97,15 +97,6 @@ extern "C" int az_engine_cfg_init(az_engine_cfg* c) {
   return AZ_OK;
 }
 
-static size_t net_nparams(const GameInfo& gi, const az_engine_cfg& c) {
-  size_t P = gi.P, F = c.num_filters, npf = c.num_policy_head_filters, nvf = c.num_value_head_filters;
-  size_t s = 9 * (size_t)gi.C * F + 5 * F;
-  s += (size_t)c.num_blocks * 2 * (9 * F * F + 5 * F);
-  s += F * npf + 5 * npf + (size_t)gi.A * P * npf + gi.A;
-  s += F * nvf + 5 * nvf + F * P * nvf + F + F + 1;
-  return s;
-}
-
 static void drop_wave_graphs(az_engine* e);
 extern "C" int az_engine_destroy(az_engine* e) {
   if (!e) return AZ_OK;
@@ -644,7 +635,7 @@ extern "C" int az_game_play(az_engine* e, const uint64_t* keys, const int32_t* a
 // ------------------------------------------------------------------------------- network
 extern "C" int az_net_num_params(const az_engine* e, int64_t* n) {
   if (!e || !n) return fail(AZ_ERR_BAD_ARG, "NULL");
-  *n = (int64_t)net_nparams(e->gi, e->cfg);
+  *n = (int64_t)net_layout(e->gi, e->cfg).total;
   return AZ_OK;
 }
 
@@ -656,51 +647,21 @@ static void bn_fold(const float* bias, const float* bn, int n, float* scale, flo
     shift[i] = az_fmaf(bias[i] - mu[i], scale[i], be[i]);
   }
 }
-// Flux conv weight W[i + k*(j + k*(ci + Cin*co))] -> MFMA B-fragment order.  Tap t = (dy+1)*3 +
-// (dx+1) reads W[i = 1-dx, j = 1-dy] (true convolution, flipped kernel).
-static void pack_conv(const float* Wt, int ksz, int Cin, int Cout, int CoutPad, float* dst /* [ntap][CoutPad/32][Cin/8][64][4] */) {
-  const int ntap = ksz * ksz, NT = CoutPad / 32, JQ = Cin / 8, half = Cin / 2;
-  for (int t = 0; t < ntap; ++t) {
-    int dy = ksz == 3 ? t / 3 - 1 : 0, dx = ksz == 3 ? t % 3 - 1 : 0;
-    int wi = ksz == 3 ? 1 - dx : 0, wj = ksz == 3 ? 1 - dy : 0;
-    for (int n = 0; n < NT; ++n) for (int jq = 0; jq < JQ; ++jq) for (int l = 0; l < 64; ++l) for (int q = 0; q < 4; ++q) {
-      int ci = (l >> 5) * half + jq * 4 + q, co = n * 32 + (l & 31);
-      float val = co < Cout ? Wt[(size_t)wi + (size_t)ksz * (wj + (size_t)ksz * (ci + (size_t)Cin * co))] : 0.0f;
-      dst[((((size_t)t * NT + n) * JQ + jq) * 64 + l) * 4 + q] = val;
-    }
-  }
-}
-
-// Flux conv weight (as pack_conv) -> k_tower16 B-fragment order (16x16x4 MFMA): lane l of step s = 4 sq + q supplies input channel c = (g&1)*F/2 + 2s + (g>>1),
-// g = l >> 4, for output column ct*16 + (l & 15).  ksz = 3: a tower layer, 1: the concatenated head convolution
-static void pack_conv16(const float* Wt, int ksz, int F, float* dst /* [ntap][F/16 col tiles][F/16][64][4] */) {
-  const int ntap = ksz * ksz, CT = F / 16;
-  for (int t = 0; t < ntap; ++t) {
-    int dy = ksz == 3 ? t / 3 - 1 : 0, dx = ksz == 3 ? t % 3 - 1 : 0;
-    int wi = ksz == 3 ? 1 - dx : 0, wj = ksz == 3 ? 1 - dy : 0;
-    for (int ct = 0; ct < CT; ++ct) for (int sq = 0; sq < CT; ++sq) for (int ln = 0; ln < 64; ++ln) for (int q = 0; q < 4; ++q) {
-      int s = 4 * sq + q, g = ln >> 4, ci = (g & 1) * (F / 2) + 2 * s + (g >> 1), co = ct * 16 + (ln & 15);
-      dst[((((size_t)t * CT + ct) * CT + sq) * 64 + ln) * 4 + q] = Wt[(size_t)wi + (size_t)ksz * (wj + (size_t)ksz * (ci + (size_t)F * co))];
-    }
-  }
-}
 static uint16_t to_bf16(float f) {                                   // round to nearest even
   uint32_t u; memcpy(&u, &f, 4);
   if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
   return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
-// Flux conv weight -> k_tower16b B-fragment order (bf16, 16x16x32 MFMA): lane l of k step ks supplies input channels ks*32 + (l >> 4)*8 + el, el = 0..7,
-// for output column ct*16 + (l & 15)
-static void pack_conv16b(const float* Wt, int ksz, int F, uint16_t* dst /* [ntap][F/16 col tiles][F/32 k steps][64][8] */) {
-  const int ntap = ksz * ksz, CT = F / 16, KSB = F / 32;
-  for (int t = 0; t < ntap; ++t) {
-    int dy = ksz == 3 ? t / 3 - 1 : 0, dx = ksz == 3 ? t % 3 - 1 : 0;
-    int wi = ksz == 3 ? 1 - dx : 0, wj = ksz == 3 ? 1 - dy : 0;
-    for (int ct = 0; ct < CT; ++ct) for (int ks = 0; ks < KSB; ++ks) for (int ln = 0; ln < 64; ++ln) for (int el = 0; el < 8; ++el) {
-      int ci = ks * 32 + (ln >> 4) * 8 + el, co = ct * 16 + (ln & 15);
-      dst[((((size_t)t * CT + ct) * KSB + ks) * 64 + ln) * 8 + el] = to_bf16(Wt[(size_t)wi + (size_t)ksz * (wj + (size_t)ksz * (ci + (size_t)F * co))]);
-    }
-  }
+// dst[j] = blob[map[j]], zero where the map says padding (net_layout.h)
+static std::vector<float> gather(const IndexMap& m, const float* blob) {
+  std::vector<float> d(m.size());
+  for (size_t j = 0; j < m.size(); ++j) d[j] = m[j] < 0 ? 0.0f : blob[m[j]];
+  return d;
+}
+static std::vector<uint16_t> gather_bf16(const IndexMap& m, const float* blob) {
+  std::vector<uint16_t> d(m.size());
+  for (size_t j = 0; j < m.size(); ++j) d[j] = m[j] < 0 ? 0 : to_bf16(blob[m[j]]);
+  return d;
 }
 // a packed piece of the network goes to the device (released by the next az_net_set_params)
 template <class T, class P> static int net_upload(az_engine* e, const std::vector<T>& h, const P** d) {
@@ -713,129 +674,44 @@ template <class T, class P> static int net_upload(az_engine* e, const std::vecto
   return AZ_OK;
 }
 
+// The host copies of the device arrays of NetDev / Net16Dev / Net16bDev: each gathered through its map (what lies where is net_layout.h's
+// business); every batch norm folded to (scale, shift) per channel, the tower's layer after layer and ending in one zero float4.
+struct NetHost {
+  std::vector<float> stem_w, stem_ss, conv_w, conv_ss, head_w, head_ss, pol_w, pol_b, val_w, val_b, val2_w, hd_w, hd16_w, s16_w, c16_w, h16_w;
+  std::vector<uint16_t> c16b_w, h16b_w;                              // bf16 engines only
+};
+static NetHost net_host(const NetLayout& lay, const NetMaps& M, const float* blob, bool bf16) {
+  NetHost h;
+  h.stem_w = gather(M.stem_w, blob); h.conv_w = gather(M.conv_w, blob); h.head_w = gather(M.head_w, blob);
+  h.pol_w = gather(M.pol_w, blob); h.pol_b = gather(M.pol_b, blob);
+  h.val_w = gather(M.val_w, blob); h.val_b = gather(M.val_b, blob); h.val2_w = gather(M.val2_w, blob);
+  h.hd_w = gather(M.hd_w, blob); h.hd16_w = gather(M.hd16_w, blob);
+  h.s16_w = gather(M.s16_w, blob); h.c16_w = gather(M.c16_w, blob); h.h16_w = gather(M.h16_w, blob);
+  if (bf16) { h.c16b_w = gather_bf16(M.c16b_w, blob); h.h16b_w = gather_bf16(M.h16b_w, blob); }
+  const int F = lay.s.F, HF = F;                                    // head features padded to the trunk width
+  h.stem_ss.assign(2 * F, 0.0f); h.conv_ss.assign((size_t)lay.ntower() * 2 * F + 4, 0.0f); h.head_ss.assign(2 * HF, 0.0f);
+  bn_fold(blob + lay.stem().b, blob + lay.stem().bn, F, h.stem_ss.data(), h.stem_ss.data() + F);
+  for (int l = 0; l < lay.ntower(); ++l)
+    bn_fold(blob + lay.tower(l).b, blob + lay.tower(l).bn, F, h.conv_ss.data() + (size_t)l * 2 * F, h.conv_ss.data() + (size_t)l * 2 * F + F);
+  const std::vector<float> hb = gather(M.head_b, blob);
+  std::vector<float> hbn = gather(M.head_bn, blob);
+  for (int co = lay.s.npf + lay.s.nvf; co < HF; ++co) hbn[(size_t)3 * HF + co] = 1.0f;   // padded channels: gamma 0, var 1 -- scale and shift exactly 0
+  bn_fold(hb.data(), hbn.data(), HF, h.head_ss.data(), h.head_ss.data() + HF);
+  return h;
+}
+
 static int ec_empty(az_engine* e, bool wipe = false);
 extern "C" int az_net_set_params(az_engine* e, const float* blob, int64_t n) {
   ENGINE(e);
   if (e->cfg.oracle != AZ_ORACLE_RESNET) return fail(AZ_ERR_STATE, "engine was created without the ResNet oracle");
   if (e->running) return fail(AZ_ERR_STATE, "self-play in progress");
-  const GameInfo& gi = e->gi;
   const az_engine_cfg& c = e->cfg;
-  if (!blob || n != (int64_t)net_nparams(gi, c)) return fail(AZ_ERR_BAD_ARG, "parameter blob has %lld values, expected %zu", (long long)n, net_nparams(gi, c));
-  const int F = c.num_filters, npf = c.num_policy_head_filters, nvf = c.num_value_head_filters, P = gi.P, C = gi.C, A = gi.A;
-  const int HF = F, L = gi.APAD, nb = c.num_blocks;   // head features padded to the trunk width
+  const NetLayout lay = net_layout(e->gi, c);
+  if (!blob || n != (int64_t)lay.total) return fail(AZ_ERR_BAD_ARG, "parameter blob has %lld values, expected %zu", (long long)n, lay.total);
   e->blob.assign(blob, blob + n);
-  const float* w = blob;
-  // stem fragments: k = t*C + ci (tap t = (dy+1)*3 + (dx+1) reads W[1-dx, 1-dy]), K padded to 2*K2,
-  // lane l supplies k = (l>>5)*K2 + j for MFMA j
-  const int K2 = (9 * C + 1) / 2;
-  std::vector<float> stem_w((size_t)(F / 32) * K2 * 64, 0.0f), stem_ss(2 * F);
-  for (int nt = 0; nt < F / 32; ++nt) for (int j = 0; j < K2; ++j) for (int l = 0; l < 64; ++l) {
-    int k = (l >> 5) * K2 + j, co = nt * 32 + (l & 31);
-    if (k >= 9 * C) continue;
-    int t = k / C, ci = k % C, dy = t / 3 - 1, dx = t % 3 - 1, wi = 1 - dx, wj = 1 - dy;
-    stem_w[((size_t)nt * K2 + j) * 64 + l] = w[wi + 3 * (wj + 3 * (ci + (size_t)C * co))];
-  }
-  bn_fold(w + 9 * C * F, w + 9 * C * F + F, F, stem_ss.data(), stem_ss.data() + F);
-  w += (size_t)9 * C * F + 5 * F;
-  const size_t layer_f = (size_t)9 * (F / 32) * (F / 8) * 64 * 4;
-  std::vector<float> conv_w(layer_f * 2 * nb + 4), conv_ss((size_t)2 * nb * 2 * F + 4);
-  for (int l = 0; l < 2 * nb; ++l) {
-    pack_conv(w, 3, F, F, F, conv_w.data() + layer_f * l);
-    bn_fold(w + (size_t)9 * F * F, w + (size_t)9 * F * F + F, F, conv_ss.data() + (size_t)l * 2 * F, conv_ss.data() + (size_t)l * 2 * F + F);
-    w += (size_t)9 * F * F + 5 * F;
-  }
-  // k_tower16 fragments (pack_conv16) and its stem
-  std::vector<float> c16_w(4), s16_w(4);
-  const int CT = F / 16;                     // column tiles = waves = float4 of B per tap and lane
-  const float* const wc0 = blob + (size_t)9 * C * F + 5 * F;        // the first tower layer
-  const size_t layer_w = (size_t)9 * F * F + 5 * F, layer16 = (size_t)9 * CT * CT * 64 * 4;
-  {
-    c16_w.assign(layer16 * 2 * nb + 4, 0.0f);
-    for (int l = 0; l < 2 * nb; ++l) pack_conv16(wc0 + layer_w * l, 3, F, c16_w.data() + layer16 * l);
-    const int KK = 9 * C, K2s = (KK + 1) / 2, NS = (2 * K2s + 3) / 4;
-    s16_w.assign((size_t)CT * NS * 64, 0.0f);
-    for (int ct = 0; ct < CT; ++ct) for (int s = 0; s < NS; ++s) for (int ln = 0; ln < 64; ++ln) {
-      int p = 4 * s + (ln >> 4), k = (p & 1) * K2s + (p >> 1), co = ct * 16 + (ln & 15);
-      if (k >= KK || p >= 2 * K2s) continue;
-      int t = k / C, ci = k % C, dy = t / 3 - 1, dx = t % 3 - 1, wi = 1 - dx, wj = 1 - dy;
-      s16_w[((size_t)ct * NS + s) * 64 + ln] = blob[wi + 3 * (wj + 3 * (ci + (size_t)C * co))];
-    }
-  }
-  // k_tower16b fragments (pack_conv16b)
-  std::vector<uint16_t> c16b_w(8), h16b_w(8);
-  const size_t layer16b = (size_t)9 * CT * (F / 32) * 64 * 8;
-  if (c.net_bf16) {
-    c16b_w.assign(layer16b * 2 * nb + 8, 0);
-    for (int l = 0; l < 2 * nb; ++l) pack_conv16b(wc0 + layer_w * l, 3, F, c16b_w.data() + layer16b * l);
-  }
-  // heads: concatenate the two 1x1 convolutions along the output channel
-  std::vector<float> hw((size_t)F * HF, 0.0f), hb(HF, 0.0f), hbn((size_t)4 * HF, 0.0f), head_w((size_t)(HF / 32) * (F / 8) * 64 * 4), head_ss(2 * HF);
-  for (int i = 0; i < HF; ++i) { hbn[i] = 0.0f; hbn[3 * HF + i] = 1.0f; }   // padded channels: gamma 0, var 1
-  const float* pw = w; const float* pb = pw + (size_t)F * npf; const float* pbn = pb + npf;
-  const float* pdw = pbn + 4 * npf; const float* pdb = pdw + (size_t)A * P * npf;
-  const float* vw = pdb + A; const float* vb = vw + (size_t)F * nvf; const float* vbn = vb + nvf;
-  const float* vdw = vbn + 4 * nvf; const float* vdb = vdw + (size_t)F * P * nvf;
-  const float* v2w = vdb + F; const float* v2b = v2w + F;
-  for (int co = 0; co < npf; ++co) {
-    for (int ci = 0; ci < F; ++ci) hw[ci + (size_t)F * co] = pw[ci + (size_t)F * co];
-    hb[co] = pb[co];
-    for (int k = 0; k < 4; ++k) hbn[(size_t)k * HF + co] = pbn[(size_t)k * npf + co];
-  }
-  for (int co = 0; co < nvf; ++co) {
-    for (int ci = 0; ci < F; ++ci) hw[ci + (size_t)F * (npf + co)] = vw[ci + (size_t)F * co];
-    hb[npf + co] = vb[co];
-    for (int k = 0; k < 4; ++k) hbn[(size_t)k * HF + npf + co] = vbn[(size_t)k * nvf + co];
-  }
-  pack_conv(hw.data(), 1, F, HF, HF, head_w.data());
-  std::vector<float> h16_w((size_t)CT * CT * 64 * 4, 0.0f);
-  pack_conv16(hw.data(), 1, F, h16_w.data());
-  if (c.net_bf16) {
-    h16b_w.assign((size_t)CT * (F / 32) * 64 * 8, 0);
-    pack_conv16b(hw.data(), 1, F, h16b_w.data());
-  }
-  bn_fold(hb.data(), hbn.data(), HF, head_ss.data(), head_ss.data() + HF);
-  // dense layers, k-major with k = p*nf + f; Flux Dense W[out + nout*(p + P*f)]
-  std::vector<float> pol_w((size_t)P * npf * L, 0.0f), pol_b(L, 0.0f), val_w((size_t)P * nvf * F), val_b(F), val2_w(F);
-  for (int q = 0; q < P; ++q) for (int f = 0; f < npf; ++f) for (int a = 0; a < A; ++a)
-    pol_w[(size_t)(q * npf + f) * L + a] = pdw[a + (size_t)A * (q + (size_t)P * f)];
-  for (int a = 0; a < A; ++a) pol_b[a] = pdb[a];
-  for (int q = 0; q < P; ++q) for (int f = 0; f < nvf; ++f) for (int o = 0; o < F; ++o)
-    val_w[(size_t)(q * nvf + f) * F + o] = vdw[o + (size_t)F * (q + (size_t)P * f)];
-  for (int o = 0; o < F; ++o) { val_b[o] = vdb[o]; val2_w[o] = v2w[o]; }
-  // MFMA dense-head fragments: per MFMA pair i (k = 4i..4i+3) and lane: (W[4i+h][o], W[4i+2+h][o])
-  const bool hd_ok = (npf % 4 == 0) && (nvf % 4 == 0);
-  const int NVT = F / 32;
-  std::vector<float> hd_w(4);
-  if (hd_ok) {
-    const size_t vsteps = (size_t)P * nvf / 4, psteps = (size_t)P * npf / 4;
-    const int NPT = (A + 31) / 32;                                  // 32-column policy tiles (1 for the device games, 3 for 82 actions)
-    hd_w.assign((NVT * vsteps + NPT * psteps) * 64 * 2, 0.0f);
-    for (int t = 0; t < NVT; ++t) for (size_t i = 0; i < vsteps; ++i) for (int l = 0; l < 64; ++l) {
-      int hh = l >> 5, o = t * 32 + (l & 31);
-      float* d = &hd_w[((t * vsteps + i) * 64 + l) * 2];
-      d[0] = val_w[(4 * i + hh) * F + o];
-      d[1] = val_w[(4 * i + 2 + hh) * F + o];
-    }
-    for (int pt = 0; pt < NPT; ++pt) for (size_t i = 0; i < psteps; ++i) for (int l = 0; l < 64; ++l) {
-      int hh = l >> 5, o = pt * 32 + (l & 31);
-      float* d = &hd_w[((NVT * vsteps + pt * psteps + i) * 64 + l) * 2];
-      d[0] = o < A ? pol_w[(4 * i + hh) * L + o] : 0.0f;
-      d[1] = o < A ? pol_w[(4 * i + 2 + hh) * L + o] : 0.0f;
-    }
-  }
-  // k_heads16 fragments (16-board tiles, 32 head filters): per 16-k block j and lane one float4, element s = W[16j + 4s + g][16 tile + (lane & 15)]
-  const bool hd16_ok = npf == 32 && nvf == 32;
-  std::vector<float> hd16_w(4);
-  if (hd16_ok) {
-    const int NV16 = F / 16, NP16 = (A + 15) / 16;
-    const size_t NB = (size_t)2 * P;
-    hd16_w.assign((size_t)(NV16 + NP16) * NB * 64 * 4, 0.0f);
-    for (int t = 0; t < NV16 + NP16; ++t) for (size_t j = 0; j < NB; ++j) for (int l = 0; l < 64; ++l) for (int s4 = 0; s4 < 4; ++s4) {
-      const size_t k = 16 * j + 4 * s4 + (l >> 4);
-      const int o = (t < NV16 ? t : t - NV16) * 16 + (l & 15);
-      hd16_w[((t * NB + j) * 64 + l) * 4 + s4] = t < NV16 ? val_w[k * F + o] : (o < A ? pol_w[k * L + o] : 0.0f);
-    }
-  }
+  if (!e->net_maps) e->net_maps.reset(new NetMaps(lay, c.net_bf16 != 0));
+  const NetMaps& M = *e->net_maps;
+  const NetHost h = net_host(lay, M, blob, c.net_bf16 != 0);
   AZCHK(sync_all(e));
   drop_wave_graphs(e);                                             // they hold the old parameter pointers
   for (void* q : e->net_allocs) (void)hipFree(q);
@@ -843,29 +719,29 @@ extern "C" int az_net_set_params(az_engine* e, const float* blob, int64_t n) {
   e->net_loaded = false;
   NetDev nd;
   memset(&nd, 0, sizeof nd);
-  nd.nblocks = nb; nd.F = F; nd.npf = npf; nd.nvf = nvf; nd.HF = HF;
-  AZCHK(net_upload(e, stem_w, &nd.stem_w)); AZCHK(net_upload(e, stem_ss, &nd.stem_ss));
-  AZCHK(net_upload(e, conv_w, &nd.conv_w)); AZCHK(net_upload(e, conv_ss, &nd.conv_ss));
-  AZCHK(net_upload(e, head_w, &nd.head_w)); AZCHK(net_upload(e, head_ss, &nd.head_ss));
-  AZCHK(net_upload(e, pol_w, &nd.pol_w)); AZCHK(net_upload(e, pol_b, &nd.pol_b)); AZCHK(net_upload(e, val_w, &nd.val_w)); AZCHK(net_upload(e, val_b, &nd.val_b)); AZCHK(net_upload(e, val2_w, &nd.val2_w));
-  nd.val2_b = *v2b;
-  AZCHK(net_upload(e, hd_w, &nd.hd_w));
-  nd.hd_ok = hd_ok ? 1 : 0;
-  AZCHK(net_upload(e, hd16_w, &nd.hd16_w));
-  nd.hd16_ok = hd16_ok ? 1 : 0;
+  nd.nblocks = c.num_blocks; nd.F = c.num_filters; nd.npf = c.num_policy_head_filters; nd.nvf = c.num_value_head_filters; nd.HF = c.num_filters;
+  AZCHK(net_upload(e, h.stem_w, &nd.stem_w)); AZCHK(net_upload(e, h.stem_ss, &nd.stem_ss));
+  AZCHK(net_upload(e, h.conv_w, &nd.conv_w)); AZCHK(net_upload(e, h.conv_ss, &nd.conv_ss));
+  AZCHK(net_upload(e, h.head_w, &nd.head_w)); AZCHK(net_upload(e, h.head_ss, &nd.head_ss));
+  AZCHK(net_upload(e, h.pol_w, &nd.pol_w)); AZCHK(net_upload(e, h.pol_b, &nd.pol_b)); AZCHK(net_upload(e, h.val_w, &nd.val_w)); AZCHK(net_upload(e, h.val_b, &nd.val_b)); AZCHK(net_upload(e, h.val2_w, &nd.val2_w));
+  nd.val2_b = blob[lay.v2_b];
+  AZCHK(net_upload(e, h.hd_w, &nd.hd_w));
+  nd.hd_ok = M.hd_ok ? 1 : 0;
+  AZCHK(net_upload(e, h.hd16_w, &nd.hd16_w));
+  nd.hd16_ok = M.hd16_ok ? 1 : 0;
   Net16Dev n16;
   memset(&n16, 0, sizeof n16);
-  n16.nblocks = nb;
-  AZCHK(net_upload(e, s16_w, &n16.stem_w)); n16.stem_ss = nd.stem_ss;
-  AZCHK(net_upload(e, c16_w, &n16.conv_w)); n16.conv_ss = nd.conv_ss;
-  AZCHK(net_upload(e, h16_w, &n16.head_w)); n16.head_ss = nd.head_ss;
+  n16.nblocks = c.num_blocks;
+  AZCHK(net_upload(e, h.s16_w, &n16.stem_w)); n16.stem_ss = nd.stem_ss;
+  AZCHK(net_upload(e, h.c16_w, &n16.conv_w)); n16.conv_ss = nd.conv_ss;
+  AZCHK(net_upload(e, h.h16_w, &n16.head_w)); n16.head_ss = nd.head_ss;
   memcpy(n16.geo, e->d_geo, sizeof n16.geo);
   e->net16 = n16;
   Net16bDev nbd;
   memset(&nbd, 0, sizeof nbd);
-  nbd.nblocks = nb; nbd.stem_w = n16.stem_w; nbd.stem_ss = n16.stem_ss; nbd.conv_ss = n16.conv_ss; nbd.head_ss = n16.head_ss;
+  nbd.nblocks = c.num_blocks; nbd.stem_w = n16.stem_w; nbd.stem_ss = n16.stem_ss; nbd.conv_ss = n16.conv_ss; nbd.head_ss = n16.head_ss;
   memcpy(nbd.geo, e->d_geo, sizeof nbd.geo);
-  if (c.net_bf16) { AZCHK(net_upload(e, c16b_w, &nbd.conv_w)); AZCHK(net_upload(e, h16b_w, &nbd.head_w)); }
+  if (c.net_bf16) { AZCHK(net_upload(e, h.c16b_w, &nbd.conv_w)); AZCHK(net_upload(e, h.h16b_w, &nbd.head_w)); }
   e->net16b = nbd;
   HIPCHK(hipStreamSynchronize(e->stream));
   e->net = nd;

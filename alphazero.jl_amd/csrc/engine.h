@@ -12,6 +12,7 @@
 #include <new>
 #include <string>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <vector>
 #include <unordered_set>
@@ -20,6 +21,7 @@
 #include "../../include/azhip.h"
 #include "env.h"
 #include "games.h"
+#include "net_layout.h"
 #include "resnet.h"
 #include "resnet16.h"
 #include "resnet16b.h"
@@ -68,6 +70,11 @@ inline bool game_info(int gid, GameInfo* gi) {
     case AZ_GAME_GO9_PLANES: *gi = {Go9Planes::A, Go9Planes::APAD, Go9Planes::W, Go9Planes::H, Go9Planes::C, Go9Planes::P, Go9Planes::MAX_PLIES, 64}; return true;   // network-only geometry: no tree
   }
   return false;
+}
+
+// where each piece of a ResNet engine's parameter blob lies (net_layout.h)
+inline NetLayout net_layout(const GameInfo& gi, const az_engine_cfg& c) {
+  return NetLayout(NetShape{gi.C, gi.P, gi.A, gi.APAD, c.num_blocks, c.num_filters, c.num_policy_head_filters, c.num_value_head_filters});
 }
 
 // ------------------------------------------------------------------------------- engine
@@ -139,6 +146,7 @@ struct az_engine {
   // network
   bool net_loaded = false;
   std::vector<float> blob;
+  std::unique_ptr<const NetMaps> net_maps;   // net_layout.h: the index maps of the arrays below; they depend on cfg only, so the first az_net_set_params builds them for all
   NetDev net = {};
   Net16bDev net16b = {};         // bf16 fragments (cfg.net_bf16)
   Net16Dev net16 = {};           // k_tower16 fragments (64 filters)

@@ -387,7 +387,7 @@ __global__ void k_tr_sumsq(const float* __restrict__ w, const unsigned char* __r
 // ------------------------------------------------------------------------------------------ host
 struct TrConv {                 // one convolution + batch norm (3x3 of the tower, or a 1x1 head convolution)
   int cin, cout, taps;
-  size_t off_w, off_b, off_bn;  // blob offsets: W, bias, (gamma, beta, mean, var)
+  size_t off_b, off_bn;         // blob offsets: bias, (gamma, beta, mean, var)
   size_t wk_wm;                 // offset in the working-parameter array: GEMM matrix [taps*cin][cout]
   size_t wk_ffwd, wk_fdg;       // tower convolutions F -> F: MFMA fragments of k_conv16_layer for forward / data gradient
   bool mfma;                    // forward and data gradient on k_conv16_layer instead of im2col + GEMM
@@ -408,7 +408,7 @@ struct az_trainer {
   long long R;
   size_t nparams;
   std::vector<TrConv> convs;    // stem, block convs..., then policy-head conv, value-head conv
-  size_t off_pd_w, off_pd_b, off_v1_w, off_v1_b, off_v2_w, off_v2_b;      // dense layers in the blob
+  size_t off_pd_b, off_v1_b, off_v2_b;                                     // dense-layer biases in the blob
   size_t wk_pd, wk_v1, wk_v2, nwork;
   float *blob, *gblob, *opt_m, *opt_v; unsigned char* trainable;           // [nparams]
   int* scat; long long nscat;                                                // working entries that carry a gradient (the primary ranges)
@@ -465,75 +465,26 @@ extern "C" int az_trainer_destroy(az_trainer* t) {
 // builds layer tables, parameter maps and buffers
 static int trainer_build(az_trainer* t) {
   const GameInfo& gi = t->gi;
-  const int F = t->F, C = gi.C, P = gi.P, A = gi.A, npf = t->npf, nvf = t->nvf;
+  const int F = t->F, C = gi.C, P = gi.P, A = gi.A;
   const long long R = t->R;
-  size_t off = 0, wk = 0;
-  auto add_conv = [&](int cin, int cout, int taps) {
-    TrConv c{};
-    c.cin = cin; c.cout = cout; c.taps = taps;
-    c.off_w = off; off += (size_t)taps * cin * cout;
-    c.off_b = off; off += cout;
-    c.off_bn = off; off += 4 * (size_t)cout;
-    c.wk_wm = wk; wk += (size_t)taps * cin * cout;
-    c.mfma = taps == 9 && cin == cout;                               // the tower's F -> F convolutions (F = 64 or 128: az_engine_create): MFMA layer kernels
-    c.wk_ffwd = c.wk_fdg = 0;
-    if (c.mfma) { c.wk_ffwd = wk; wk += (size_t)taps * cin * cout; c.wk_fdg = wk; wk += (size_t)taps * cin * cout; }
-    t->convs.push_back(c);
-  };
-  add_conv(C, F, 9);
-  for (int l = 0; l < 2 * t->nblocks; ++l) add_conv(F, F, 9);
+  const NetLayout lay = net_layout(gi, t->e->cfg);
+  const TrainMaps tm(lay);                                            // net_layout.h: the working parameters and where each comes from
+  const IndexMap &map = tm.map, &scat = tm.scat;
+  const std::vector<unsigned char> trainable = trainable_mask(lay);
+  const size_t wk = map.size();
   // tr_forward_backward takes the input of every MFMA layer from the layer below (bn_of(l - 1)) and the stem's from the batch's planes:
-  // that holds only while the stem is the one non-MFMA tower layer.  A game with as many planes as filters would make it one.
-  t->convs[0].mfma = false; t->convs[0].wk_ffwd = t->convs[0].wk_fdg = 0;
-  for (int l = 1; l <= 2 * t->nblocks; ++l)
-    if (!t->convs[l].mfma) return fail(AZ_ERR_STATE, "trainer: tower layer %d is not an MFMA layer", l);
-  add_conv(F, npf, 1);                                              // policy head: conv, (bn), then dense
-  t->off_pd_w = off; off += (size_t)A * P * npf; t->off_pd_b = off; off += A;
-  add_conv(F, nvf, 1);                                              // value head
-  t->off_v1_w = off; off += (size_t)F * P * nvf; t->off_v1_b = off; off += F;
-  t->off_v2_w = off; off += F; t->off_v2_b = off; off += 1;
-  if (off != t->nparams) return fail(AZ_ERR_STATE, "trainer layout (%zu) does not match the network (%zu parameters)", off, t->nparams);
-  t->wk_pd = wk; wk += (size_t)P * npf * A;
-  t->wk_v1 = wk; wk += (size_t)P * nvf * F;
-  t->wk_v2 = wk; wk += F;
-  t->nwork = wk;
-  // parameter maps: work[j] = blob[map[j]]
-  std::vector<int> map(wk);
-  std::vector<unsigned char> trainable(t->nparams, 1);
-  for (const TrConv& c : t->convs) {
-    for (int tap = 0; tap < c.taps; ++tap) {
-      const int dy = c.taps == 9 ? tap / 3 - 1 : 0, dx = c.taps == 9 ? tap % 3 - 1 : 0;
-      const int wi = c.taps == 9 ? 1 - dx : 0, wj = c.taps == 9 ? 1 - dy : 0, ks = c.taps == 9 ? 3 : 1;
-      for (int ci = 0; ci < c.cin; ++ci) for (int co = 0; co < c.cout; ++co) {
-        const int b = (int)(c.off_w + (size_t)wi + (size_t)ks * (wj + (size_t)ks * (ci + (size_t)c.cin * co)));   // Flux W(kw, kh, ci, co), true convolution
-        map[c.wk_wm + ((size_t)tap * c.cin + ci) * c.cout + co] = b;
-      }
-    }
-    if (c.mfma) {
-      // fragment order of conv16 (see az_net_set_params): lane ln of float4 sq, component q, column tile ct supplies input
-      // channel ci = (g & 1) F/2 + 2 (4 sq + q) + (g >> 1), g = ln >> 4, for output channel co = 16 ct + (ln & 15)
-      const int Fc = c.cin, CT = Fc / 16;
-      auto blob_of = [&](int tap, int ci, int co) {
-        const int dy = tap / 3 - 1, dx = tap % 3 - 1, wi = 1 - dx, wj = 1 - dy;
-        return (int)(c.off_w + (size_t)wi + 3 * (wj + 3 * (ci + (size_t)Fc * co)));
-      };
-      for (int tap = 0; tap < 9; ++tap) for (int ct = 0; ct < CT; ++ct) for (int sq = 0; sq < CT; ++sq) for (int ln = 0; ln < 64; ++ln) for (int q = 0; q < 4; ++q) {
-        const int sidx = 4 * sq + q, g = ln >> 4, kin = (g & 1) * (Fc / 2) + 2 * sidx + (g >> 1), nout = ct * 16 + (ln & 15);
-        const size_t j = ((((size_t)tap * CT + ct) * CT + sq) * 64 + ln) * 4 + q;
-        map[c.wk_ffwd + j] = blob_of(tap, kin, nout);                  // forward: in = ci, out = co
-        map[c.wk_fdg + j] = blob_of(8 - tap, nout, kin);               // data gradient: in = co, out = ci, taps mirrored
-      }
-    }
-    for (int i = 0; i < 2 * c.cout; ++i) trainable[c.off_bn + 2 * c.cout + i] = 0;                              // running mean / variance
+  // the stem is the one non-MFMA tower layer, whatever its plane count.
+  for (size_t l = 0; l < lay.conv.size(); ++l) {
+    const ConvAt& at = lay.conv[l];
+    TrConv c{};
+    c.cin = at.cin; c.cout = at.cout; c.taps = at.taps();
+    c.off_b = at.b; c.off_bn = at.bn;
+    c.wk_wm = tm.conv[l].wm; c.wk_ffwd = tm.conv[l].ffwd; c.wk_fdg = tm.conv[l].fdg;
+    c.mfma = l >= 1 && (int)l <= lay.ntower();                       // the tower's F -> F convolutions (F = 64 or 128: az_engine_create): MFMA layer kernels
+    t->convs.push_back(c);
   }
-  for (int p = 0; p < P; ++p) for (int f = 0; f < npf; ++f) for (int a = 0; a < A; ++a)
-    map[t->wk_pd + ((size_t)p * npf + f) * A + a] = (int)(t->off_pd_w + a + (size_t)A * (p + (size_t)P * f));  // Dense W(out, in), in = p + P f (Flux.flatten of WHC)
-  for (int p = 0; p < P; ++p) for (int f = 0; f < nvf; ++f) for (int o = 0; o < F; ++o)
-    map[t->wk_v1 + ((size_t)p * nvf + f) * F + o] = (int)(t->off_v1_w + o + (size_t)F * (p + (size_t)P * f));
-  for (int o = 0; o < F; ++o) map[t->wk_v2 + o] = (int)(t->off_v2_w + o);
-  std::vector<int> scat;
-  for (const TrConv& c : t->convs) for (size_t j = 0; j < (size_t)c.taps * c.cin * c.cout; ++j) scat.push_back((int)(c.wk_wm + j));
-  for (size_t j = t->wk_pd; j < wk; ++j) scat.push_back((int)j);
+  t->off_pd_b = lay.pd_b; t->off_v1_b = lay.v1_b; t->off_v2_b = lay.v2_b;
+  t->wk_pd = tm.pd; t->wk_v1 = tm.v1; t->wk_v2 = tm.v2; t->nwork = wk;
   t->nscat = (long long)scat.size();
   AZCHK(tr_alloc(t, &t->scat, scat.size()));
   HIPCHK(hipMemcpyAsync(t->scat, scat.data(), sizeof(int) * scat.size(), hipMemcpyHostToDevice, t->stream));

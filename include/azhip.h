@@ -186,7 +186,8 @@ int az_game_play(az_engine* e, const uint64_t* keys, const int32_t* actions, int
  *   stem   conv W(3,3,C,F) b(F)  bn gamma,beta,mean,var (F each)
  *   block  x num_blocks: conv1 W(3,3,F,F) b bn(4F)  conv2 W(3,3,F,F) b bn(4F)
  *   phead  conv W(1,1,F,npf) b bn(4npf)  dense W(A, P*npf) b(A)
- *   vhead  conv W(1,1,F,nvf) b bn(4nvf)  dense W(F, P*nvf) b(F)  dense W(1,F) b(1)   */
+ *   vhead  conv W(1,1,F,nvf) b bn(4nvf)  dense W(F, P*nvf) b(F)  dense W(1,F) b(1)
+ * The library's own statement of this layout, and of every reordering of the weights for its kernels, is csrc/net_layout.h (NetLayout). */
 int az_net_num_params(const az_engine* e, int64_t* n);
 int az_net_set_params(az_engine* e, const float* blob, int64_t n); /* Network.copy(nn; on_gpu=true, test_mode=true) */
 int az_net_get_params(const az_engine* e, float* blob, int64_t n);
