@@ -166,6 +166,15 @@ SYMBOLS = {
     "az_memory_empty": [_VP],
     "az_dataset_create": [_VP, _I32, _I32, _I32, _I32, C.POINTER(_VP)],
     "az_dataset_create_from_tensors": [_I32, _I32, _I64, _VP, _VP, _VP, _VP, _VP, C.POINTER(_VP)],
+    "az_plane_memory_create": [_I32, _I32, _I64, C.POINTER(_VP)],
+    "az_plane_memory_destroy": [_VP],
+    "az_plane_memory_push_samples": [_VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP],
+    "az_plane_memory_push_trace": [_VP, _I32, _VP, _VP, _VP, _VP, _VP, C.c_double],
+    "az_plane_memory_read": [_VP, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _VP],
+    "az_plane_memory_length": [_VP, C.POINTER(_I64), C.POINTER(_I64)],
+    "az_plane_memory_new_batch": [_VP],
+    "az_plane_memory_empty": [_VP],
+    "az_dataset_create_from_plane_memory": [_VP, _I32, _I32, _I32, C.POINTER(_VP)],
     "az_dataset_destroy": [_VP],
     "az_dataset_get_info": [_VP, C.POINTER(DatasetInfo)],
     "az_dataset_read": [_VP, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _VP],

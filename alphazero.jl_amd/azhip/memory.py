@@ -257,3 +257,116 @@ class TensorDataset(Dataset):
 
     def samples(self):
         raise TypeError("a data set made from tensors holds no TrainingSamples: use tensors()")
+
+    @classmethod
+    def _adopt(cls, gspec, handle):
+        """a TensorDataset around a data-set handle the library built itself (PlaneMemoryBuffer.dataset)"""
+        self = cls.__new__(cls)
+        self.gspec, self._h = gspec, handle
+        info = _L.DatasetInfo()
+        _L.check(_L.lib().az_dataset_get_info(handle, _C.byref(info)))
+        self.num_samples, self.sum_n, self.Wtot, self.Wmean, self.Hp = info.num_samples, info.sum_n, info.Wtot, info.Wmean, info.Hp
+        return self
+
+
+class PlaneMemoryBuffer:
+    """MemoryBuffer(gspec, size) for a game whose rules live on the host (az_plane_memory_*): a circular buffer in HBM of what such a
+    game can give -- per sample the planes X (C, H, W) and the mask A (num_actions,) the network sees, π by FULL action index, z, t
+    and n.  Any of the four geometries; Go9PlanesSpec is the reason for it.
+
+    Two samples are one state when their (X, A) rows are bit-identical.  dataset() merges them (use_position_averaging), converts
+    them (convert_samples, learning.jl:17-51) and returns a TensorDataset, all on the device: Trainer takes it as it is."""
+
+    def __init__(self, gspec, capacity, device=0):
+        self.gspec = gspec
+        h = _C.c_void_p()
+        _L.check(_L.lib().az_plane_memory_create(gspec.game_id, int(device), int(capacity), _C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _L.lib().az_plane_memory_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _arrays(self, X, A, P):
+        nA = self.gspec.num_actions()
+        w, h, c = self.gspec.state_dim()
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        A = np.ascontiguousarray(A, dtype=np.float32)
+        P = np.ascontiguousarray(P, dtype=np.float64)
+        n = X.shape[0] if X.ndim else -1
+        if X.shape != (n, c, h, w):
+            raise ValueError("X must have shape (n, %d, %d, %d), got %s" % (c, h, w, X.shape))
+        for name, a in (("A", A), ("π", P)):
+            if a.shape != (n, nA):
+                raise ValueError("%s must have shape (%d, %d), got %s" % (name, n, nA, a.shape))
+        return n, X, A, P
+
+    @staticmethod
+    def _vector(name, a, n, dtype):
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.shape != (n,):
+            raise ValueError("%s must have shape (%d,), got %s" % (name, n, a.shape))
+        return a
+
+    def push_samples(self, X, A, π, z, t, n=None):
+        """push!(mem.buf, e) for samples the host holds (n: how often each was seen, default 1); cur_batch_size does not move"""
+        cnt, X, A, P = self._arrays(X, A, π)
+        z, t = self._vector("z", z, cnt, np.float64), self._vector("t", t, cnt, np.float64)
+        nv = None if n is None else self._vector("n", n, cnt, np.int64)
+        vp = lambda a: a.ctypes.data_as(_C.c_void_p) if a is not None else None
+        _L.check(_L.lib().az_plane_memory_push_samples(self._h, cnt, vp(X), vp(A), vp(P), vp(z), vp(t), vp(nv)))
+
+    def push_trace(self, X, A, π, rewards, white_playing, gamma):
+        """push_trace!(mem, trace, gamma) (memory.jl:74-87) for one game in playing order: the planes, mask and π of every position,
+        white's reward after every move and who was to move"""
+        cnt, X, A, P = self._arrays(X, A, π)
+        r = self._vector("rewards", rewards, cnt, np.float64)
+        wp = self._vector("white_playing", np.asarray(white_playing).astype(bool), cnt, np.uint8)
+        vp = lambda a: a.ctypes.data_as(_C.c_void_p)
+        _L.check(_L.lib().az_plane_memory_push_trace(self._h, cnt, vp(X), vp(A), vp(P), vp(r), vp(wp), float(gamma)))
+
+    def _lens(self):
+        a, b = _C.c_int64(), _C.c_int64()
+        _L.check(_L.lib().az_plane_memory_length(self._h, _C.byref(a), _C.byref(b)))
+        return a.value, b.value
+
+    def samples(self):
+        """get_experience(mem) on the host: (X, A, π, z, t, n) arrays in buffer order, oldest first"""
+        cnt, nA = len(self), self.gspec.num_actions()
+        w, h, c = self.gspec.state_dim()
+        X = np.zeros((cnt, c, h, w), dtype=np.float32); A = np.zeros((cnt, nA), dtype=np.float32); P = np.zeros((cnt, nA))
+        z = np.zeros(cnt); t = np.zeros(cnt); n = np.zeros(cnt, dtype=np.int64)
+        vp = lambda a: a.ctypes.data_as(_C.c_void_p)
+        _L.check(_L.lib().az_plane_memory_read(self._h, 0, cnt, vp(X), vp(A), vp(P), vp(z), vp(t), vp(n)))
+        return X, A, P, z, t, n
+
+    def __len__(self):
+        return self._lens()[0]
+
+    def cur_batch_size(self):
+        return self._lens()[1]
+
+    def new_batch(self):
+        _L.check(_L.lib().az_plane_memory_new_batch(self._h))
+
+    def empty(self):
+        _L.check(_L.lib().az_plane_memory_empty(self._h))
+
+    def dataset(self, last_batch=False, use_symmetries=False, use_position_averaging=False, weighing_policy=_L.WEIGHT_CONSTANT):
+        """get_experience / last_batch -> merge_by_state -> convert_samples on the device; the caller closes the TensorDataset"""
+        if use_symmetries:
+            raise ValueError("use_symmetries needs the game's symmetries, which live on the host: push the symmetric images "
+                             "(planes, mask and π of each) as samples of their own")
+        h = _C.c_void_p()
+        _L.check(_L.lib().az_dataset_create_from_plane_memory(self._h, 1 if last_batch else 0, 1 if use_position_averaging else 0,
+                                                              int(weighing_policy), _C.byref(h)))
+        return TensorDataset._adopt(self.gspec, h)

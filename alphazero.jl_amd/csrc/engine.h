@@ -332,6 +332,26 @@ struct az_dataset {
   std::vector<void*> allocs;
   bool own_stream = false;           // az_dataset_create_from_tensors: no memory behind it whose stream it could share; d_samples and d_envs are NULL
 };
+// plane_memory.hip: MemoryBuffer for a host-stepped game.  A sample is what the network sees -- the row (X, A) of RW = C*H*W + nA
+// Float32 words -- plus ND = nA + 2 doubles (pi by full action index, z, t) and n.
+struct az_plane_memory {
+  int game, device;
+  GameInfo gi;
+  hipStream_t stream;
+  int xs, nA, RW, ND;
+  float* d_XA;                       // [cap][RW]
+  double* d_D;                       // [cap][ND]
+  long long* d_n;                    // [cap]
+  int64_t cap, total, cur_batch;     // as az_memory
+  int hash_bits;                     // 128; az_debug_plane_memory_hash_bits lowers it
+};
+// the weight convert_samples gives a sample seen n times (learning.jl:17-25): every data-set builder's
+__device__ __forceinline__ float sample_weight(int policy, long long n) {
+  return policy == AZ_WEIGHT_CONSTANT ? 1.0f : policy == AZ_WEIGHT_LOG ? (float)(az_log2((double)n) + 1.0) : (float)n;
+}
+// memory.hip: checks the (W, X, A, P, V) tensors of a data set on the device as az_dataset_create_from_tensors documents
+// (AZ_ERR_BAD_ARG naming the first offending sample) and sets Wtot, Wmean and Hp from them
+int dataset_tensor_stats(az_dataset* d, hipStream_t st);
 // push_trace! (memory.jl:74-87) of ng games whose move records are ALREADY on the device: game g = d_moves[first[g] .. +cnt[g])
 int memory_push_device(az_memory* m, const az_move_rec* d_moves, const std::vector<long long>& first, const std::vector<int>& cnt, double gamma);
 template <class T> inline int mem_alloc(std::vector<void*>* keep, T** p, size_t n) {

@@ -171,7 +171,7 @@ __global__ void k_mem_convert(const az_sample* __restrict__ s, long long n, int 
   const az_sample e = s[i];
   const GEnv env = Gm::from_key(e.key[0], e.key[1]);
   envs[i] = env;
-  const float w = policy == AZ_WEIGHT_CONSTANT ? 1.0f : policy == AZ_WEIGHT_LOG ? (float)(az_log2((double)e.n) + 1.0) : (float)e.n;
+  const float w = sample_weight(policy, (long long)e.n);
   W[i] = w;
   const uint32_t m = Gm::mask(env);
   double hp = 0.0;
@@ -526,34 +526,11 @@ __global__ void __launch_bounds__(256) k_ds_check(const float* __restrict__ W, c
   if (code) atomicMin(bad, ((unsigned long long)i << 3) | (unsigned long long)code);
   t_w[i] = (double)w; t_hp[i] = code ? 0.0 : hp;
 }
-extern "C" int az_dataset_create_from_tensors(int32_t game, int32_t device, int64_t n, const float* W, const float* X, const float* A,
-                                              const float* P, const float* V, az_dataset** out) {
-  if (!out) return fail(AZ_ERR_BAD_ARG, "NULL argument");
-  *out = nullptr;
-  GameInfo gi;
-  if (!game_info(game, &gi)) return fail(AZ_ERR_BAD_ARG, "unknown game id %d", game);
-  if (n < 1 || n > (1LL << 31) - 1) return fail(AZ_ERR_BAD_ARG, "n must be in 1..2^31-1");
-  if (!W || !X || !A || !P || !V) return fail(AZ_ERR_BAD_ARG, "NULL tensor");
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(AZ_ERR_BAD_ARG, "device %d not available (%d visible)", device, ndev);
-  HIPCHK(hipSetDevice(device));
-  az_dataset* d = new (std::nothrow) az_dataset();
-  if (!d) return fail(AZ_ERR_HIP, "out of host memory");
-  d->game = game; d->device = device; d->gi = gi; d->stream = nullptr; d->own_stream = true; d->n = n; d->sum_n = n;
-  d->Wtot = 0.0; d->Wmean = 0.f; d->Hp = 0.f; d->d_samples = nullptr; d->d_envs = nullptr;
+int dataset_tensor_stats(az_dataset* d, hipStream_t st) {
+  const int64_t n = d->n;
+  const size_t xs = (size_t)d->gi.C * d->gi.P, nA = (size_t)d->gi.A, N = (size_t)n;
   std::vector<void*> tmp;
   int rc = [&]() -> int {
-    HIPCHK(hipStreamCreate(&d->stream));
-    hipStream_t st = d->stream;
-    const size_t xs = (size_t)gi.C * gi.P, nA = (size_t)gi.A, N = (size_t)n;
-    AZCHK(mem_alloc(&d->allocs, &d->d_W, N)); AZCHK(mem_alloc(&d->allocs, &d->d_V, N));
-    AZCHK(mem_alloc(&d->allocs, &d->d_A, N * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_P, N * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_X, N * xs));
-    HIPCHK(hipMemcpyAsync(d->d_W, W, sizeof(float) * N, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d->d_V, V, sizeof(float) * N, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d->d_A, A, sizeof(float) * N * nA, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d->d_P, P, sizeof(float) * N * nA, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d->d_X, X, sizeof(float) * N * xs, hipMemcpyHostToDevice, st));
     unsigned long long* d_bad; double *tw, *thp;
     AZCHK(mem_alloc(&tmp, &d_bad, 1)); AZCHK(mem_alloc(&tmp, &tw, N)); AZCHK(mem_alloc(&tmp, &thp, N));
     HIPCHK(hipMemsetAsync(d_bad, 0xff, sizeof(unsigned long long), st));
@@ -577,6 +554,38 @@ extern "C" int az_dataset_create_from_tensors(int32_t game, int32_t device, int6
     return AZ_OK;
   }();
   for (void* p : tmp) (void)hipFree(p);
+  return rc;
+}
+extern "C" int az_dataset_create_from_tensors(int32_t game, int32_t device, int64_t n, const float* W, const float* X, const float* A,
+                                              const float* P, const float* V, az_dataset** out) {
+  if (!out) return fail(AZ_ERR_BAD_ARG, "NULL argument");
+  *out = nullptr;
+  GameInfo gi;
+  if (!game_info(game, &gi)) return fail(AZ_ERR_BAD_ARG, "unknown game id %d", game);
+  if (n < 1 || n > (1LL << 31) - 1) return fail(AZ_ERR_BAD_ARG, "n must be in 1..2^31-1");
+  if (!W || !X || !A || !P || !V) return fail(AZ_ERR_BAD_ARG, "NULL tensor");
+  int ndev = 0;
+  HIPCHK(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return fail(AZ_ERR_BAD_ARG, "device %d not available (%d visible)", device, ndev);
+  HIPCHK(hipSetDevice(device));
+  az_dataset* d = new (std::nothrow) az_dataset();
+  if (!d) return fail(AZ_ERR_HIP, "out of host memory");
+  d->game = game; d->device = device; d->gi = gi; d->stream = nullptr; d->own_stream = true; d->n = n; d->sum_n = n;
+  d->Wtot = 0.0; d->Wmean = 0.f; d->Hp = 0.f; d->d_samples = nullptr; d->d_envs = nullptr;
+  int rc = [&]() -> int {
+    HIPCHK(hipStreamCreate(&d->stream));
+    hipStream_t st = d->stream;
+    const size_t xs = (size_t)gi.C * gi.P, nA = (size_t)gi.A, N = (size_t)n;
+    AZCHK(mem_alloc(&d->allocs, &d->d_W, N)); AZCHK(mem_alloc(&d->allocs, &d->d_V, N));
+    AZCHK(mem_alloc(&d->allocs, &d->d_A, N * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_P, N * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_X, N * xs));
+    HIPCHK(hipMemcpyAsync(d->d_W, W, sizeof(float) * N, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d->d_V, V, sizeof(float) * N, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d->d_A, A, sizeof(float) * N * nA, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d->d_P, P, sizeof(float) * N * nA, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d->d_X, X, sizeof(float) * N * xs, hipMemcpyHostToDevice, st));
+    AZCHK(dataset_tensor_stats(d, st));
+    return AZ_OK;
+  }();
   if (rc != AZ_OK) { az_dataset_destroy(d); return rc; }
   *out = d;
   return AZ_OK;

@@ -1,0 +1,406 @@
+// plane_memory.hip -- the replay memory of a host-stepped game (include/azhip.h "replay memory of plane samples").
+//
+//   MemoryBuffer / push_trace! / get_experience / last_batch            src/memory.jl:20-87
+//   merge_by_state                                                       src/memory.jl:89-112
+//   convert_samples (W, X, A, P, V)                                      src/learning.jl:17-51
+//
+// memory.hip stores 128-bit state keys and re-encodes them with the game's device twin.  A game whose rules live on the host has
+// no twin, so this memory stores what the host can give: the planes X and the mask A the network sees, pi by full action index,
+// z, t and n.  Two samples are one state when their (X, A) rows are bit-identical.  The data-set build never leaves HBM:
+//   k_pm_hash    one wavefront per sample mixes the row's words into a 128-bit key (fixed shuffle tree, no atomics)
+//   sort_pairs   twice (prims.h, stable): ascending (key, buffer index), so a group keeps buffer order
+//   k_pm_heads   one wavefront per adjacent pair compares the FULL rows: the hash only brings equal rows together, it never
+//                decides that two rows are equal.  Equal keys over different rows raise the error word
+//   k_pm_groups  + scan + a third sort_pairs on each group's first buffer index: output rows in order of first occurrence
+//   k_pm_merge   one wavefront per output row walks its members in buffer order (Float64, sequential, then one division, the
+//                order k_mem_merge documents) and writes W, X, A, P, V; without merging the same kernel runs on groups of one
+// The result is an az_dataset like az_dataset_create_from_tensors's, checked and summed by the same code (dataset_tensor_stats).
+#include "engine.h"
+#include "prims.h"
+
+#define PLANE_MEMORY(m) if (!(m)) return fail(AZ_ERR_BAD_ARG, "plane memory is NULL"); HIPCHK(hipSetDevice((m)->device))
+
+static constexpr int PM_WAVES = 4;                                   // wavefronts per workgroup: one sample / pair / group each
+static inline unsigned pm_grid(long long n) { return (unsigned)((n + PM_WAVES - 1) / PM_WAVES); }
+
+// ---- push: check the staged samples, then store them into the ring ----------------------------------------------------------------
+enum { PM_NONFINITE = 1, PM_NVIS = 2, PM_A01 = 3, PM_NOLEGAL = 4, PM_PNEG = 5, PM_PILLEGAL = 6 };
+// One wavefront per sample, lanes over the words.  bad = the smallest (sample << 3 | clause) that failed (k_ds_check's encoding).
+__global__ void __launch_bounds__(64 * PM_WAVES) k_pm_check(const float* __restrict__ X, const float* __restrict__ A, const double* __restrict__ P,
+                                                            const double* __restrict__ z, const double* __restrict__ t, const long long* __restrict__ nv,
+                                                            long long n, int xs, int nA, unsigned long long* __restrict__ bad) {
+  const int lane = threadIdx.x & 63;
+  const long long i = (long long)blockIdx.x * PM_WAVES + (threadIdx.x >> 6);
+  if (i >= n) return;
+  bool finite = true, a01 = true, pneg = false, pill = false, legal = false;
+  for (int w = lane; w < xs; w += 64) finite = finite && isfinite(X[(size_t)i * xs + w]);
+  for (int a = lane; a < nA; a += 64) {
+    const float m = A[(size_t)i * nA + a];
+    const double p = P[(size_t)i * nA + a];
+    finite = finite && isfinite(m) && isfinite((float)p);            // the data set holds Float32(pi)
+    a01 = a01 && (m == 0.0f || m == 1.0f);
+    legal = legal || m == 1.0f;
+    pneg = pneg || p < 0.0;
+    pill = pill || (p > 0.0 && m == 0.0f);
+  }
+  if (lane == 0) finite = finite && isfinite(z[i]) && isfinite(t[i]);
+  const bool nbad = nv && nv[i] < 1;
+  const int code = __ballot(!finite) ? PM_NONFINITE : nbad ? PM_NVIS : __ballot(!a01) ? PM_A01 : !__ballot(legal) ? PM_NOLEGAL
+                   : __ballot(pneg) ? PM_PNEG : __ballot(pill) ? PM_PILLEGAL : 0;
+  if (code && lane == 0) atomicMin(bad, ((unsigned long long)i << 3) | (unsigned long long)code);
+}
+// pushed sample j (j >= skip: the others would be overwritten within this very call) is staged sample (reverse ? n - 1 - j : j)
+// and lands in slot (total + j) % cap
+__global__ void __launch_bounds__(64 * PM_WAVES) k_pm_store(const float* __restrict__ X, const float* __restrict__ A, const double* __restrict__ P,
+                                                            const double* __restrict__ z, const double* __restrict__ t, const long long* __restrict__ nv,
+                                                            long long n, long long skip, int reverse, int xs, int nA, long long total, long long cap,
+                                                            float* __restrict__ XA, double* __restrict__ D, long long* __restrict__ N) {
+  const int lane = threadIdx.x & 63;
+  const long long j = skip + (long long)blockIdx.x * PM_WAVES + (threadIdx.x >> 6);
+  if (j >= n) return;
+  const size_t src = (size_t)(reverse ? n - 1 - j : j), slot = (size_t)((total + j) % cap);
+  const int RW = xs + nA, ND = nA + 2;
+  for (int w = lane; w < xs; w += 64) XA[slot * RW + w] = X[src * xs + w];
+  for (int a = lane; a < nA; a += 64) {
+    XA[slot * RW + xs + a] = A[src * nA + a];
+    D[slot * ND + a] = P[src * nA + a];
+  }
+  if (lane == 0) { D[slot * ND + nA] = z[src]; D[slot * ND + nA + 1] = t[src]; N[slot] = nv ? nv[src] : 1LL; }
+}
+
+// ---- merge_by_state over rows --------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long pm_fmix(unsigned long long h) {
+  h ^= h >> 33; h *= 0xff51afd7ed558ccdULL; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ULL; h ^= h >> 33;
+  return h;
+}
+// Row hash: lane l mixes words l, l + 64, ... (each with its position) into two 64-bit halves; a fixed shuffle tree folds the 64
+// lanes into lane 0 (the fold is not commutative, the tree has one shape: the key depends on the row alone).  Buffer index r is
+// sample (seq0 + r) of the ring.  bits < 128 truncates the key (az_debug_plane_memory_hash_bits).
+__global__ void __launch_bounds__(64 * PM_WAVES) k_pm_hash(const float* __restrict__ XA, long long cap, long long seq0, long long n, int RW, int bits,
+                                                           unsigned long long* __restrict__ k0, unsigned long long* __restrict__ k1,
+                                                           unsigned long long* __restrict__ k1_keep, unsigned int* __restrict__ idx) {
+  const int lane = threadIdx.x & 63;
+  const long long r = (long long)blockIdx.x * PM_WAVES + (threadIdx.x >> 6);
+  if (r >= n) return;
+  const unsigned int* row = (const unsigned int*)XA + (size_t)((seq0 + r) % cap) * RW;
+  unsigned long long a = 0x9e3779b97f4a7c15ULL + (unsigned long long)lane, b = 0xc2b2ae3d27d4eb4fULL ^ (unsigned long long)lane;
+  for (int w = lane; w < RW; w += 64) {
+    const unsigned long long v = row[w], p = (unsigned long long)(w + 1);
+    a = (a ^ (v | (p << 32))) * 0x9e3779b97f4a7c15ULL; a ^= a >> 29;
+    b = (b ^ ((v << 32) | p)) * 0xc2b2ae3d27d4eb4fULL; b ^= b >> 31;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long ta = __shfl_down(a, o), tb = __shfl_down(b, o);
+    a = pm_fmix(a * 0x87c37b91114253d5ULL + ta);
+    b = pm_fmix(b * 0x4cf5ad432745937fULL + tb);
+  }
+  if (lane == 0) {
+    if (bits < 64) { a &= (1ULL << bits) - 1ULL; b = 0ULL; }
+    else if (bits < 128) b &= (1ULL << (bits - 64)) - 1ULL;
+    k0[r] = a; k1[r] = b; k1_keep[r] = b; idx[r] = (unsigned int)r;
+  }
+}
+// Position i of the sorted order starts a group unless its row IS row i - 1's.  Keys that differ settle it without reading the
+// rows; equal keys are never believed: the wavefront compares every word.  Equal keys over different rows are a collision -- the
+// equal rows of either side may lie apart in the order, so the build is given up (a plain store of 1; every writer stores the same).
+__global__ void __launch_bounds__(64 * PM_WAVES) k_pm_heads(const float* __restrict__ XA, long long cap, long long seq0, long long n, int RW,
+                                                            const unsigned long long* __restrict__ k0, const unsigned long long* __restrict__ k1,
+                                                            const unsigned int* __restrict__ order, int* __restrict__ head, int* __restrict__ collision) {
+  const int lane = threadIdx.x & 63;
+  const long long i = (long long)blockIdx.x * PM_WAVES + (threadIdx.x >> 6);
+  if (i >= n) return;
+  if (i == 0) { if (lane == 0) head[0] = 1; return; }
+  const unsigned int ra = order[i], rb = order[i - 1];
+  if (k0[ra] != k0[rb] || k1[ra] != k1[rb]) { if (lane == 0) head[i] = 1; return; }
+  const unsigned int* a = (const unsigned int*)XA + (size_t)((seq0 + ra) % cap) * RW;
+  const unsigned int* b = (const unsigned int*)XA + (size_t)((seq0 + rb) % cap) * RW;
+  bool diff = false;
+  for (int w = lane; w < RW; w += 64) diff = diff || a[w] != b[w];
+  const bool differ = __ballot(diff) != 0ULL;
+  if (lane == 0) { head[i] = differ ? 1 : 0; if (differ) *collision = 1; }
+}
+static __global__ void k_pm_gather_u64(const unsigned long long* __restrict__ src, const unsigned int* __restrict__ idx, long long n, unsigned long long* __restrict__ dst) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = src[idx[i]];
+}
+// group s (1-based segid of its head, in key order): its first buffer index -- the sort is stable, so that is its head's -- is the
+// key of the sort that orders the output, its number the value; gpos[s] = where it starts in the key order
+__global__ void k_pm_groups(const int* __restrict__ head, const int* __restrict__ seg, const unsigned int* __restrict__ order, long long n,
+                            unsigned long long* __restrict__ gkey, unsigned int* __restrict__ gval, unsigned int* __restrict__ gpos) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || !head[i]) return;
+  const int s = seg[i] - 1;
+  gkey[s] = order[i]; gval[s] = (unsigned int)s; gpos[s] = (unsigned int)i;
+}
+// One wavefront per output row g = group gord[g], members order[gpos[s] .. gpos[s + 1]) in buffer order.  Lane l owns doubles l and
+// l + 64 of the ND = nA + 2 <= 128 (pi..., z, t): two named accumulators, no indexed private array.  Each sum STARTS with the first
+// member (keeps -0.0) and adds the others one by one, then divides by the count; n is summed by every lane alike.  X and A are the
+// first member's.  order == NULL: no merging, row g is buffer index g.
+__global__ void __launch_bounds__(64 * PM_WAVES) k_pm_merge(const float* __restrict__ XA, const double* __restrict__ D, const long long* __restrict__ N,
+                                                            long long cap, long long seq0, long long n, long long ngroups, int xs, int nA, int policy,
+                                                            const unsigned int* __restrict__ order, const unsigned int* __restrict__ gord,
+                                                            const unsigned int* __restrict__ gpos, float* __restrict__ W, float* __restrict__ X,
+                                                            float* __restrict__ A, float* __restrict__ P, float* __restrict__ V, long long* __restrict__ t_n) {
+  const int lane = threadIdx.x & 63;
+  const long long g = (long long)blockIdx.x * PM_WAVES + (threadIdx.x >> 6);
+  if (g >= ngroups) return;
+  const int RW = xs + nA, ND = nA + 2;
+  long long start = g, end = g + 1;
+  if (order) {
+    const long long s = gord[g];
+    start = gpos[s];
+    end = s + 1 < ngroups ? (long long)gpos[s + 1] : n;
+  }
+  const int j0 = lane, j1 = lane + 64;
+  const bool h0 = j0 < ND, h1 = j1 < ND;
+  const size_t first = (size_t)((seq0 + (order ? (long long)order[start] : start)) % cap);
+  double acc0 = h0 ? D[first * ND + j0] : 0.0, acc1 = h1 ? D[first * ND + j1] : 0.0;
+  long long nsum = N[first];
+#pragma unroll 4
+  for (long long m = start + 1; m < end; ++m) {
+    const size_t slot = (size_t)((seq0 + (long long)order[m]) % cap);
+    if (h0) acc0 += D[slot * ND + j0];
+    if (h1) acc1 += D[slot * ND + j1];
+    nsum += N[slot];
+  }
+  const double cnt = (double)(end - start);
+  acc0 = acc0 / cnt; acc1 = acc1 / cnt;
+  if (j0 < nA) P[(size_t)g * nA + j0] = (float)acc0;
+  if (j1 < nA) P[(size_t)g * nA + j1] = (float)acc1;
+  if (j0 == nA) V[g] = (float)acc0;
+  if (j1 == nA) V[g] = (float)acc1;
+  if (lane == 0) { W[g] = sample_weight(policy, nsum); t_n[g] = nsum; }
+  for (int w = lane; w < xs; w += 64) X[(size_t)g * xs + w] = XA[first * RW + w];
+  for (int a = lane; a < nA; a += 64) A[(size_t)g * nA + a] = XA[first * RW + xs + a];
+}
+
+// ---- the memory ----------------------------------------------------------------------------------------------------------------------
+extern "C" int az_plane_memory_create(int32_t game, int32_t device, int64_t capacity, az_plane_memory** out) {
+  if (!out) return fail(AZ_ERR_BAD_ARG, "NULL argument");
+  *out = nullptr;
+  GameInfo gi;
+  if (!game_info(game, &gi)) return fail(AZ_ERR_BAD_ARG, "unknown game id %d", game);
+  if (capacity < 1 || capacity > (1LL << 31) - 1) return fail(AZ_ERR_BAD_ARG, "capacity must be in 1..2^31-1");
+  if (gi.A + 2 > 128) return fail(AZ_ERR_BAD_ARG, "game id %d has more than 126 actions", game);   // k_pm_merge: two doubles per lane
+  int ndev = 0;
+  HIPCHK(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return fail(AZ_ERR_BAD_ARG, "device %d not available (%d visible)", device, ndev);
+  HIPCHK(hipSetDevice(device));
+  az_plane_memory* m = new (std::nothrow) az_plane_memory();
+  if (!m) return fail(AZ_ERR_HIP, "out of host memory");
+  m->game = game; m->device = device; m->gi = gi; m->stream = nullptr; m->d_XA = nullptr; m->d_D = nullptr; m->d_n = nullptr;
+  m->xs = gi.C * gi.P; m->nA = gi.A; m->RW = m->xs + m->nA; m->ND = m->nA + 2;
+  m->cap = capacity; m->total = 0; m->cur_batch = 0; m->hash_bits = 128;
+  int st = [&]() -> int {
+    HIPCHK(hipStreamCreate(&m->stream));
+    AZCHK(mem_alloc(nullptr, &m->d_XA, (size_t)capacity * m->RW));
+    AZCHK(mem_alloc(nullptr, &m->d_D, (size_t)capacity * m->ND));
+    AZCHK(mem_alloc(nullptr, &m->d_n, (size_t)capacity));
+    return AZ_OK;
+  }();
+  if (st != AZ_OK) { az_plane_memory_destroy(m); return st; }
+  *out = m;
+  return AZ_OK;
+}
+extern "C" int az_plane_memory_destroy(az_plane_memory* m) {
+  if (!m) return AZ_OK;
+  (void)hipSetDevice(m->device);
+  if (m->d_XA) (void)hipFree(m->d_XA);
+  if (m->d_D) (void)hipFree(m->d_D);
+  if (m->d_n) (void)hipFree(m->d_n);
+  if (m->stream) (void)hipStreamDestroy(m->stream);
+  delete m;
+  return AZ_OK;
+}
+extern "C" int az_plane_memory_length(az_plane_memory* m, int64_t* length, int64_t* cur_batch_size) {
+  PLANE_MEMORY(m);
+  const int64_t len = std::min<int64_t>(m->total, m->cap);
+  if (length) *length = len;
+  if (cur_batch_size) *cur_batch_size = std::min<int64_t>(m->cur_batch, len);     // memory.jl:53
+  return AZ_OK;
+}
+extern "C" int az_plane_memory_new_batch(az_plane_memory* m) { PLANE_MEMORY(m); m->cur_batch = 0; return AZ_OK; }
+extern "C" int az_plane_memory_empty(az_plane_memory* m) { PLANE_MEMORY(m); m->total = 0; m->cur_batch = 0; return AZ_OK; }
+extern "C" int az_debug_plane_memory_hash_bits(az_plane_memory* m, int32_t bits) {
+  PLANE_MEMORY(m);
+  if (bits < 1 || bits > 128) return fail(AZ_ERR_BAD_ARG, "hash bits must be in 1..128");
+  m->hash_bits = bits;
+  return AZ_OK;
+}
+
+// stage n host samples, check them, store them (reverse: the last staged sample is pushed first).  Nothing is pushed on failure.
+static int plane_push(az_plane_memory* m, int64_t n, const float* X, const float* A, const double* P, const double* z, const double* t,
+                      const int64_t* nvis, bool reverse) {
+  const size_t N = (size_t)n, xs = (size_t)m->xs, nA = (size_t)m->nA;
+  hipStream_t st = m->stream;
+  std::vector<void*> tmp;
+  int rc = [&]() -> int {
+    float *sX, *sA; double *sP, *sz, *stt; long long* sn = nullptr; unsigned long long* d_bad;
+    AZCHK(mem_alloc(&tmp, &sX, N * xs)); AZCHK(mem_alloc(&tmp, &sA, N * nA)); AZCHK(mem_alloc(&tmp, &sP, N * nA));
+    AZCHK(mem_alloc(&tmp, &sz, N)); AZCHK(mem_alloc(&tmp, &stt, N)); AZCHK(mem_alloc(&tmp, &d_bad, 1));
+    if (nvis) AZCHK(mem_alloc(&tmp, &sn, N));
+    HIPCHK(hipMemcpyAsync(sX, X, sizeof(float) * N * xs, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sA, A, sizeof(float) * N * nA, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sP, P, sizeof(double) * N * nA, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sz, z, sizeof(double) * N, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(stt, t, sizeof(double) * N, hipMemcpyHostToDevice, st));
+    if (nvis) HIPCHK(hipMemcpyAsync(sn, nvis, sizeof(long long) * N, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_bad, 0xff, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_pm_check, dim3(pm_grid(n)), dim3(64 * PM_WAVES), 0, st, sX, sA, sP, sz, stt, sn, (long long)n, m->xs, m->nA, d_bad);
+    unsigned long long bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    if (bad != ~0ull) {
+      static const char* const what[] = {"", "a non-finite value", "n < 1", "an entry of A outside {0, 1}", "no legal action (a row of A without a 1)",
+                                         "P < 0", "P > 0 where A == 0 (the loss takes the logarithm of the masked policy there)"};
+      return fail(AZ_ERR_BAD_ARG, "sample %lld: %s", (long long)(bad >> 3), what[bad & 7]);
+    }
+    const long long skip = std::max<long long>(0, n - m->cap);
+    hipLaunchKernelGGL(k_pm_store, dim3(pm_grid(n - skip)), dim3(64 * PM_WAVES), 0, st, sX, sA, sP, sz, stt, sn, (long long)n, skip, reverse ? 1 : 0,
+                       m->xs, m->nA, (long long)m->total, (long long)m->cap, m->d_XA, m->d_D, m->d_n);
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    return AZ_OK;
+  }();
+  for (void* p : tmp) (void)hipFree(p);
+  AZCHK(rc);
+  m->total += n;
+  return AZ_OK;
+}
+extern "C" int az_plane_memory_push_samples(az_plane_memory* m, int64_t n, const float* X, const float* A, const double* P, const double* z,
+                                            const double* t, const int64_t* nvis) {
+  PLANE_MEMORY(m);
+  if (n < 0 || n > (1LL << 31) - 1) return fail(AZ_ERR_BAD_ARG, "n must be in 0..2^31-1");
+  if (!n) return AZ_OK;
+  if (!X || !A || !P || !z || !t) return fail(AZ_ERR_BAD_ARG, "NULL array");
+  return plane_push(m, n, X, A, P, z, t, nvis, false);               // cur_batch_size is push_trace!'s to advance
+}
+extern "C" int az_plane_memory_push_trace(az_plane_memory* m, int32_t len, const float* X, const float* A, const double* P, const double* rewards,
+                                          const uint8_t* white_playing, double gamma) {
+  PLANE_MEMORY(m);
+  if (len < 0) return fail(AZ_ERR_BAD_ARG, "len must be >= 0");
+  if (!len) return AZ_OK;
+  if (!X || !A || !P || !rewards || !white_playing) return fail(AZ_ERR_BAD_ARG, "NULL array");
+  if (!std::isfinite(gamma)) return fail(AZ_ERR_BAD_ARG, "gamma is not finite");
+  std::vector<double> z((size_t)len), t((size_t)len);
+  double wr = 0.0;
+  for (int i = len - 1; i >= 0; --i) {                               // memory.jl:76-84
+    if (!std::isfinite(rewards[i])) return fail(AZ_ERR_BAD_ARG, "sample %d: a non-finite value", i);
+    wr = gamma * wr + rewards[i];
+    z[i] = white_playing[i] ? wr : -wr;
+    t[i] = (double)(len - i);
+  }
+  AZCHK(plane_push(m, len, X, A, P, z.data(), t.data(), nullptr, true));
+  m->cur_batch += len;                                               // mem.cur_batch_size += n, memory.jl:86
+  return AZ_OK;
+}
+
+// samples [first, first + count) of the buffer, oldest first, back to the host: at most two contiguous runs of the ring
+extern "C" int az_plane_memory_read(az_plane_memory* m, int64_t first, int64_t count, float* X, float* A, double* P, double* z, double* t, int64_t* nvis) {
+  PLANE_MEMORY(m);
+  const int64_t len = std::min<int64_t>(m->total, m->cap);
+  if (first < 0 || count < 0 || first + count > len) return fail(AZ_ERR_BAD_ARG, "range [%lld, %lld) outside the %lld samples", (long long)first, (long long)(first + count), (long long)len);
+  if (!count) return AZ_OK;
+  const size_t xs = (size_t)m->xs, nA = (size_t)m->nA, RW = (size_t)m->RW, ND = (size_t)m->ND;
+  std::vector<float> xa((size_t)count * RW);
+  std::vector<double> dd((size_t)count * ND);
+  int64_t seq = m->total - len + first, left = count, done = 0;
+  while (left > 0) {
+    const int64_t pos = seq % m->cap, run = std::min<int64_t>(left, m->cap - pos);
+    HIPCHK(hipMemcpyAsync(xa.data() + (size_t)done * RW, m->d_XA + (size_t)pos * RW, sizeof(float) * (size_t)run * RW, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(dd.data() + (size_t)done * ND, m->d_D + (size_t)pos * ND, sizeof(double) * (size_t)run * ND, hipMemcpyDeviceToHost, m->stream));
+    if (nvis) HIPCHK(hipMemcpyAsync(nvis + done, m->d_n + pos, sizeof(int64_t) * (size_t)run, hipMemcpyDeviceToHost, m->stream));
+    seq += run; left -= run; done += run;
+  }
+  HIPCHK(hipStreamSynchronize(m->stream));
+  for (size_t i = 0; i < (size_t)count; ++i) {
+    if (X) std::memcpy(X + i * xs, xa.data() + i * RW, sizeof(float) * xs);
+    if (A) std::memcpy(A + i * nA, xa.data() + i * RW + xs, sizeof(float) * nA);
+    if (P) std::memcpy(P + i * nA, dd.data() + i * ND, sizeof(double) * nA);
+    if (z) z[i] = dd[i * ND + nA];
+    if (t) t[i] = dd[i * ND + nA + 1];
+  }
+  return AZ_OK;
+}
+
+static int plane_dataset_build(az_plane_memory* m, az_dataset* d, int which, bool merge, int policy) {
+  const int64_t len = std::min<int64_t>(m->total, m->cap);
+  const int64_t n0 = which == 1 ? std::min<int64_t>(m->cur_batch, len) : len;
+  if (n0 < 1) return fail(AZ_ERR_STATE, which == 1 ? "the current batch is empty (push_trace advances it, new_batch resets it)" : "the plane memory is empty");
+  const long long seq0 = m->total - n0;                              // the newest n0 samples, oldest first
+  const int xs = m->xs, nA = m->nA;
+  std::vector<void*> tmp;
+  int rc = [&]() -> int {
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipStreamCreate(&d->stream));
+    hipStream_t st = d->stream;
+    unsigned int *order = nullptr, *gord = nullptr, *gpos = nullptr;
+    int64_t n2 = n0;
+    if (merge) {
+      unsigned long long *k0, *k1, *k1keep, *ks, *ks2, *gkey, *gks; unsigned int *i0, *i1, *i2, *gval; int *head, *seg, *stmp, *coll;
+      const size_t N = (size_t)n0;
+      AZCHK(mem_alloc(&tmp, &k0, N)); AZCHK(mem_alloc(&tmp, &k1, N)); AZCHK(mem_alloc(&tmp, &k1keep, N)); AZCHK(mem_alloc(&tmp, &ks, N)); AZCHK(mem_alloc(&tmp, &ks2, N));
+      AZCHK(mem_alloc(&tmp, &i0, N)); AZCHK(mem_alloc(&tmp, &i1, N)); AZCHK(mem_alloc(&tmp, &i2, N));
+      AZCHK(mem_alloc(&tmp, &head, N)); AZCHK(mem_alloc(&tmp, &seg, N)); AZCHK(mem_alloc(&tmp, &coll, 1));
+      AZCHK(mem_alloc(&tmp, &stmp, std::max(prims::sort_tmp_ints(n0), prims::scan_tmp_ints(n0))));
+      const unsigned gb = (unsigned)((n0 + 255) / 256);
+      HIPCHK(hipMemsetAsync(coll, 0, sizeof(int), st));
+      hipLaunchKernelGGL(k_pm_hash, dim3(pm_grid(n0)), dim3(64 * PM_WAVES), 0, st, m->d_XA, (long long)m->cap, seq0, (long long)n0, m->RW, m->hash_bits, k0, k1, k1keep, i0);
+      // LSD as dataset_build (memory.hip): stable by k1, then by k0 -> ascending (k0, k1, buffer index)
+      HIPCHK(prims::sort_pairs(k1, ks, i0, i1, n0, stmp, st));
+      hipLaunchKernelGGL(k_pm_gather_u64, dim3(gb), dim3(256), 0, st, k0, i1, (long long)n0, ks2);
+      HIPCHK(prims::sort_pairs(ks2, ks, i1, i2, n0, stmp, st));
+      hipLaunchKernelGGL(k_pm_heads, dim3(pm_grid(n0)), dim3(64 * PM_WAVES), 0, st, m->d_XA, (long long)m->cap, seq0, (long long)n0, m->RW, k0, k1keep, i2, head, coll);
+      HIPCHK(prims::scan_ints(head, seg, n0, true, stmp, st));
+      int nseg = 0, collision = 0;
+      HIPCHK(hipMemcpyAsync(&nseg, seg + (n0 - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(&collision, coll, sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(hipGetLastError());
+      if (collision) return fail(AZ_ERR_STATE, "plane hash collision: two different (X, A) rows share their %d-bit key; no data set was built", m->hash_bits);
+      n2 = nseg;
+      const size_t G = (size_t)n2;
+      AZCHK(mem_alloc(&tmp, &gkey, G)); AZCHK(mem_alloc(&tmp, &gks, G)); AZCHK(mem_alloc(&tmp, &gval, G)); AZCHK(mem_alloc(&tmp, &gord, G)); AZCHK(mem_alloc(&tmp, &gpos, G));
+      hipLaunchKernelGGL(k_pm_groups, dim3(gb), dim3(256), 0, st, head, seg, i2, (long long)n0, gkey, gval, gpos);
+      HIPCHK(prims::sort_pairs(gkey, gks, gval, gord, n2, stmp, st));   // n2 <= n0: stmp is large enough
+      order = i2;
+    }
+    d->n = n2;
+    const size_t G = (size_t)n2;
+    AZCHK(mem_alloc(&d->allocs, &d->d_W, G)); AZCHK(mem_alloc(&d->allocs, &d->d_V, G));
+    AZCHK(mem_alloc(&d->allocs, &d->d_A, G * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_P, G * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_X, G * xs));
+    long long *tn, *tsum;
+    AZCHK(mem_alloc(&tmp, &tn, G)); AZCHK(mem_alloc(&tmp, &tsum, prims::sum_tmp_doubles(n2)));
+    hipLaunchKernelGGL(k_pm_merge, dim3(pm_grid(n2)), dim3(64 * PM_WAVES), 0, st, m->d_XA, m->d_D, m->d_n, (long long)m->cap, seq0, (long long)n0, (long long)n2,
+                       xs, nA, policy, order, gord, gpos, d->d_W, d->d_X, d->d_A, d->d_P, d->d_V, tn);
+    long long* d_sn = nullptr; long long sn = 0;
+    HIPCHK(prims::sum_values<long long>(tn, n2, tsum, &d_sn, st));    // sum(e.n) is an Int: exact
+    HIPCHK(hipMemcpyAsync(&sn, d_sn, sizeof sn, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    d->sum_n = (int64_t)sn;
+    AZCHK(dataset_tensor_stats(d, st));                              // Wtot, Wmean, Hp as az_dataset_create_from_tensors computes them
+    return AZ_OK;
+  }();
+  for (void* p : tmp) (void)hipFree(p);
+  return rc;
+}
+extern "C" int az_dataset_create_from_plane_memory(az_plane_memory* m, int32_t which, int32_t use_position_averaging, int32_t weighing_policy,
+                                                   az_dataset** out) {
+  PLANE_MEMORY(m);
+  if (!out) return fail(AZ_ERR_BAD_ARG, "NULL argument");
+  *out = nullptr;
+  if (which != 0 && which != 1) return fail(AZ_ERR_BAD_ARG, "which must be 0 (get_experience) or 1 (last_batch)");
+  if (weighing_policy < AZ_WEIGHT_CONSTANT || weighing_policy > AZ_WEIGHT_LINEAR) return fail(AZ_ERR_BAD_ARG, "unknown samples_weighing_policy %d", weighing_policy);
+  az_dataset* d = new (std::nothrow) az_dataset();
+  if (!d) return fail(AZ_ERR_HIP, "out of host memory");
+  d->game = m->game; d->device = m->device; d->gi = m->gi; d->stream = nullptr; d->own_stream = true; d->n = 0; d->sum_n = 0;
+  d->Wtot = 0.0; d->Wmean = 0.f; d->Hp = 0.f; d->d_samples = nullptr; d->d_envs = nullptr;
+  d->d_W = d->d_X = d->d_A = d->d_P = d->d_V = nullptr;
+  const int st = plane_dataset_build(m, d, which, use_position_averaging != 0, weighing_policy);
+  if (st != AZ_OK) { az_dataset_destroy(d); return st; }
+  *out = d;
+  return AZ_OK;
+}

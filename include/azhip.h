@@ -72,9 +72,9 @@ typedef enum {
   AZ_GAME_CONNECT_FOUR = 0, AZ_GAME_TICTACTOE = 1, AZ_GAME_MANCALA = 2,
   /* Network-only tensor geometry, no device twin: GI.state_dim = (9, 9, 4), 82 actions -- OpenSpiel 9x9 Go through
    * src/openspiel.jl (BASELINE configs[4]).  Rules and tree stay on the host; the engine serves az_net_set_params /
-   * az_net_forward (Network.forward_normalized) for it, trains it on a data set made from tensors
-   * (az_dataset_create_from_tensors, az_trainer_*, az_learning_status) and rejects every search, game, key-based and
-   * replay-memory entry point. */
+   * az_net_forward (Network.forward_normalized) for it, keeps its samples in a replay memory of planes (az_plane_memory_*), trains it on a
+   * data set made from that memory or from tensors (az_dataset_create_from_plane_memory, az_dataset_create_from_tensors, az_trainer_*,
+   * az_learning_status) and rejects every search, game, key-based and keyed replay-memory (az_memory_*) entry point. */
   AZ_GAME_GO9_PLANES = 3
 } az_game_id;
 
@@ -497,8 +497,8 @@ int az_memory_empty(az_memory* m);                                              
 int az_dataset_create(az_memory* m, int32_t which, int32_t use_symmetries, int32_t use_position_averaging,
                       int32_t weighing_policy, az_dataset** out);
 /* The data of a Trainer from tensors the caller converted itself (convert_samples, src/learning.jl:17-51): a host that steps its own
- * game -- any GameInterface game of a supported geometry, AZ_GAME_GO9_PLANES included, which has no replay memory here -- or one that
- * labels positions by other means.  Host arrays, sample index first: W [n], X [n][C][H][W] (the layout of az_net_forward), A [n][nA],
+ * game and keeps its samples itself -- any GameInterface game of a supported geometry, AZ_GAME_GO9_PLANES included; az_plane_memory below
+ * keeps them on the device instead -- or one that labels positions by other means.  Host arrays, sample index first: W [n], X [n][C][H][W] (the layout of az_net_forward), A [n][nA],
  * P [n][nA], V [n] (the layouts az_dataset_read writes).  AZ_ERR_BAD_ARG with the first offending sample in az_last_error() for n < 1,
  * a NULL pointer, a non-finite value, W <= 0, an entry of A outside {0, 1}, a row of A without a legal action, P < 0, or P > 0 where
  * A == 0 (the loss takes the logarithm of the masked network policy there).  Wtot, Wmean and Hp = entropy_wmean(P, W)
@@ -524,6 +524,54 @@ typedef struct { float L, Lp, Lv, Lreg, Linv, Hp, Hpnet; } az_learning_status_t;
 int az_learning_status(az_engine* e, az_dataset* d, double l2_regularization, double nonvalidity_penalty,
                        double rewards_renormalization, int64_t loss_computation_batch_size, az_learning_status_t* out);
 
+/* ---- replay memory of plane samples: MemoryBuffer (src/memory.jl) for a host-stepped game ----------------------------------
+ * az_memory stores state keys and re-encodes them with the game's device twin.  A game whose rules live on the host -- any
+ * GameInterface game of a supported geometry, AZ_GAME_GO9_PLANES above all -- has no twin, so this memory stores what the host can
+ * give: per sample the planes X [C][H][W] (Float32, the layout of az_net_forward) and the mask A [nA] (Float32 in {0, 1}) the
+ * network sees, pi [nA] (Float64, by FULL action index), z, t (Float64) and n (Int64).  A circular buffer in HBM with
+ * MemoryBuffer's semantics (memory.jl:35-65): a push over capacity overwrites the oldest sample, cur_batch_size = min(samples
+ * pushed by push_trace since new_batch, length).  All four geometries are accepted.
+ *   state identity       The device never sees the host's state: two samples are ONE state when their (X, A) rows are bit-identical
+ *                        (0.0 and -0.0 differ), which is what the network can tell apart.  For a game whose vectorize_state is
+ *                        injective this is merge_by_state's grouping (memory.jl:98-112); otherwise it groups more.
+ *   merging              pi, z, t of a merged row are the sums over its samples, accumulated one by one in buffer order in Float64
+ *                        starting from the first, divided by the count (the order az_dataset_create keeps); n is the sum.  Rows
+ *                        come out in the order of each state's first occurrence in the buffer (the reference's values(dict) order
+ *                        is unspecified); without merging in buffer order.
+ *   hashing              Rows are brought together by a 128-bit hash and then compared word by word; a hash never decides that
+ *                        two rows are equal.  Two different rows with one hash make the call fail with AZ_ERR_STATE ("plane hash
+ *                        collision"); rows are never merged wrongly or split silently.
+ *   convert_samples      (learning.jl:17-51) W from n by the weighing policy as az_dataset_create computes it, X / A the first
+ *                        sample's of the state, P = Float32(pi), V = Float32(z).  t stays in the memory: a data set does not carry it. */
+typedef struct az_plane_memory az_plane_memory;
+int az_plane_memory_create(int32_t game, int32_t device, int64_t capacity, az_plane_memory** out);   /* capacity 1..2^31-1 */
+int az_plane_memory_destroy(az_plane_memory* m);
+/* push!(mem.buf, e) for n samples on the host, sample index first: X [n][C][H][W], A [n][nA], P [n][nA] (= pi), z [n], t [n], nvis [n]
+ * (= n of each sample; NULL: 1).  Does not advance cur_batch_size (as az_memory_push_samples).  Checked on the device before
+ * anything is stored: AZ_ERR_BAD_ARG with the first offending sample in az_last_error() for a non-finite value, nvis < 1, an entry
+ * of A outside {0, 1}, a row of A without a legal action, P < 0, or P > 0 where A == 0; the memory is then unchanged.  n = 0 is AZ_OK. */
+int az_plane_memory_push_samples(az_plane_memory* m, int64_t n, const float* X, const float* A, const double* P, const double* z,
+                                 const double* t, const int64_t* nvis);
+/* push_trace!(mem, trace, gamma) (memory.jl:74-87) for ONE game of len positions in playing order: rewards[i] is white's reward
+ * after move i, white_playing[i] != 0 where white is to move in position i.  Samples are pushed for i = len .. 1 (counted from 1), in
+ * that order: wr = gamma * wr + rewards[i], z = white_playing[i] ? wr : -wr, t = len - i + 1, n = 1; cur_batch_size += len.  The
+ * checks of az_plane_memory_push_samples apply (sample = position, counted from 0), rewards and gamma must be finite. */
+int az_plane_memory_push_trace(az_plane_memory* m, int32_t len, const float* X, const float* A, const double* P, const double* rewards,
+                               const uint8_t* white_playing, double gamma);
+/* Samples [first, first + count) of the buffer, oldest first, to host arrays in the layouts of az_plane_memory_push_samples (any
+ * pointer may be NULL): what get_experience returns, e.g. to slice the samples by t (memory_report) or to save the memory. */
+int az_plane_memory_read(az_plane_memory* m, int64_t first, int64_t count, float* X, float* A, double* P, double* z, double* t, int64_t* nvis);
+int az_plane_memory_length(az_plane_memory* m, int64_t* length, int64_t* cur_batch_size);   /* length, cur_batch_size (:53-59) */
+int az_plane_memory_new_batch(az_plane_memory* m);                                            /* new_batch! (:55) */
+int az_plane_memory_empty(az_plane_memory* m);                                                /* empty! (:57-60) */
+/* The data of a Trainer from the memory, built on the device: which = 0 get_experience / 1 last_batch, use_position_averaging =
+ * merge_by_state over rows ("state identity", "merging" above), convert_samples with the weighing policy.  The result is the kind of
+ * data set az_dataset_create_from_tensors makes (no az_sample records; Wtot, Wmean and Hp computed by the same code) and owns its
+ * memory: the az_plane_memory may be pushed to or destroyed afterwards.  num_samples = rows after merging, sum_n = sum of n.
+ * AZ_ERR_STATE when there is no sample to take (an empty memory; which = 1 with an empty batch) and for a hash collision. */
+int az_dataset_create_from_plane_memory(az_plane_memory* m, int32_t which, int32_t use_position_averaging, int32_t weighing_policy,
+                                        az_dataset** out);
+
 /* ---- the optimiser step (src/learning.jl:123-141, src/networks/flux.jl:68-95) --------------- */
 typedef struct az_trainer az_trainer;   /* Trainer (src/learning.jl:98-121): network in train mode + optimiser state */
 typedef enum { AZ_OPT_ADAM = 0, AZ_OPT_CYCLIC_NESTEROV = 1 } az_optimiser;   /* src/networks/network.jl:163-190 */
@@ -539,8 +587,8 @@ typedef struct {
 } az_train_cfg;
 int az_train_cfg_init(az_train_cfg* cfg);
 /* Trainer(gspec, network, samples, params): the engine supplies the architecture and the initial parameters, the
- * data set (az_dataset_create or az_dataset_create_from_tensors) the converted samples, Wmean and Hp.  All four network
- * geometries train, AZ_GAME_GO9_PLANES through a data set made from tensors.  The engine's own network is not modified:
+ * data set (az_dataset_create, az_dataset_create_from_tensors or az_dataset_create_from_plane_memory) the converted samples, Wmean
+ * and Hp.  All four network geometries train, AZ_GAME_GO9_PLANES through a data set made from tensors or from a plane memory.  The engine's own network is not modified:
  * fetch the result with az_trainer_get_params and install it with az_net_set_params.  The engine and the data set
  * must outlive the trainer. */
 int az_trainer_create(az_engine* e, az_dataset* d, const az_train_cfg* cfg, az_trainer** out);

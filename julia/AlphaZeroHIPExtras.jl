@@ -272,5 +272,17 @@ const UNBOUND = Dict(
   :az_solver_table_clear => "see az_solver_table_create",
   :az_solver_table_info => "see az_solver_table_create",
   :az_c4_solve_table => "takes az_solver_cfg by reference, as az_c4_solve: no static ccall rule for that record yet; the Pons benchmark runs through the Python host",
+  # the replay memory of plane samples serves hosts that step their own game over the C ABI or from Python (azhip.PlaneMemoryBuffer).  A Julia
+  # host of such a game runs the reference's own MemoryBuffer, merge_by_state and convert_samples and hands the tensors to
+  # az_dataset_create_from_tensors (bound above); az_plane_memory is also a handle tests/test_julia_glue_static.py has no ccall rule for
+  :az_plane_memory_create => "az_plane_memory is a handle type without a static ccall rule; a Julia host keeps the reference's MemoryBuffer (see the note above)",
+  :az_plane_memory_destroy => "see az_plane_memory_create",
+  :az_plane_memory_push_samples => "see az_plane_memory_create; takes the per-sample n as const int64_t*, another type without a ccall rule",
+  :az_plane_memory_push_trace => "see az_plane_memory_create; the reference's push_trace! serves a Julia host",
+  :az_plane_memory_read => "see az_plane_memory_create",
+  :az_plane_memory_length => "see az_plane_memory_create",
+  :az_plane_memory_new_batch => "see az_plane_memory_create",
+  :az_plane_memory_empty => "see az_plane_memory_create",
+  :az_dataset_create_from_plane_memory => "builds from an az_plane_memory, which is unbound (see az_plane_memory_create)",
 )
 

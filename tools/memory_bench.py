@@ -1,5 +1,9 @@
 """Time the device replay-memory path at scale: push_trace! of a self-play phase, the Trainer's data set
-(symmetries + merge_by_state + convert_samples) and learning_status (5x64 ResNet, test mode)."""
+(symmetries + merge_by_state + convert_samples) and learning_status (5x64 ResNet, test mode).
+
+--planes: the replay memory of a host-stepped game instead (azhip.PlaneMemoryBuffer, 9x9x4 Go geometry, about 30 % repeated
+positions): az_dataset_create_from_plane_memory (merged, LOG_WEIGHT) against what a host without it does for the same samples -- a
+numpy merge_by_state + convert_samples, then az_dataset_create_from_tensors with its upload -- in the same run; --out writes both as JSON."""
 import argparse
 import os
 import sys
@@ -12,7 +16,90 @@ import azhip  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--games", type=int, default=16384)
 ap.add_argument("--filters", type=int, default=64)
+ap.add_argument("--planes", action="store_true")
+ap.add_argument("--samples", type=int, default=1 << 20)
+ap.add_argument("--out", default=None)
 a = ap.parse_args()
+
+
+def host_merge_convert(X, A, P, z, nv):
+    """what a host does today: merge_by_state over the (X, A) rows and convert_samples (LOG_WEIGHT), vectorised numpy.  Rows are
+    grouped by a 64-bit multiply-add hash and the grouping is verified word by word; sums run in buffer order (np.add.at)."""
+    import numpy as np
+    n = len(z)
+    rows = np.concatenate([X.reshape(n, -1), A], axis=1).view(np.uint32)
+    mult = np.random.default_rng(0).integers(1, 1 << 63, rows.shape[1], dtype=np.uint64) | np.uint64(1)
+    h = np.concatenate([(rows[k:k + 65536].astype(np.uint64) * mult).sum(axis=1, dtype=np.uint64) for k in range(0, n, 65536)])
+    _, first, inv = np.unique(h, return_index=True, return_inverse=True)
+    assert np.array_equal(rows, rows[first][inv]), "hash collision"
+    order = np.argsort(first, kind="stable")                                  # groups in order of first occurrence
+    rank = np.empty_like(order)
+    rank[order] = np.arange(len(order))
+    g = rank[inv]
+    cnt = np.bincount(g, minlength=len(order)).astype(np.float64)
+    pi = np.zeros((len(order), P.shape[1]))
+    zs = np.zeros(len(order))
+    ns = np.zeros(len(order), dtype=np.int64)
+    np.add.at(pi, g, P)
+    np.add.at(zs, g, z)
+    np.add.at(ns, g, nv)
+    f = first[order]
+    W = (np.log2(ns.astype(np.float64)) + 1.0).astype(np.float32)
+    return W, X[f], A[f], (pi / cnt[:, None]).astype(np.float32), (zs / cnt).astype(np.float32)
+
+
+def planes_bench():
+    import json
+    import numpy as np
+    gspec = azhip.Go9PlanesSpec()
+    n = a.samples
+    rng = np.random.default_rng(1)
+    X = rng.integers(0, 2, size=(n, 4, 9, 9), dtype=np.uint8).astype(np.float32)
+    A = (rng.random((n, 82), dtype=np.float32) < 0.6).astype(np.float32)
+    A[:, 81] = 1.0
+    dup = rng.permutation(n)[:int(0.3 * n)]                                   # these samples repeat an earlier (or later) position
+    src = rng.integers(0, n, len(dup))
+    X[dup], A[dup] = X[src], A[src]
+    P = rng.random((n, 82)) * A
+    P /= P.sum(axis=1, keepdims=True)
+    z, t, nv = rng.uniform(-1, 1, n), rng.integers(1, 80, n).astype(np.float64), np.ones(n, dtype=np.int64)
+    mem = azhip.PlaneMemoryBuffer(gspec, n)
+    t0 = time.perf_counter()
+    mem.push_samples(X, A, P, z, t, nv)
+    push_ms = 1e3 * (time.perf_counter() - t0)
+    dev_ms = []
+    for _ in range(4):
+        t0 = time.perf_counter()
+        d = mem.dataset(use_position_averaging=True, weighing_policy=azhip.LOG_WEIGHT)
+        dev_ms.append(1e3 * (time.perf_counter() - t0))
+        rows, info = len(d), (d.sum_n, d.Wtot, d.Hp)
+        d.close()
+    host = []
+    for _ in range(2):
+        t0 = time.perf_counter()
+        tensors = host_merge_convert(X, A, P, z, nv)
+        t1 = time.perf_counter()
+        td = azhip.TensorDataset(gspec, *tensors)
+        t2 = time.perf_counter()
+        host.append((1e3 * (t1 - t0), 1e3 * (t2 - t1)))
+        assert len(td) == rows and td.sum_n == rows and abs(td.Wtot - info[1]) <= 1e-6 * info[1], (len(td), rows, td.Wtot, info)
+        td.close()
+    res = {"samples": n, "merged_rows": rows, "geometry": "9x9x4, 82 actions", "weighing_policy": "LOG_WEIGHT",
+           "device_dataset_build_ms": [round(x, 2) for x in dev_ms], "device_dataset_build_ms_best_after_first": round(min(dev_ms[1:]), 2),
+           "push_samples_ms_incl_upload": round(push_ms, 1),
+           "host_numpy_merge_convert_ms": [round(h[0], 1) for h in host], "host_create_from_tensors_ms_incl_upload": [round(h[1], 1) for h in host],
+           "host_path_ms_best": round(min(h[0] + h[1] for h in host), 1)}
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+if a.planes:
+    planes_bench()
+    sys.exit(0)
 gspec = azhip.ConnectFourSpec()
 with azhip.Engine(game=0, oracle=azhip.ORACLE_HASH, num_workers=4096, batch_size=4096, num_iters_per_turn=8, reset_every=1,
                   dirichlet_noise_eps=0.25, cpuct=1.0, temperature=([0], [1.0])) as e:
