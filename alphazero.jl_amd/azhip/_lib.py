@@ -86,6 +86,7 @@ class LearningStatusRec(C.Structure):
 
 
 WEIGHT_CONSTANT, WEIGHT_LOG, WEIGHT_LINEAR = 0, 1, 2
+PLANE_MAX_SYMMETRIES = 15    # AZ_PLANE_MAX_SYMMETRIES
 OPT_ADAM, OPT_CYCLIC_NESTEROV = 0, 1
 
 
@@ -175,6 +176,9 @@ SYMBOLS = {
     "az_plane_memory_new_batch": [_VP],
     "az_plane_memory_empty": [_VP],
     "az_dataset_create_from_plane_memory": [_VP, _I32, _I32, _I32, C.POINTER(_VP)],
+    "az_plane_memory_set_symmetries": [_VP, _I32, _VP, _VP],
+    "az_plane_memory_num_symmetries": [_VP, C.POINTER(_I32)],
+    "az_dataset_create_from_plane_memory_sym": [_VP, _I32, _I32, _I32, _I32, C.POINTER(_VP)],
     "az_dataset_destroy": [_VP],
     "az_dataset_get_info": [_VP, C.POINTER(DatasetInfo)],
     "az_dataset_read": [_VP, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _VP],

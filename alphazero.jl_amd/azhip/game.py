@@ -99,6 +99,44 @@ def spec_of_game_id(game_id):
     raise ValueError("unknown game id %r" % (game_id,))
 
 
+def _dihedral_src(k, p, n):
+    """the cell whose content image k has at cell p = y * n + x of an n x n board: the 7 non-trivial dihedral maps in the reference's
+    order (rot, rot2, rot3, flip, flip.rot, flip.rot2, flip.rot3; games/tictactoe/game.jl:149-168), rot(x, y) = (y, n-1-x),
+    flip(x, y) = (x, n-1-y), 0-based -- TicTacToe::sym_src of csrc/games.h for any n"""
+    x, y = p % n, p // n
+    for _ in range(k + 1 if k < 3 else k - 3):
+        x, y = y, n - 1 - x
+    if k >= 3:
+        y = n - 1 - y
+    return y * n + x
+
+
+def plane_symmetries(gspec):
+    """GI.symmetries(gspec) as the gather tables PlaneMemoryBuffer.set_symmetries takes: (xperm (nsym, C*H*W), aperm (nsym, num_actions)),
+    int32, with X'[w] = X[xperm[k][w]], A'[j] = A[aperm[k][j]], π'[j] = π[aperm[k][j]].
+
+    They assume the encodings of this package: X is (C, H, W), word c*H*W + y*W + x is plane c at column x of row y, and every plane is
+    a picture of the board (a symmetry moves all planes alike).
+      Tic-tac-toe    the 7 non-trivial dihedral maps in the reference's order; action j is cell j = y*3 + x
+      Connect Four   the column mirror x -> 6 - x; action a is column a, so a -> 6 - a
+      Go9PlanesSpec  the same 7 maps on the cell p = y*9 + x of the 9 x 9 board; action p < 81 plays cell p and moves with it, the
+                     pass action 81 is fixed.  A host whose planes or actions are indexed otherwise builds its own tables
+      Mancala        none (the reference declares none): empty tables"""
+    nA = gspec.num_actions()
+    w, h, c = gspec.state_dim()
+    gid = gspec.game_id
+    if gid in (L.GAME_TICTACTOE, L.GAME_GO9_PLANES):
+        cell = np.array([[_dihedral_src(k, p, w) for p in range(w * h)] for k in range(7)], dtype=np.int32)
+        aperm = np.concatenate([cell, np.tile(np.arange(w * h, nA, dtype=np.int32), (7, 1))], axis=1)
+    elif gid == L.GAME_CONNECT_FOUR:
+        cell = np.array([[y * w + (w - 1 - x) for y in range(h) for x in range(w)]], dtype=np.int32)
+        aperm = np.arange(nA - 1, -1, -1, dtype=np.int32)[None, :]
+    else:
+        return np.zeros((0, c * h * w), dtype=np.int32), np.zeros((0, nA), dtype=np.int32)
+    xperm = np.concatenate([cell + k * w * h for k in range(c)], axis=1)
+    return np.ascontiguousarray(xperm, dtype=np.int32), np.ascontiguousarray(aperm, dtype=np.int32)
+
+
 class GameEnv:
     """AbstractGameEnv (game.jl:77-175)."""
 

@@ -8,7 +8,7 @@ from dataclasses import dataclass
 
 from . import _lib as L
 from .engine import Engine
-from .memory import Dataset, MemoryBuffer, TensorDataset
+from .memory import Dataset, MemoryBuffer, PlaneMemoryBuffer, TensorDataset
 
 CONSTANT_WEIGHT, LOG_WEIGHT, LINEAR_WEIGHT = L.WEIGHT_CONSTANT, L.WEIGHT_LOG, L.WEIGHT_LINEAR
 
@@ -79,7 +79,10 @@ class Trainer:
 
     `mem` may also be a TensorDataset: samples the caller converted itself (the only way for the 9x9x4 geometry).  The trainer then
     takes them as they are -- use_symmetries, last_batch and params.use_position_averaging act on a memory's samples and are an
-    error with tensors -- and does not own the data set: the caller closes it."""
+    error with tensors -- and does not own the data set: the caller closes it.
+
+    A PlaneMemoryBuffer (the replay memory of a host-stepped game) is a memory like MemoryBuffer: the trainer builds its data set
+    through mem.dataset(...) -- use_symmetries over the symmetries declared with set_symmetries -- and owns it."""
 
     def __init__(self, gspec, network, mem, params: LearningParams, use_symmetries=False, last_batch=False, device=0):
         self.gspec, self.params = gspec, params
@@ -91,6 +94,11 @@ class Trainer:
             if mem.gspec != gspec:
                 raise ValueError("the TensorDataset was made for %s" % type(mem.gspec).__name__)
             self.data = mem
+        elif isinstance(mem, PlaneMemoryBuffer):
+            if mem.gspec != gspec:
+                raise ValueError("the PlaneMemoryBuffer was made for %s" % type(mem.gspec).__name__)
+            self.data = mem.dataset(last_batch=last_batch, use_symmetries=use_symmetries, use_position_averaging=params.use_position_averaging,
+                                    weighing_policy=params.samples_weighing_policy)
         else:
             self.data = Dataset(mem, last_batch, use_symmetries, params.use_position_averaging, params.samples_weighing_policy)
         self.Wmean, self.Hp = self.data.Wmean, self.data.Hp

@@ -361,12 +361,36 @@ class PlaneMemoryBuffer:
     def empty(self):
         _L.check(_L.lib().az_plane_memory_empty(self._h))
 
+    def set_symmetries(self, xperm, aperm):
+        """GI.symmetries of the host's game, declared once (they belong to the game, not to the samples): nsym gather permutations
+        xperm (nsym, C*H*W) over the words of a sample's planes and aperm (nsym, num_actions) over the actions,
+        X'[w] = X[xperm[k][w]], A'[j] = A[aperm[k][j]], π'[j] = π[aperm[k][j]].  plane_symmetries(gspec) has the tables of the shipped
+        geometries.  Empty tables (nsym = 0) clear the set; a row that is not a bijection is refused and the old set stays."""
+        nA = self.gspec.num_actions()
+        w, h, c = self.gspec.state_dim()
+        xperm = np.ascontiguousarray(xperm, dtype=np.int32)
+        aperm = np.ascontiguousarray(aperm, dtype=np.int32)
+        nsym = xperm.shape[0] if xperm.ndim else -1
+        if xperm.shape != (nsym, c * h * w):
+            raise ValueError("xperm must have shape (nsym, %d), got %s" % (c * h * w, xperm.shape))
+        if aperm.shape != (nsym, nA):
+            raise ValueError("aperm must have shape (%d, %d), got %s" % (nsym, nA, aperm.shape))
+        vp = lambda a: a.ctypes.data_as(_C.c_void_p) if a.size else None
+        _L.check(_L.lib().az_plane_memory_set_symmetries(self._h, nsym, vp(xperm), vp(aperm)))
+
+    @property
+    def num_symmetries(self):
+        k = _C.c_int32()
+        _L.check(_L.lib().az_plane_memory_num_symmetries(self._h, _C.byref(k)))
+        return k.value
+
     def dataset(self, last_batch=False, use_symmetries=False, use_position_averaging=False, weighing_policy=_L.WEIGHT_CONSTANT):
-        """get_experience / last_batch -> merge_by_state -> convert_samples on the device; the caller closes the TensorDataset"""
-        if use_symmetries:
-            raise ValueError("use_symmetries needs the game's symmetries, which live on the host: push the symmetric images "
-                             "(planes, mask and π of each) as samples of their own")
+        """get_experience / last_batch -> augment_with_symmetries (over the declared symmetries, images never stored) -> merge_by_state
+        -> convert_samples on the device; the caller closes the TensorDataset"""
+        if use_symmetries and self.num_symmetries == 0:
+            raise ValueError("use_symmetries needs the game's symmetries, which live on the host: declare them once with "
+                             "set_symmetries (plane_symmetries(gspec) has those of the shipped geometries)")
         h = _C.c_void_p()
-        _L.check(_L.lib().az_dataset_create_from_plane_memory(self._h, 1 if last_batch else 0, 1 if use_position_averaging else 0,
-                                                              int(weighing_policy), _C.byref(h)))
+        _L.check(_L.lib().az_dataset_create_from_plane_memory_sym(self._h, 1 if last_batch else 0, 1 if use_symmetries else 0,
+                                                                  1 if use_position_averaging else 0, int(weighing_policy), _C.byref(h)))
         return TensorDataset._adopt(self.gspec, h)

@@ -344,6 +344,10 @@ struct az_plane_memory {
   long long* d_n;                    // [cap]
   int64_t cap, total, cur_batch;     // as az_memory
   int hash_bits;                     // 128; az_debug_plane_memory_hash_bits lowers it
+  // GI.symmetries as the host declared them (az_plane_memory_set_symmetries): symmetry k as ONE gather over the row's RW words,
+  // perm[k][w] = xperm[k][w] for w < xs, xs + aperm[k][w - xs] after; 16 bits hold an index below RW <= xs + 126
+  int nsym;                          // 0: none declared
+  unsigned short* d_perm;            // [AZ_PLANE_MAX_SYMMETRIES][RW], rows [0, nsym) valid
 };
 // the weight convert_samples gives a sample seen n times (learning.jl:17-25): every data-set builder's
 __device__ __forceinline__ float sample_weight(int policy, long long n) {

@@ -15,6 +15,11 @@
 //   k_pm_merge   one wavefront per output row walks its members in buffer order (Float64, sequential, then one division, the
 //                order k_mem_merge documents) and writes W, X, A, P, V; without merging the same kernel runs on groups of one
 // The result is an az_dataset like az_dataset_create_from_tensors's, checked and summed by the same code (dataset_tensor_stats).
+//
+//   augment_with_symmetries                                              src/memory.jl:114-130
+// The host declares GI.symmetries once as gather permutations (az_plane_memory_set_symmetries).  A build with use_symmetries runs the
+// same pipeline over [samples ; images]; an image is never written anywhere: k_pm_hash, k_pm_heads and k_pm_merge read "word w of
+// virtual row r" (pm_row / pm_word below), and their instantiation without symmetries is the build as it was.
 #include "engine.h"
 #include "prims.h"
 
@@ -73,21 +78,60 @@ __device__ __forceinline__ unsigned long long pm_fmix(unsigned long long h) {
   h ^= h >> 33; h *= 0xff51afd7ed558ccdULL; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ULL; h ^= h >> 33;
   return h;
 }
+// ---- virtual rows: augment_with_symmetries (memory.jl:114-130) without storing an image ---------------------------------------------
+// What a build reads.  Buffer index r < n0 is sample (seq0 + r) of the ring.  With symmetries declared and asked for, r >= n0 is image
+// k = (r - n0) % nsym of sample i = (r - n0) / nsym (the order of k_mem_augment): the same ring row read through perm[k], word w of the
+// image being word perm[k][w] of the sample.  n0 * (1 + nsym) < 2^31, so the image's number divides in 32 bits.
+struct PmView {
+  const float* XA;
+  long long cap, seq0, n0;
+  int RW, nsym;
+  const unsigned short* perm;                                        // [nsym][RW]
+};
+struct PmRow {
+  const unsigned int* words;                                         // the ring row's RW words
+  const unsigned short* perm;                                        // NULL: the sample itself
+  size_t slot;
+};
+template <bool SYM> __device__ __forceinline__ PmRow pm_row(const PmView& v, long long r) {
+  long long i = r;
+  const unsigned short* perm = nullptr;
+  if (SYM && r >= v.n0) {
+    const unsigned int q = (unsigned int)(r - v.n0), ns = (unsigned int)v.nsym;
+    i = (long long)(q / ns);
+    perm = v.perm + (size_t)(q % ns) * v.RW;
+  }
+  const size_t slot = (size_t)((v.seq0 + i) % v.cap);
+  return PmRow{(const unsigned int*)v.XA + slot * v.RW, perm, slot};
+}
+// word w of virtual row `row`
+template <bool SYM> __device__ __forceinline__ unsigned int pm_word(const PmRow& row, int w) {
+  if (SYM && row.perm) return row.words[row.perm[w]];
+  return row.words[w];
+}
+// where double j of the virtual row's ND = nA + 2 lies in the ring's: pi'[j] = pi[aperm[j]]; z and t are the sample's
+template <bool SYM> __device__ __forceinline__ int pm_dcol(const PmRow& row, int xs, int nA, int j) {
+  if (SYM && row.perm && j < nA) return (int)row.perm[xs + j] - xs;
+  return j;
+}
+
 // Row hash: lane l mixes words l, l + 64, ... (each with its position) into two 64-bit halves; a fixed shuffle tree folds the 64
-// lanes into lane 0 (the fold is not commutative, the tree has one shape: the key depends on the row alone).  Buffer index r is
-// sample (seq0 + r) of the ring.  bits < 128 truncates the key (az_debug_plane_memory_hash_bits).
-__global__ void __launch_bounds__(64 * PM_WAVES) k_pm_hash(const float* __restrict__ XA, long long cap, long long seq0, long long n, int RW, int bits,
+// lanes into lane 0 (the fold is not commutative, the tree has one shape: the key depends on the row alone).  bits < 128 truncates
+// the key (az_debug_plane_memory_hash_bits).  SYM = false is the build without symmetries: no table is touched.
+template <bool SYM>
+__global__ void __launch_bounds__(64 * PM_WAVES) k_pm_hash(PmView v, long long n, int bits,
                                                            unsigned long long* __restrict__ k0, unsigned long long* __restrict__ k1,
                                                            unsigned long long* __restrict__ k1_keep, unsigned int* __restrict__ idx) {
   const int lane = threadIdx.x & 63;
   const long long r = (long long)blockIdx.x * PM_WAVES + (threadIdx.x >> 6);
   if (r >= n) return;
-  const unsigned int* row = (const unsigned int*)XA + (size_t)((seq0 + r) % cap) * RW;
+  const PmRow row = pm_row<SYM>(v, r);
+  const int RW = v.RW;
   unsigned long long a = 0x9e3779b97f4a7c15ULL + (unsigned long long)lane, b = 0xc2b2ae3d27d4eb4fULL ^ (unsigned long long)lane;
   for (int w = lane; w < RW; w += 64) {
-    const unsigned long long v = row[w], p = (unsigned long long)(w + 1);
-    a = (a ^ (v | (p << 32))) * 0x9e3779b97f4a7c15ULL; a ^= a >> 29;
-    b = (b ^ ((v << 32) | p)) * 0xc2b2ae3d27d4eb4fULL; b ^= b >> 31;
+    const unsigned long long x = pm_word<SYM>(row, w), p = (unsigned long long)(w + 1);
+    a = (a ^ (x | (p << 32))) * 0x9e3779b97f4a7c15ULL; a ^= a >> 29;
+    b = (b ^ ((x << 32) | p)) * 0xc2b2ae3d27d4eb4fULL; b ^= b >> 31;
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -104,7 +148,8 @@ __global__ void __launch_bounds__(64 * PM_WAVES) k_pm_hash(const float* __restri
 // Position i of the sorted order starts a group unless its row IS row i - 1's.  Keys that differ settle it without reading the
 // rows; equal keys are never believed: the wavefront compares every word.  Equal keys over different rows are a collision -- the
 // equal rows of either side may lie apart in the order, so the build is given up (a plain store of 1; every writer stores the same).
-__global__ void __launch_bounds__(64 * PM_WAVES) k_pm_heads(const float* __restrict__ XA, long long cap, long long seq0, long long n, int RW,
+template <bool SYM>
+__global__ void __launch_bounds__(64 * PM_WAVES) k_pm_heads(PmView v, long long n,
                                                             const unsigned long long* __restrict__ k0, const unsigned long long* __restrict__ k1,
                                                             const unsigned int* __restrict__ order, int* __restrict__ head, int* __restrict__ collision) {
   const int lane = threadIdx.x & 63;
@@ -113,10 +158,10 @@ __global__ void __launch_bounds__(64 * PM_WAVES) k_pm_heads(const float* __restr
   if (i == 0) { if (lane == 0) head[0] = 1; return; }
   const unsigned int ra = order[i], rb = order[i - 1];
   if (k0[ra] != k0[rb] || k1[ra] != k1[rb]) { if (lane == 0) head[i] = 1; return; }
-  const unsigned int* a = (const unsigned int*)XA + (size_t)((seq0 + ra) % cap) * RW;
-  const unsigned int* b = (const unsigned int*)XA + (size_t)((seq0 + rb) % cap) * RW;
+  const PmRow a = pm_row<SYM>(v, (long long)ra), b = pm_row<SYM>(v, (long long)rb);
+  const int RW = v.RW;
   bool diff = false;
-  for (int w = lane; w < RW; w += 64) diff = diff || a[w] != b[w];
+  for (int w = lane; w < RW; w += 64) diff = diff || pm_word<SYM>(a, w) != pm_word<SYM>(b, w);
   const bool differ = __ballot(diff) != 0ULL;
   if (lane == 0) { head[i] = differ ? 1 : 0; if (differ) *collision = 1; }
 }
@@ -136,16 +181,18 @@ __global__ void k_pm_groups(const int* __restrict__ head, const int* __restrict_
 // One wavefront per output row g = group gord[g], members order[gpos[s] .. gpos[s + 1]) in buffer order.  Lane l owns doubles l and
 // l + 64 of the ND = nA + 2 <= 128 (pi..., z, t): two named accumulators, no indexed private array.  Each sum STARTS with the first
 // member (keeps -0.0) and adds the others one by one, then divides by the count; n is summed by every lane alike.  X and A are the
-// first member's.  order == NULL: no merging, row g is buffer index g.
-__global__ void __launch_bounds__(64 * PM_WAVES) k_pm_merge(const float* __restrict__ XA, const double* __restrict__ D, const long long* __restrict__ N,
-                                                            long long cap, long long seq0, long long n, long long ngroups, int xs, int nA, int policy,
+// first member's.  order == NULL: no merging, row g is buffer index g.  A member that is an image gives its sample's doubles through
+// the action permutation (pm_dcol) and its sample's n.
+template <bool SYM>
+__global__ void __launch_bounds__(64 * PM_WAVES) k_pm_merge(PmView v, const double* __restrict__ D, const long long* __restrict__ N,
+                                                            long long n, long long ngroups, int xs, int nA, int policy,
                                                             const unsigned int* __restrict__ order, const unsigned int* __restrict__ gord,
                                                             const unsigned int* __restrict__ gpos, float* __restrict__ W, float* __restrict__ X,
                                                             float* __restrict__ A, float* __restrict__ P, float* __restrict__ V, long long* __restrict__ t_n) {
   const int lane = threadIdx.x & 63;
   const long long g = (long long)blockIdx.x * PM_WAVES + (threadIdx.x >> 6);
   if (g >= ngroups) return;
-  const int RW = xs + nA, ND = nA + 2;
+  const int ND = nA + 2;
   long long start = g, end = g + 1;
   if (order) {
     const long long s = gord[g];
@@ -154,15 +201,15 @@ __global__ void __launch_bounds__(64 * PM_WAVES) k_pm_merge(const float* __restr
   }
   const int j0 = lane, j1 = lane + 64;
   const bool h0 = j0 < ND, h1 = j1 < ND;
-  const size_t first = (size_t)((seq0 + (order ? (long long)order[start] : start)) % cap);
-  double acc0 = h0 ? D[first * ND + j0] : 0.0, acc1 = h1 ? D[first * ND + j1] : 0.0;
-  long long nsum = N[first];
+  const PmRow first = pm_row<SYM>(v, order ? (long long)order[start] : start);
+  double acc0 = h0 ? D[first.slot * ND + pm_dcol<SYM>(first, xs, nA, j0)] : 0.0, acc1 = h1 ? D[first.slot * ND + pm_dcol<SYM>(first, xs, nA, j1)] : 0.0;
+  long long nsum = N[first.slot];
 #pragma unroll 4
   for (long long m = start + 1; m < end; ++m) {
-    const size_t slot = (size_t)((seq0 + (long long)order[m]) % cap);
-    if (h0) acc0 += D[slot * ND + j0];
-    if (h1) acc1 += D[slot * ND + j1];
-    nsum += N[slot];
+    const PmRow row = pm_row<SYM>(v, (long long)order[m]);
+    if (h0) acc0 += D[row.slot * ND + pm_dcol<SYM>(row, xs, nA, j0)];
+    if (h1) acc1 += D[row.slot * ND + pm_dcol<SYM>(row, xs, nA, j1)];
+    nsum += N[row.slot];
   }
   const double cnt = (double)(end - start);
   acc0 = acc0 / cnt; acc1 = acc1 / cnt;
@@ -171,8 +218,8 @@ __global__ void __launch_bounds__(64 * PM_WAVES) k_pm_merge(const float* __restr
   if (j0 == nA) V[g] = (float)acc0;
   if (j1 == nA) V[g] = (float)acc1;
   if (lane == 0) { W[g] = sample_weight(policy, nsum); t_n[g] = nsum; }
-  for (int w = lane; w < xs; w += 64) X[(size_t)g * xs + w] = XA[first * RW + w];
-  for (int a = lane; a < nA; a += 64) A[(size_t)g * nA + a] = XA[first * RW + xs + a];
+  for (int w = lane; w < xs; w += 64) X[(size_t)g * xs + w] = __uint_as_float(pm_word<SYM>(first, w));
+  for (int a = lane; a < nA; a += 64) A[(size_t)g * nA + a] = __uint_as_float(pm_word<SYM>(first, xs + a));
 }
 
 // ---- the memory ----------------------------------------------------------------------------------------------------------------------
@@ -183,6 +230,7 @@ extern "C" int az_plane_memory_create(int32_t game, int32_t device, int64_t capa
   if (!game_info(game, &gi)) return fail(AZ_ERR_BAD_ARG, "unknown game id %d", game);
   if (capacity < 1 || capacity > (1LL << 31) - 1) return fail(AZ_ERR_BAD_ARG, "capacity must be in 1..2^31-1");
   if (gi.A + 2 > 128) return fail(AZ_ERR_BAD_ARG, "game id %d has more than 126 actions", game);   // k_pm_merge: two doubles per lane
+  if (gi.C * gi.P + gi.A > 65535) return fail(AZ_ERR_BAD_ARG, "game id %d has rows of more than 65535 words", game);   // d_perm: 16-bit entries
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return fail(AZ_ERR_BAD_ARG, "device %d not available (%d visible)", device, ndev);
@@ -191,12 +239,13 @@ extern "C" int az_plane_memory_create(int32_t game, int32_t device, int64_t capa
   if (!m) return fail(AZ_ERR_HIP, "out of host memory");
   m->game = game; m->device = device; m->gi = gi; m->stream = nullptr; m->d_XA = nullptr; m->d_D = nullptr; m->d_n = nullptr;
   m->xs = gi.C * gi.P; m->nA = gi.A; m->RW = m->xs + m->nA; m->ND = m->nA + 2;
-  m->cap = capacity; m->total = 0; m->cur_batch = 0; m->hash_bits = 128;
+  m->cap = capacity; m->total = 0; m->cur_batch = 0; m->hash_bits = 128; m->nsym = 0; m->d_perm = nullptr;
   int st = [&]() -> int {
     HIPCHK(hipStreamCreate(&m->stream));
     AZCHK(mem_alloc(nullptr, &m->d_XA, (size_t)capacity * m->RW));
     AZCHK(mem_alloc(nullptr, &m->d_D, (size_t)capacity * m->ND));
     AZCHK(mem_alloc(nullptr, &m->d_n, (size_t)capacity));
+    AZCHK(mem_alloc(nullptr, &m->d_perm, (size_t)AZ_PLANE_MAX_SYMMETRIES * m->RW));
     return AZ_OK;
   }();
   if (st != AZ_OK) { az_plane_memory_destroy(m); return st; }
@@ -209,6 +258,7 @@ extern "C" int az_plane_memory_destroy(az_plane_memory* m) {
   if (m->d_XA) (void)hipFree(m->d_XA);
   if (m->d_D) (void)hipFree(m->d_D);
   if (m->d_n) (void)hipFree(m->d_n);
+  if (m->d_perm) (void)hipFree(m->d_perm);
   if (m->stream) (void)hipStreamDestroy(m->stream);
   delete m;
   return AZ_OK;
@@ -226,6 +276,41 @@ extern "C" int az_debug_plane_memory_hash_bits(az_plane_memory* m, int32_t bits)
   PLANE_MEMORY(m);
   if (bits < 1 || bits > 128) return fail(AZ_ERR_BAD_ARG, "hash bits must be in 1..128");
   m->hash_bits = bits;
+  return AZ_OK;
+}
+
+// GI.symmetries of the host's game.  Every row is checked to be a bijection of its range here, in plain host code, before anything
+// changes: a table that is not one would make the kernels read outside a sample's row.
+extern "C" int az_plane_memory_set_symmetries(az_plane_memory* m, int32_t nsym, const int32_t* xperm, const int32_t* aperm) {
+  PLANE_MEMORY(m);
+  if (nsym < 0 || nsym > AZ_PLANE_MAX_SYMMETRIES) return fail(AZ_ERR_BAD_ARG, "nsym must be in 0..%d", AZ_PLANE_MAX_SYMMETRIES);
+  if (nsym > 0 && (!xperm || !aperm)) return fail(AZ_ERR_BAD_ARG, "NULL %s table with nsym = %d", !xperm ? "xperm" : "aperm", nsym);
+  const int xs = m->xs, nA = m->nA, RW = m->RW;
+  std::vector<unsigned short> perm((size_t)nsym * RW);
+  std::vector<int> taken;
+  for (int k = 0; k < nsym; ++k)
+    for (int table = 0; table < 2; ++table) {
+      const int len = table ? nA : xs, base = table ? xs : 0;
+      const int32_t* row = table ? aperm + (size_t)k * nA : xperm + (size_t)k * xs;
+      const char* name = table ? "aperm" : "xperm";
+      taken.assign((size_t)len, -1);
+      for (int w = 0; w < len; ++w) {
+        const int32_t src = row[w];
+        if (src < 0 || src >= len) return fail(AZ_ERR_BAD_ARG, "symmetry %d: %s[%d] = %d is outside 0..%d", k, name, w, (int)src, len - 1);
+        if (taken[src] >= 0) return fail(AZ_ERR_BAD_ARG, "symmetry %d: %s[%d] = %d repeats the source of %s[%d]: not a bijection", k, name, w, (int)src, name, taken[src]);
+        taken[src] = w;
+        perm[(size_t)k * RW + base + w] = (unsigned short)(base + src);
+      }
+    }
+  HIPCHK(hipStreamSynchronize(m->stream));
+  if (nsym > 0) HIPCHK(hipMemcpy(m->d_perm, perm.data(), sizeof(unsigned short) * perm.size(), hipMemcpyHostToDevice));
+  m->nsym = nsym;
+  return AZ_OK;
+}
+extern "C" int az_plane_memory_num_symmetries(az_plane_memory* m, int32_t* nsym) {
+  PLANE_MEMORY(m);
+  if (!nsym) return fail(AZ_ERR_BAD_ARG, "NULL argument");
+  *nsym = m->nsym;
   return AZ_OK;
 }
 
@@ -325,11 +410,16 @@ extern "C" int az_plane_memory_read(az_plane_memory* m, int64_t first, int64_t c
   return AZ_OK;
 }
 
-static int plane_dataset_build(az_plane_memory* m, az_dataset* d, int which, bool merge, int policy) {
+// nsym = 0: the selected samples alone; otherwise [samples ; images] over the declared symmetries (virtual rows, see PmView)
+static int plane_dataset_build(az_plane_memory* m, az_dataset* d, int which, int nsym, bool merge, int policy) {
   const int64_t len = std::min<int64_t>(m->total, m->cap);
   const int64_t n0 = which == 1 ? std::min<int64_t>(m->cur_batch, len) : len;
   if (n0 < 1) return fail(AZ_ERR_STATE, which == 1 ? "the current batch is empty (push_trace advances it, new_batch resets it)" : "the plane memory is empty");
   const long long seq0 = m->total - n0;                              // the newest n0 samples, oldest first
+  const int64_t n1 = n0 * (1 + nsym);                                // rows of the build; the sort's indices are 32-bit
+  if (n1 > (1LL << 31) - 1) return fail(AZ_ERR_BAD_ARG, "%lld samples with %d symmetries are %lld rows: more than 2^31-1", (long long)n0, nsym, (long long)n1);
+  const bool sym = nsym > 0;
+  const PmView view{m->d_XA, (long long)m->cap, seq0, (long long)n0, m->RW, nsym, m->d_perm};
   const int xs = m->xs, nA = m->nA;
   std::vector<void*> tmp;
   int rc = [&]() -> int {
@@ -337,25 +427,25 @@ static int plane_dataset_build(az_plane_memory* m, az_dataset* d, int which, boo
     HIPCHK(hipStreamCreate(&d->stream));
     hipStream_t st = d->stream;
     unsigned int *order = nullptr, *gord = nullptr, *gpos = nullptr;
-    int64_t n2 = n0;
+    int64_t n2 = n1;
     if (merge) {
       unsigned long long *k0, *k1, *k1keep, *ks, *ks2, *gkey, *gks; unsigned int *i0, *i1, *i2, *gval; int *head, *seg, *stmp, *coll;
-      const size_t N = (size_t)n0;
+      const size_t N = (size_t)n1;
       AZCHK(mem_alloc(&tmp, &k0, N)); AZCHK(mem_alloc(&tmp, &k1, N)); AZCHK(mem_alloc(&tmp, &k1keep, N)); AZCHK(mem_alloc(&tmp, &ks, N)); AZCHK(mem_alloc(&tmp, &ks2, N));
       AZCHK(mem_alloc(&tmp, &i0, N)); AZCHK(mem_alloc(&tmp, &i1, N)); AZCHK(mem_alloc(&tmp, &i2, N));
       AZCHK(mem_alloc(&tmp, &head, N)); AZCHK(mem_alloc(&tmp, &seg, N)); AZCHK(mem_alloc(&tmp, &coll, 1));
-      AZCHK(mem_alloc(&tmp, &stmp, std::max(prims::sort_tmp_ints(n0), prims::scan_tmp_ints(n0))));
-      const unsigned gb = (unsigned)((n0 + 255) / 256);
+      AZCHK(mem_alloc(&tmp, &stmp, std::max(prims::sort_tmp_ints(n1), prims::scan_tmp_ints(n1))));
+      const unsigned gb = (unsigned)((n1 + 255) / 256);
       HIPCHK(hipMemsetAsync(coll, 0, sizeof(int), st));
-      hipLaunchKernelGGL(k_pm_hash, dim3(pm_grid(n0)), dim3(64 * PM_WAVES), 0, st, m->d_XA, (long long)m->cap, seq0, (long long)n0, m->RW, m->hash_bits, k0, k1, k1keep, i0);
+      hipLaunchKernelGGL(sym ? k_pm_hash<true> : k_pm_hash<false>, dim3(pm_grid(n1)), dim3(64 * PM_WAVES), 0, st, view, (long long)n1, m->hash_bits, k0, k1, k1keep, i0);
       // LSD as dataset_build (memory.hip): stable by k1, then by k0 -> ascending (k0, k1, buffer index)
-      HIPCHK(prims::sort_pairs(k1, ks, i0, i1, n0, stmp, st));
-      hipLaunchKernelGGL(k_pm_gather_u64, dim3(gb), dim3(256), 0, st, k0, i1, (long long)n0, ks2);
-      HIPCHK(prims::sort_pairs(ks2, ks, i1, i2, n0, stmp, st));
-      hipLaunchKernelGGL(k_pm_heads, dim3(pm_grid(n0)), dim3(64 * PM_WAVES), 0, st, m->d_XA, (long long)m->cap, seq0, (long long)n0, m->RW, k0, k1keep, i2, head, coll);
-      HIPCHK(prims::scan_ints(head, seg, n0, true, stmp, st));
+      HIPCHK(prims::sort_pairs(k1, ks, i0, i1, n1, stmp, st));
+      hipLaunchKernelGGL(k_pm_gather_u64, dim3(gb), dim3(256), 0, st, k0, i1, (long long)n1, ks2);
+      HIPCHK(prims::sort_pairs(ks2, ks, i1, i2, n1, stmp, st));
+      hipLaunchKernelGGL(sym ? k_pm_heads<true> : k_pm_heads<false>, dim3(pm_grid(n1)), dim3(64 * PM_WAVES), 0, st, view, (long long)n1, k0, k1keep, i2, head, coll);
+      HIPCHK(prims::scan_ints(head, seg, n1, true, stmp, st));
       int nseg = 0, collision = 0;
-      HIPCHK(hipMemcpyAsync(&nseg, seg + (n0 - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(&nseg, seg + (n1 - 1), sizeof(int), hipMemcpyDeviceToHost, st));
       HIPCHK(hipMemcpyAsync(&collision, coll, sizeof(int), hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));
       HIPCHK(hipGetLastError());
@@ -363,8 +453,8 @@ static int plane_dataset_build(az_plane_memory* m, az_dataset* d, int which, boo
       n2 = nseg;
       const size_t G = (size_t)n2;
       AZCHK(mem_alloc(&tmp, &gkey, G)); AZCHK(mem_alloc(&tmp, &gks, G)); AZCHK(mem_alloc(&tmp, &gval, G)); AZCHK(mem_alloc(&tmp, &gord, G)); AZCHK(mem_alloc(&tmp, &gpos, G));
-      hipLaunchKernelGGL(k_pm_groups, dim3(gb), dim3(256), 0, st, head, seg, i2, (long long)n0, gkey, gval, gpos);
-      HIPCHK(prims::sort_pairs(gkey, gks, gval, gord, n2, stmp, st));   // n2 <= n0: stmp is large enough
+      hipLaunchKernelGGL(k_pm_groups, dim3(gb), dim3(256), 0, st, head, seg, i2, (long long)n1, gkey, gval, gpos);
+      HIPCHK(prims::sort_pairs(gkey, gks, gval, gord, n2, stmp, st));   // n2 <= n1: stmp is large enough
       order = i2;
     }
     d->n = n2;
@@ -373,7 +463,7 @@ static int plane_dataset_build(az_plane_memory* m, az_dataset* d, int which, boo
     AZCHK(mem_alloc(&d->allocs, &d->d_A, G * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_P, G * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_X, G * xs));
     long long *tn, *tsum;
     AZCHK(mem_alloc(&tmp, &tn, G)); AZCHK(mem_alloc(&tmp, &tsum, prims::sum_tmp_doubles(n2)));
-    hipLaunchKernelGGL(k_pm_merge, dim3(pm_grid(n2)), dim3(64 * PM_WAVES), 0, st, m->d_XA, m->d_D, m->d_n, (long long)m->cap, seq0, (long long)n0, (long long)n2,
+    hipLaunchKernelGGL(sym ? k_pm_merge<true> : k_pm_merge<false>, dim3(pm_grid(n2)), dim3(64 * PM_WAVES), 0, st, view, m->d_D, m->d_n, (long long)n1, (long long)n2,
                        xs, nA, policy, order, gord, gpos, d->d_W, d->d_X, d->d_A, d->d_P, d->d_V, tn);
     long long* d_sn = nullptr; long long sn = 0;
     HIPCHK(prims::sum_values<long long>(tn, n2, tsum, &d_sn, st));    // sum(e.n) is an Int: exact
@@ -387,20 +477,25 @@ static int plane_dataset_build(az_plane_memory* m, az_dataset* d, int which, boo
   for (void* p : tmp) (void)hipFree(p);
   return rc;
 }
-extern "C" int az_dataset_create_from_plane_memory(az_plane_memory* m, int32_t which, int32_t use_position_averaging, int32_t weighing_policy,
-                                                   az_dataset** out) {
+extern "C" int az_dataset_create_from_plane_memory_sym(az_plane_memory* m, int32_t which, int32_t use_symmetries, int32_t use_position_averaging,
+                                                       int32_t weighing_policy, az_dataset** out) {
   PLANE_MEMORY(m);
   if (!out) return fail(AZ_ERR_BAD_ARG, "NULL argument");
   *out = nullptr;
   if (which != 0 && which != 1) return fail(AZ_ERR_BAD_ARG, "which must be 0 (get_experience) or 1 (last_batch)");
   if (weighing_policy < AZ_WEIGHT_CONSTANT || weighing_policy > AZ_WEIGHT_LINEAR) return fail(AZ_ERR_BAD_ARG, "unknown samples_weighing_policy %d", weighing_policy);
+  if (use_symmetries && m->nsym == 0) return fail(AZ_ERR_BAD_ARG, "use_symmetries: no symmetries were declared for this memory (game.jl:332; az_plane_memory_set_symmetries)");
   az_dataset* d = new (std::nothrow) az_dataset();
   if (!d) return fail(AZ_ERR_HIP, "out of host memory");
   d->game = m->game; d->device = m->device; d->gi = m->gi; d->stream = nullptr; d->own_stream = true; d->n = 0; d->sum_n = 0;
   d->Wtot = 0.0; d->Wmean = 0.f; d->Hp = 0.f; d->d_samples = nullptr; d->d_envs = nullptr;
   d->d_W = d->d_X = d->d_A = d->d_P = d->d_V = nullptr;
-  const int st = plane_dataset_build(m, d, which, use_position_averaging != 0, weighing_policy);
+  const int st = plane_dataset_build(m, d, which, use_symmetries ? m->nsym : 0, use_position_averaging != 0, weighing_policy);
   if (st != AZ_OK) { az_dataset_destroy(d); return st; }
   *out = d;
   return AZ_OK;
+}
+extern "C" int az_dataset_create_from_plane_memory(az_plane_memory* m, int32_t which, int32_t use_position_averaging, int32_t weighing_policy,
+                                                   az_dataset** out) {
+  return az_dataset_create_from_plane_memory_sym(m, which, 0, use_position_averaging, weighing_policy, out);
 }

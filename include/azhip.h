@@ -571,6 +571,25 @@ int az_plane_memory_empty(az_plane_memory* m);                                  
  * AZ_ERR_STATE when there is no sample to take (an empty memory; which = 1 with an empty batch) and for a hash collision. */
 int az_dataset_create_from_plane_memory(az_plane_memory* m, int32_t which, int32_t use_position_averaging, int32_t weighing_policy,
                                         az_dataset** out);
+#define AZ_PLANE_MAX_SYMMETRIES 15
+/* GI.symmetries for a memory whose game lives on the host: nsym non-identical symmetries, each a pair of gather permutations
+ *   X'[w] = X[xperm[k][w]]  (w over the C*H*W words of a sample's planes, layout of az_net_forward)
+ *   A'[j] = A[aperm[k][j]], pi'[j] = pi[aperm[k][j]]   (game.jl:192 "mask2 == mask1[sigma]", memory.jl:119)
+ * z, t, n are the sample's.  nsym = 0 (pointers may be NULL) clears them.  The symmetries belong to the game, not to the samples: the
+ * call may come at any time, on an empty or a full memory, and nothing is stored per sample.  AZ_ERR_BAD_ARG for nsym outside
+ * 0..AZ_PLANE_MAX_SYMMETRIES, a NULL table with nsym > 0, and any row that is not a bijection of its range (az_last_error() names the
+ * symmetry, the table and the first offending index: out of range, or a source that an earlier index already took); the set declared
+ * before is then unchanged.  An identity permutation is not refused (the reference does not refuse one either). */
+int az_plane_memory_set_symmetries(az_plane_memory* m, int32_t nsym, const int32_t* xperm /*[nsym][C*H*W]*/, const int32_t* aperm /*[nsym][nA]*/);
+int az_plane_memory_num_symmetries(az_plane_memory* m, int32_t* nsym);
+/* az_dataset_create_from_plane_memory with augment_with_symmetries (memory.jl:114-130) in front of the merge.  use_symmetries == 0: exactly
+ * that call.  Otherwise the n0 selected samples (oldest first) become the sequence [samples ; images] of n1 = n0 * (1 + nsym) rows,
+ * image k of sample i at buffer index n0 + i * nsym + k, and everything promised above ("state identity", "merging", "hashing",
+ * "convert_samples") holds over that sequence in that buffer order; num_samples = rows after merging, sum_n = (1 + nsym) * sum of n.
+ * The images are never stored: every kernel reads them through the permutations.  AZ_ERR_BAD_ARG when use_symmetries != 0 and no
+ * symmetries were declared for this memory (game.jl:332), and when n1 > 2^31 - 1. */
+int az_dataset_create_from_plane_memory_sym(az_plane_memory* m, int32_t which, int32_t use_symmetries, int32_t use_position_averaging,
+                                            int32_t weighing_policy, az_dataset** out);
 
 /* ---- the optimiser step (src/learning.jl:123-141, src/networks/flux.jl:68-95) --------------- */
 typedef struct az_trainer az_trainer;   /* Trainer (src/learning.jl:98-121): network in train mode + optimiser state */

@@ -284,5 +284,8 @@ const UNBOUND = Dict(
   :az_plane_memory_new_batch => "see az_plane_memory_create",
   :az_plane_memory_empty => "see az_plane_memory_create",
   :az_dataset_create_from_plane_memory => "builds from an az_plane_memory, which is unbound (see az_plane_memory_create)",
+  :az_plane_memory_set_symmetries => "see az_plane_memory_create; a Julia host has GI.symmetries and the reference's augment_with_symmetries",
+  :az_plane_memory_num_symmetries => "see az_plane_memory_create",
+  :az_dataset_create_from_plane_memory_sym => "builds from an az_plane_memory, which is unbound (see az_plane_memory_create)",
 )
 

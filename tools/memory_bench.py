@@ -3,7 +3,11 @@
 
 --planes: the replay memory of a host-stepped game instead (azhip.PlaneMemoryBuffer, 9x9x4 Go geometry, about 30 % repeated
 positions): az_dataset_create_from_plane_memory (merged, LOG_WEIGHT) against what a host without it does for the same samples -- a
-numpy merge_by_state + convert_samples, then az_dataset_create_from_tensors with its upload -- in the same run; --out writes both as JSON."""
+numpy merge_by_state + convert_samples, then az_dataset_create_from_tensors with its upload -- in the same run; --out writes both as JSON.
+
+--planes --symmetries: the same samples with the 7 dihedral symmetries declared (azhip.plane_symmetries, set_symmetries): the merged
+LOG_WEIGHT build over the 8 x samples virtual rows, against what a host without declared symmetries does for the same data set -- gather
+the images with numpy, push all 8 x samples into a memory of 8 x the capacity (upload included), run the build without symmetries."""
 import argparse
 import os
 import sys
@@ -17,6 +21,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--games", type=int, default=16384)
 ap.add_argument("--filters", type=int, default=64)
 ap.add_argument("--planes", action="store_true")
+ap.add_argument("--symmetries", action="store_true")
 ap.add_argument("--samples", type=int, default=1 << 20)
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
@@ -48,11 +53,8 @@ def host_merge_convert(X, A, P, z, nv):
     return W, X[f], A[f], (pi / cnt[:, None]).astype(np.float32), (zs / cnt).astype(np.float32)
 
 
-def planes_bench():
-    import json
+def plane_samples(n):
     import numpy as np
-    gspec = azhip.Go9PlanesSpec()
-    n = a.samples
     rng = np.random.default_rng(1)
     X = rng.integers(0, 2, size=(n, 4, 9, 9), dtype=np.uint8).astype(np.float32)
     A = (rng.random((n, 82), dtype=np.float32) < 0.6).astype(np.float32)
@@ -63,6 +65,91 @@ def planes_bench():
     P = rng.random((n, 82)) * A
     P /= P.sum(axis=1, keepdims=True)
     z, t, nv = rng.uniform(-1, 1, n), rng.integers(1, 80, n).astype(np.float64), np.ones(n, dtype=np.int64)
+    return X, A, P, z, t, nv
+
+
+def write_result(res):
+    import json
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+def timed_builds(mem, repeats, **kw):
+    ms = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        d = mem.dataset(use_position_averaging=True, weighing_policy=azhip.LOG_WEIGHT, **kw)
+        ms.append(round(1e3 * (time.perf_counter() - t0), 2))
+        info = (len(d), d.sum_n, d.Wtot, d.Hp)
+        d.close()
+    return ms, info
+
+
+def memory_bytes(gspec, capacity):
+    """HBM of a plane memory's ring: per sample the (X, A) row in Float32, pi / z / t in Float64 and n"""
+    w, h, c = gspec.state_dim()
+    nA = gspec.num_actions()
+    return capacity * (4 * (w * h * c + nA) + 8 * (nA + 2) + 8)
+
+
+def symmetries_bench():
+    import numpy as np
+    gspec = azhip.Go9PlanesSpec()
+    n = a.samples
+    X, A, P, z, t, nv = plane_samples(n)
+    xperm, aperm = azhip.plane_symmetries(gspec)
+    nsym = len(xperm)
+    # declared: n samples, the images are read through the tables
+    mem = azhip.PlaneMemoryBuffer(gspec, n)
+    mem.set_symmetries(xperm, aperm)
+    t0 = time.perf_counter()
+    mem.push_samples(X, A, P, z, t, nv)
+    push_ms = 1e3 * (time.perf_counter() - t0)
+    plain_ms, _ = timed_builds(mem, 4)
+    sym_ms, info = timed_builds(mem, 5, use_symmetries=True)
+    mem.close()
+    # pushed: the host gathers the images (chunks of samples, so the host never holds all 8 n rows) and pushes them in the order
+    # n + i * nsym + k into a memory of (1 + nsym) n samples
+    big = azhip.PlaneMemoryBuffer(gspec, n * (1 + nsym))
+    t0 = time.perf_counter()
+    big.push_samples(X, A, P, z, t, nv)
+    big_push_ms, gather_ms = 1e3 * (time.perf_counter() - t0), 0.0
+    chunk = 1 << 16
+    for lo in range(0, n, chunk):
+        hi = min(n, lo + chunk)
+        t0 = time.perf_counter()
+        m = hi - lo
+        Xi = X[lo:hi].reshape(m, -1)[:, xperm].reshape(m * nsym, 4, 9, 9)
+        Ai, Pi = A[lo:hi][:, aperm].reshape(m * nsym, -1), P[lo:hi][:, aperm].reshape(m * nsym, -1)
+        zi, ti, ni = np.repeat(z[lo:hi], nsym), np.repeat(t[lo:hi], nsym), np.repeat(nv[lo:hi], nsym)
+        t1 = time.perf_counter()
+        big.push_samples(Xi, Ai, Pi, zi, ti, ni)
+        t2 = time.perf_counter()
+        gather_ms += 1e3 * (t1 - t0)
+        big_push_ms += 1e3 * (t2 - t1)
+    big_ms, big_info = timed_builds(big, 5)
+    big.close()
+    assert info == big_info, (info, big_info)                                   # the same rows in the same order: the same sums exactly
+    write_result({"samples": n, "symmetries": nsym, "virtual_rows": n * (1 + nsym), "merged_rows": info[0], "sum_n": info[1],
+                  "geometry": "9x9x4, 82 actions", "weighing_policy": "LOG_WEIGHT",
+                  "declared_push_samples_ms_incl_upload": round(push_ms, 1), "declared_memory_bytes": memory_bytes(gspec, n),
+                  "declared_build_ms": sym_ms, "declared_build_ms_best_after_first": min(sym_ms[1:]),
+                  "same_memory_build_without_symmetries_ms": plain_ms,
+                  "pushed_host_numpy_gather_ms": round(gather_ms, 1), "pushed_push_samples_ms_incl_upload": round(big_push_ms, 1),
+                  "pushed_memory_bytes": memory_bytes(gspec, n * (1 + nsym)),
+                  "pushed_build_ms": big_ms, "pushed_build_ms_best_after_first": min(big_ms[1:]),
+                  "pushed_build_ms_spread_after_first": round(max(big_ms[1:]) - min(big_ms[1:]), 2)})
+
+
+def planes_bench():
+    import numpy as np
+    gspec = azhip.Go9PlanesSpec()
+    n = a.samples
+    X, A, P, z, t, nv = plane_samples(n)
     mem = azhip.PlaneMemoryBuffer(gspec, n)
     t0 = time.perf_counter()
     mem.push_samples(X, A, P, z, t, nv)
@@ -89,16 +176,13 @@ def planes_bench():
            "push_samples_ms_incl_upload": round(push_ms, 1),
            "host_numpy_merge_convert_ms": [round(h[0], 1) for h in host], "host_create_from_tensors_ms_incl_upload": [round(h[1], 1) for h in host],
            "host_path_ms_best": round(min(h[0] + h[1] for h in host), 1)}
-    print(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
+    write_result(res)
 
 
+if a.symmetries and not a.planes:
+    ap.error("--symmetries is a mode of --planes")
 if a.planes:
-    planes_bench()
+    symmetries_bench() if a.symmetries else planes_bench()
     sys.exit(0)
 gspec = azhip.ConnectFourSpec()
 with azhip.Engine(game=0, oracle=azhip.ORACLE_HASH, num_workers=4096, batch_size=4096, num_iters_per_turn=8, reset_every=1,
