@@ -224,7 +224,8 @@ static long long fr_ahead(const az_engine* e) {
   const long long cap = e->v.cap_nodes;
   return std::min<long long>(std::min<long long>(e->fr_look_waves, cap) * std::min(fr_per_wave(e), cap) + 2, cap);
 }
-// a look at the node counts alone, between two rounds
+// a look at the node counts alone, between two rounds (a mapped-on-demand pool only).  It reads nothing the step report holds -- the
+// counts come from k_node_counts through vm_grow's own copy -- so it keeps its plain wait for the group's streams.
 static int fr_look(az_engine* e) {
   e->fr_since_look = 0;
   AZCHK(sync_groups(e));
@@ -404,6 +405,7 @@ static int create_eval_cache(az_engine* e) {
   return AZ_OK;
 }
 
+static constexpr size_t FETCH_BYTES = (size_t)1 << 20;            // a look of the headline fetches ~30 KB
 // the records a phase leaves, the device's error word, and the words host and kernels exchange without a sync (host-mapped)
 static int create_words(az_engine* e) {
   DView& v = e->v; const int G = v.G;
@@ -419,6 +421,11 @@ static int create_words(az_engine* e) {
   // free-running phases: the device's own bookkeeping (FRState) and two host-mapped progress words
   AZCHK(dalloc(e, &e->d_fr, 1)); AZCHK(dalloc(e, &e->d_bg_stop, 1));
   AZCHK(halloc_mapped(e, &e->h_busy, &e->d_busy, AZ_MAX_GROUPS, -1));
+  // ... the report a look reads after one synchronisation, and pinned staging for the records of the games that look fetches
+  AZCHK(halloc_pinned(e, &e->h_report, 1, hipHostMallocMapped));
+  memset(e->h_report, 0, sizeof *e->h_report);
+  HIPCHK(hipHostGetDevicePointer((void**)&e->d_report, e->h_report, 0));
+  AZCHK(halloc_pinned(e, &e->h_fetch, FETCH_BYTES));
   return halloc_mapped(e, &e->h_fr_words, &e->d_fr_words, 2, 0);
 }
 
@@ -894,8 +901,8 @@ template <class Gm> static int wave_group(az_engine* e, int g, uint32_t sim_idx)
   LAUNCH_ON(e, st, AZ_K_SELECT, G, (k_tree<Gm>), gb, 256, 0, v, e->p, (e->pending[g] || e->fr_on) ? 1 : 0, 1, par);
   e->pending[g] = true;
   // One slot group, free-running: the wave's launch, the tower and the heads follow each other on ONE stream (no event between them: a
-  // dependency across streams costs ~10 us, three of them per wave were 3 % of it); the move step and the background search go to a second
-  // stream, behind an event recorded here, and the next wave's launch waits for them.
+  // dependency across streams costs ~10 us, three of them per wave were 3 % of it); the move step and the background search go to two side
+  // streams, behind an event recorded here, and the next wave's launch waits for ONE event that stands for both (below).
   hipStream_t s2 = st;
   e->bg_signal = false;
   const bool side = e->fr_on && !split && e->cfg.oracle == AZ_ORACLE_RESNET && e->fr_s[1] && st == e->fr_s[0];
@@ -924,12 +931,14 @@ template <class Gm> static int wave_group(az_engine* e, int g, uint32_t sim_idx)
       AZCHK(ec_next_launch(e, &e->gv[g]));
       DView bv = e->gv[g];
       bv.run_k = e->fr_kbg; bv.low_prio = env_process().bg_prio ? 0 : 1;
-      if (side && e->bg_signal) { bv.bg_stop = e->d_bg_stop; bv.bg_seq = e->bg_seq; }   // ... until the wave's tower has run (net_impl.h sets the word)
+      if (side && e->bg_signal) { bv.bg_stop = e->d_bg_stop; bv.bg_seq = e->bg_seq; }   // ... until the wave's tower has run (the tower raises the word, or wave_net_f has it set: net_impl.h)
       LAUNCH_ON(e, s2, AZ_K_EXPAND, G, (k_tree<Gm>), gb, 256, 0, bv, e->p, 0, 1, par ^ 1);
     }
     if (side) {
+      // ONE join on the wave's stream: the background search ends last (it runs until the tower has), so its stream takes the move step's
+      // event behind its launch and the wave's stream waits for the background stream's event alone
+      HIPCHK(hipEventRecord(e->fr_ev[2], s3)); HIPCHK(hipStreamWaitEvent(s2, e->fr_ev[2], 0));
       HIPCHK(hipEventRecord(e->fr_ev[1], s2)); HIPCHK(hipStreamWaitEvent(st, e->fr_ev[1], 0));
-      HIPCHK(hipEventRecord(e->fr_ev[2], s3)); HIPCHK(hipStreamWaitEvent(st, e->fr_ev[2], 0));
     }   // the next wave's launch finds the slots' state settled
     else if (split && e->cfg.oracle == AZ_ORACLE_RESNET) HIPCHK(hipStreamWaitEvent(st, e->ev_net[g], 0));   // the next wave's launch needs this wave's answers
   }
@@ -1033,6 +1042,7 @@ template <class Gm> static int run_waves(az_engine* e, int nga, int n, uint32_t 
       hipGraphExec_t ex = nullptr;
       AZCHK(wave_pair_graph<Gm>(e, &ex));
       HIPCHK(hipGraphLaunch(ex, e->stream));
+      e->report_fresh = false;
       e->stats.waves += 2;
       done += 2;
     } else {
@@ -1276,6 +1286,7 @@ extern "C" int az_selfplay_begin(az_engine* e, int32_t num_games, int32_t first_
     }
   }
   memset(&e->stats, 0, sizeof e->stats);
+  e->report_fresh = false;
   e->aborted_ids.clear();
   const int n0 = num_games < 0 ? G : std::min(G, (int)num_games);
   std::vector<int> slots(n0);
@@ -1429,42 +1440,87 @@ template <class Gm> static int move_round(az_engine* e) {
   return vm_grow(e, e->p.nsims + 2);                                 // chunks for the next explore! of every slot
 }
 
+// the step report (tree.h StepReport): one workgroup, behind the wave.  (Lane 0 adds the 255 partial sums alone: ~1300 LDS reads, a
+// few us of the 19 us a look costs; a wavefront reduction would shorten that and is not what the look waits for -- the wave is.)
+static __global__ void __launch_bounds__(256) k_step_report(FRState* st, const int* err, const int* finished, int G, const long long* stat,
+                                                            int nrec, int drain, StepReport* out) {
+  __shared__ long long s_sum[256][4];
+  __shared__ int s_ret[256];
+  const int t = threadIdx.x;
+  long long a[4] = {0, 0, 0, 0};
+  for (int i = t; i < nrec; i += 256) for (int k = 0; k < 4; ++k) a[k] += stat[(size_t)i * 4 + k];
+  int r = 0;
+  for (int s = t; s < G; s += 256) r += finished[s] == 2;
+  for (int k = 0; k < 4; ++k) s_sum[t][k] = a[k];
+  s_ret[t] = r;
+  __syncthreads();
+  if (t != 0) return;
+  for (int i = 1; i < 256; ++i) { for (int k = 0; k < 4; ++k) a[k] += s_sum[i][k]; r += s_ret[i]; }
+  const FRState fs = *st;
+  const int ec = *err;
+  out->fr = fs;
+  for (int k = 0; k < 4; ++k) out->stat[k] = a[k];
+  out->err = ec; out->retired = r;
+  if (drain && ec == 0 && fs.resv != 0) st->resv = 0;
+}
 // Free-running phase: what the host still does, every fr_round_waves waves and at the end of every az_selfplay_step -- wait for the
 // device, fetch the games that ended since its last look (game records and, if the caller wants host traces, their move records),
 // deal with retired slots (replacement games), back the node-pool chunks the slots will reach before the next look.
+// What it reads comes in ONE piece: k_step_report (tree.h) runs behind the wave and leaves the phase's words, the error word, the
+// statistics sums and the number of retired slots in pinned memory, so a look that finds no finished game and no retired slot
+// synchronises once and copies nothing.  Finished games cost one batch of copies into pinned staging and a second synchronisation;
+// the slots' `finished` words are fetched only when the report counts a retired slot.
 template <class Gm> static int fr_round(az_engine* e) {
   const int G = e->v.G;
   e->fr_since_round = 0; e->fr_since_look = 0;
-  AZCHK(sync_groups(e));
+  // One slot group: the group's stream has been made to wait for the side streams at the end of every wave (wave_group), so the report
+  // kernel, launched on it, is ordered behind everything it reports and one wait covers the wave and the report.  Several groups: their
+  // streams are joined by the host first and the report runs on the engine's stream.
+  const bool one = e->ngroups == 1;
+  hipStream_t rs = one ? e->gs[0] : e->stream;
+  if (!one) AZCHK(sync_groups(e));
   if (e->xch_epoch && !e->split_off) {                              // split towers have run: did one give up? (the word is only valid once the device is idle)
     AZCHK(sync_all(e));
     if (*(volatile int*)e->h_xflag) { AZCHK(recover_split<Gm>(e)); AZCHK(sync_all(e)); }
   }
-  FRState fs;
-  HIPCHK(hipMemcpyAsync(&fs, e->d_fr, sizeof fs, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(e->h_finished.data(), e->v.finished, sizeof(int) * G, hipMemcpyDeviceToHost, e->stream));
-  AZCHK(check_device_error(e));   // synchronises
+  hipLaunchKernelGGL(k_step_report, dim3(1), dim3(256), 0, rs, e->d_fr, e->v.err, e->v.finished, G, e->gv[0].stat, (int)(e->stat_words / 4),
+                     e->d_phase ? 0 : 1, e->d_report);
+  HIPCHK(hipStreamSynchronize(rs));
+  HIPCHK(hipGetLastError());
+  if (one) AZCHK(sync_groups(e));                                    // (the side streams: idle by now, these return at once)
+  const StepReport rp = *e->h_report;
+  if (rp.err) return check_device_error(e);                         // names the error and clears the word
+  FRState fs = rp.fr;
   bool dirty = false;
   const int done = (int)(fs.resv >> 40);
   const long long nrec = (long long)(fs.resv & ((1ULL << 40) - 1));
   const int nd = done - e->fr_prev_done;
   if (nd > 0) {
-    e->h_done.resize(nd); e->h_done_off.resize(nd);
-    HIPCHK(hipMemcpyAsync(e->h_done.data(), e->d_done + e->fr_prev_done, sizeof(az_game_rec) * nd, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(e->h_done_off.data(), e->d_done_off + e->fr_prev_done, sizeof(long long) * nd, hipMemcpyDeviceToHost, e->stream));
     const size_t m0 = e->q_moves.size();
     const long long nm = nrec - e->fr_prev_recs;
     const bool to_host = (e->host_moves || !e->d_phase) && nm > 0;
+    const size_t b_rec = sizeof(az_game_rec) * (size_t)nd, b_off = sizeof(long long) * (size_t)nd, b_mv = to_host ? sizeof(az_move_rec) * (size_t)nm : 0;
+    const bool pinned = b_rec + b_off + b_mv <= FETCH_BYTES;         // (all three hold 8-byte words and are multiples of 8 bytes long)
+    az_game_rec* h_rec; long long* h_off; az_move_rec* h_mv = nullptr;
+    if (to_host) e->q_moves.resize(m0 + (size_t)nm);
+    if (pinned) {
+      h_off = (long long*)e->h_fetch; h_rec = (az_game_rec*)(e->h_fetch + b_off); h_mv = (az_move_rec*)(e->h_fetch + b_off + b_rec);
+    } else {
+      e->h_done.resize(nd); e->h_done_off.resize(nd);
+      h_rec = e->h_done.data(); h_off = e->h_done_off.data(); if (to_host) h_mv = e->q_moves.data() + m0;
+    }
+    HIPCHK(hipMemcpyAsync(h_rec, e->d_done + e->fr_prev_done, b_rec, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(h_off, e->d_done_off + e->fr_prev_done, b_off, hipMemcpyDeviceToHost, e->stream));
     if (to_host) {
-      e->q_moves.resize(m0 + (size_t)nm);
       const az_move_rec* src = (e->d_phase ? e->d_phase : e->d_stage) + e->fr_prev_recs;
-      HIPCHK(hipMemcpyAsync(e->q_moves.data() + m0, src, sizeof(az_move_rec) * (size_t)nm, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipMemcpyAsync(h_mv, src, b_mv, hipMemcpyDeviceToHost, e->stream));
     }
     HIPCHK(hipStreamSynchronize(e->stream));
+    if (pinned && to_host) memcpy(e->q_moves.data() + m0, h_mv, b_mv);
     for (int i = 0; i < nd; ++i) {
-      az_game_rec g = e->h_done[i];
-      g.first_move = (int32_t)((long long)m0 + e->h_done_off[i] - e->fr_prev_recs);
-      if (e->d_phase) { e->ph_games.push_back(g); e->ph_off.push_back(e->h_done_off[i]); }
+      az_game_rec g = h_rec[i];
+      g.first_move = (int32_t)((long long)m0 + h_off[i] - e->fr_prev_recs);
+      if (e->d_phase) { e->ph_games.push_back(g); e->ph_off.push_back(h_off[i]); }
       e->q_games.push_back(g);
       e->games_done++;
       e->stats.games++;
@@ -1475,15 +1531,18 @@ template <class Gm> static int fr_round(az_engine* e) {
   e->stats.moves = fs.moves;
   if (e->total_games >= 0) fs.next_game = std::min(fs.next_game, e->total_games);   // slots that asked in vain pushed the counter past the end
   e->next_game = fs.next_game;
+  if (!e->d_phase && (done > 0 || nrec > 0)) {                      // unbounded phase: the staging area has been drained -- and k_step_report
+    fs.resv = 0; e->fr_prev_done = 0; e->fr_prev_recs = 0;           // has set the device's word back already
+  }
   // retired slots (node pool or move records full; the kernels have taken them out of the counts): reported as aborted; the slot
   // plays ONE replacement game, or the next game, with an empty tree -- as in lock step (move_round)
-  std::vector<int> aslots, aslots_refill;
-  std::vector<uint32_t> agids;
-  for (int sl = 0; sl < G; ++sl) if (e->h_finished[sl] == 2) aslots.push_back(sl);
-  if (!aslots.empty()) {
-    std::vector<uint32_t> gid(G);
+  if (rp.retired > 0) {
+    std::vector<int> aslots, aslots_refill;
+    std::vector<uint32_t> agids, gid(G);
+    HIPCHK(hipMemcpyAsync(e->h_finished.data(), e->v.finished, sizeof(int) * G, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipMemcpyAsync(gid.data(), e->v.game_id, sizeof(uint32_t) * G, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    for (int sl = 0; sl < G; ++sl) if (e->h_finished[sl] == 2) aslots.push_back(sl);
     for (int sl : aslots) {
       const int32_t id = (int32_t)gid[sl];
       e->aborted_ids.push_back(id);
@@ -1504,17 +1563,16 @@ template <class Gm> static int fr_round(az_engine* e) {
     AZCHK(start_games<Gm>(e, aslots_refill, agids, nullptr, 1, 1));  // a retired slot starts over with an empty tree
     dirty = true;
   }
-  if (!e->d_phase && (done > 0 || nrec > 0)) {                      // unbounded phase: the staging area has been drained
-    fs.resv = 0; e->fr_prev_done = 0; e->fr_prev_recs = 0; dirty = true;
-  }
-  if (dirty) {
+  if (dirty) {                                                      // the host changed the phase's words: only then do they go back
     HIPCHK(hipMemcpyAsync(e->d_fr, &fs, sizeof fs, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
   }
   e->active_slots = 0;
   for (int g = 0; g < AZ_MAX_GROUPS; ++g) { e->group_active[g] = g < e->ngroups ? std::max(0, fs.active[g]) : 0; e->active_slots += e->group_active[g]; }
   e->h_fr_words[0] = e->fr_prev_done; e->h_fr_words[1] = e->active_slots;
-  return vm_grow(e, fr_ahead(e));                                   // what a slot can add before the next look
+  AZCHK(vm_grow(e, fr_ahead(e)));                                   // what a slot can add before the next look
+  e->report_fresh = !e->vm_rows && !dirty;                           // nothing launched since the report: its statistics sums are current
+  return AZ_OK;
 }
 template <class Gm> static int fr_step(az_engine* e, int nwaves) {
   for (int w = 0; w < nwaves; ++w) {
@@ -1558,11 +1616,15 @@ extern "C" int az_selfplay_get_stats(az_engine* e, az_selfplay_stats* s) {
   ENGINE(e);
   if (!s) return fail(AZ_ERR_BAD_ARG, "NULL");
   long long st[4] = {0, 0, 0, 0};
-  AZCHK(sync_groups(e));
-  e->h_stat.resize(e->stat_words);
-  HIPCHK(hipMemcpyAsync(e->h_stat.data(), e->gv[0].stat, sizeof(long long) * e->stat_words, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  for (size_t i = 0; i < e->stat_words; ++i) st[i & 3] += e->h_stat[i];
+  if (e->report_fresh) {                                            // right after a free-running step: its report holds the sums, the device is idle
+    for (int k = 0; k < 4; ++k) st[k] = e->h_report->stat[k];
+  } else {
+    AZCHK(sync_groups(e));
+    e->h_stat.resize(e->stat_words);
+    HIPCHK(hipMemcpyAsync(e->h_stat.data(), e->gv[0].stat, sizeof(long long) * e->stat_words, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (size_t i = 0; i < e->stat_words; ++i) st[i & 3] += e->h_stat[i];
+  }
   e->stats.simulations = st[0]; e->stats.nodes_traversed = st[1]; e->stats.leaf_evals = st[2]; e->stats.evals_reused = st[3];
   e->stats.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - e->t_begin).count();
   *s = e->stats;
@@ -1618,6 +1680,7 @@ extern "C" int az_selfplay_end(az_engine* e) {
   if (!e->running) return AZ_OK;
   AZCHK(reset_wave_state(e));                                      // an unfinished simulation (stepping form stopped mid-move) is dropped
   hipLaunchKernelGGL(k_slot_records, dim3((e->v.G + 255) / 256), dim3(256), 0, e->stream, e->v, (int)SR_CLEAR_ACTIVE);
+  e->report_fresh = false;
   HIPCHK(hipStreamSynchronize(e->stream));
   e->running = false;
   e->active_slots = 0;

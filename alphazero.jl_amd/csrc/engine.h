@@ -178,14 +178,21 @@ struct az_engine {
   // finished games into the phase buffer itself; the host looks every fr_round_waves waves (fr_round, azhip.hip)
   bool fr_on = false;                // the phase in progress is free-running
   int fr_k = 0, fr_kbg = 0, fr_round_waves = 0;  // simulations a slot may select per wave launch / per background launch (DView::run_k); waves between two looks of the host
-  hipStream_t fr_s[4] = {}; hipEvent_t fr_ev[4] = {};   // one slot group: the tree / network streams and events of its free-running phases (gs[0] / gt[0] / ev_* point at them meanwhile)
+  hipStream_t fr_s[4] = {}; hipEvent_t fr_ev[4] = {};   // one slot group: the streams and events of its free-running phases (gs[0] = gt[0] = fr_s[0] meanwhile): [0] the wave, [1] background search, [2] move step, [3] k_set_word behind a tower form that does not raise the stop word itself
   FRState* d_fr = nullptr; az_game_rec* d_done = nullptr; long long* d_done_off = nullptr; int done_cap = 0;
   int* h_busy = nullptr; int* d_busy = nullptr;      // [AZ_MAX_GROUPS] host-mapped: slots of each group still inside an explore! that runs ahead (DView::busy_host); -1 = no report
-  int* d_bg_stop = nullptr; int bg_seq = 0; bool bg_signal = false;   // the background search's stop word: set to bg_seq on the wave's stream once its tower has run (bg_signal: this wave has one)
+  int* d_bg_stop = nullptr; int bg_seq = 0; bool bg_signal = false;   // the background search's stop word: raised to bg_seq by the wave's tower near its end (paired forms) or by k_set_word behind it (bg_signal: this wave has one)
   int* h_fr_words = nullptr; int* d_fr_words = nullptr;  // host-mapped: finished games / searching slots as of the previous wave (FRArgs::host_words)
   int fr_prev_done = 0, fr_since_round = 0, fr_given_up = 0; long long fr_prev_recs = 0;
   int fr_look_waves = 0, fr_since_look = 0;      // mapped-on-demand pool: waves between two looks at the node counts (fr_look, azhip.hip; <= fr_round_waves) / since the last one
   std::vector<az_game_rec> h_done; std::vector<long long> h_done_off;
+  // the step report (tree.h StepReport, pinned and host-mapped: k_step_report writes it behind the wave, fr_round reads it after one
+  // synchronisation); report_fresh: no kernel has been launched since it was written, so az_selfplay_get_stats may take its sums from it
+  // (report_fresh holds only while EVERY launch that can write the statistics accumulators clears it: today that is k_tree alone, and all
+  // its launches go through LAUNCH_ON, which clears it, or through the graph replay in run_waves, which does so by hand.  A launch added
+  // outside the macro that touches DView::stat must clear it too.)
+  StepReport* h_report = nullptr; StepReport* d_report = nullptr; bool report_fresh = false;
+  char* h_fetch = nullptr;           // pinned staging of a look's finished games: records, offsets, move records (FETCH_BYTES; larger batches go straight to the vectors)
   std::vector<az_game_rec> q_games;
   std::vector<az_move_rec> q_moves;
   // device-resident records of the current phase (az_selfplay_run / begin with num_games > 0): the move records of every
@@ -283,6 +290,7 @@ inline int prof_end(az_engine* e, hipStream_t st, int cls) {
 #define LAUNCH_ON(e, st, cls, units, kern, grid, block, shmem, ...)         \
   do {                                                                      \
     AZCHK(prof_begin(e, st, cls, units));                                   \
+    (e)->report_fresh = false;                                              \
     hipLaunchKernelGGL(kern, dim3(grid), dim3(block), shmem, st, __VA_ARGS__); \
     AZCHK(prof_end(e, st, cls));                                            \
   } while (0)

@@ -15,13 +15,14 @@
 //            board for a whole tile; k_tower computes every tap).  az_prof.exec_units weighs a launch's boards with it, so that a roofline
 //            can count the work DONE instead of the dense convolution's
 //   HIST     its tower_hist bucket;  name(): its az_net_last_kernel spelling
+//   STOP     its kernel takes the background search's stop word (TowerIn::stop) and raises it from its last round of workgroups
 // set_kernel_attrs_f and launch_tower walk Forms<Gm, F>; a form's properties are stated nowhere else.
 template <class T> static constexpr double geo_frac() { return T::Geo::tab.cost / (9.0 * (T::RPAD / 16)); }
 // what the k_tower16 family of the fp32 network shares
 template <class T_, int ID_, bool OK_, int HIST_> struct FormFp32 {
   using T = T_;
   static constexpr int ID = ID_, HIST = HIST_;
-  static constexpr bool OK = OK_, BF16 = false;
+  static constexpr bool OK = OK_, BF16 = false, STOP = false;
   static const Net16Dev& net(const az_engine* e) { return e->net16; }
   static constexpr double frac() { return geo_frac<T>(); }
 };
@@ -35,6 +36,7 @@ template <class Gm, int F> struct FormSplit : FormFp32<T16S<Gm, F>, TW_SPLIT, F 
 };
 template <class Gm, int F, int NT0, int NT1, int ID_> struct FormPaired : FormFp32<T16P<Gm, F, NT0, NT1>, ID_, F == 64, 2> {
   template <bool FP> static constexpr auto K = &k_tower16x2<Gm, F, FP, NT0, NT1>;
+  static constexpr bool STOP = true;
   static void name(char* s, size_t n, const char* g) {
     if (NT0 == 11) snprintf(s, n, "k_tower16x2<%s,%d>", g, F);
     else snprintf(s, n, "k_tower16x2<%s,%d,NT=%d>", g, F, NT0 + NT1);
@@ -42,6 +44,7 @@ template <class Gm, int F, int NT0, int NT1, int ID_> struct FormPaired : FormFp
 };
 template <class Gm, int F> struct FormPairedC : FormFp32<T16P<Gm, F>, TW_P21C, F == 64, 2> {
   template <bool FP> static constexpr auto K = &k_tower16x2c<Gm, F, FP>;
+  static constexpr bool STOP = true;
   static void name(char* s, size_t n, const char* g) { snprintf(s, n, "k_tower16x2c<%s,%d>", g, F); }
 };
 // both paired forms in one launch (workgroups 0 .. first - 1 of T, the rest of T7); launched by wave_net_f only, never FROM_PLANES, and
@@ -54,7 +57,7 @@ template <class Gm, int F> struct FormMixed : FormFp32<T16P<Gm, F>, TW_MIXED, F 
 template <class Gm, int F> struct Form32 {
   struct T { static constexpr int TB = TOWER_ROWS / Gm::P, THREADS = TowerCfg<F>::THREADS, BYTES = TowerLds<F>::BYTES; };
   static constexpr int ID = TW_32, HIST = 3;
-  static constexpr bool OK = true, BF16 = false;
+  static constexpr bool OK = true, BF16 = false, STOP = false;
   template <bool FP> static constexpr auto K = &k_tower<Gm, F, FP>;
   static const NetDev& net(const az_engine* e) { return e->net; }
   static constexpr double frac() { return 1.0; }
@@ -63,7 +66,7 @@ template <class Gm, int F> struct Form32 {
 template <class Gm, int F, int NT, int ID_, int HIST_> struct Form16b {
   using T = T16B<Gm, F, NT>;
   static constexpr int ID = ID_, HIST = HIST_;
-  static constexpr bool OK = NT != 22 || F == 128, BF16 = true;
+  static constexpr bool OK = NT != 22 || F == 128, BF16 = true, STOP = false;
   template <bool FP> static constexpr auto K = &k_tower16b<Gm, F, FP, NT>;
   static const Net16bDev& net(const az_engine* e) { return e->net16b; }
   static constexpr double frac() { return geo_frac<T>(); }
@@ -250,7 +253,8 @@ static int launch_heads(az_engine* e, hipStream_t st, const float* hfeat, const 
 }
 // Where a tower launch finds its boards (envs[eslots[i]], device count in n_ptr; FROM_PLANES: X) and leaves the head features; xerr = the
 // error word a split tower's exchange reports to (e->v.err in the network seam, the group's DView::xerr in a wave)
-struct TowerIn { float* hfeat; const GEnv* envs; const int* eslots; const int* n_ptr; const float* X; int* xerr; };
+// stop / stop_val: the stop word of the background search this launch runs over and the value that raises it (forms with STOP; NULL: none)
+struct TowerIn { float* hfeat; const GEnv* envs; const int* eslots; const int* n_ptr; const float* X; int* xerr; int* stop = nullptr; int stop_val = 0; };
 static const char* game_name(const az_engine* e) {
   static const char* const gn[] = {"ConnectFour", "TicTacToe", "Mancala", "Go9Planes"};
   return gn[e->cfg.game];
@@ -268,7 +272,10 @@ template <class D, bool FROM_PLANES> static int launch_form(az_engine* e, hipStr
       AZCHK(xch_slot<typename T::Game>(e, in.hfeat, &xa, &ep));
       LAUNCH_ON(e, st, AZ_K_TOWER, n, (D::template K<FROM_PLANES>), T::SPLIT * tiles, T::THREADS, T::BYTES, D::net(e), in.envs, in.eslots, in.n_ptr, n, in.X, in.hfeat,
                 xa, ep, in.xerr, e->d_xflag);
-    } else
+    } else if constexpr (D::STOP)
+      LAUNCH_ON(e, st, AZ_K_TOWER, n, (D::template K<FROM_PLANES>), tiles, T::THREADS, T::BYTES, D::net(e), in.envs, in.eslots, in.n_ptr, n, in.X, in.hfeat,
+                in.stop, in.stop_val, e->num_cu > 0 ? e->num_cu : 256);
+    else
       LAUNCH_ON(e, st, AZ_K_TOWER, n, (D::template K<FROM_PLANES>), tiles, T::THREADS, T::BYTES, D::net(e), in.envs, in.eslots, in.n_ptr, n, in.X, in.hfeat);
     return AZ_OK;
   }
@@ -332,7 +339,10 @@ template <class Gm, int F> static int wave_net_f(az_engine* e, int g, bool split
       if (wgs > rounds * (cu - bg) - 14) tw = TW_P21C;
     }
   }
-  const TowerIn in{e->g_hfeat[g], v.leaf_env, eslots, nev, nullptr, v.xerr};
+  // the background search's stop word: a paired form raises it itself, from its last round of workgroups (resnet16.h tower16x2_body)
+  const bool tower_stops = e->bg_signal && F == 64 && !e->cfg.net_bf16 && (tw == TW_P21 || tw == TW_P19 || tw == TW_P21C);
+  TowerIn in{e->g_hfeat[g], v.leaf_env, eslots, nev, nullptr, v.xerr};
+  if (tower_stops) { in.stop = e->d_bg_stop; in.stop_val = e->bg_seq; }
   bool mixed = false;
   if constexpr (FormMixed<Gm, F>::OK) {
     // (r6, measured, off unless AZHIP_TOWER_MIXED=1) A batch between 15 and 16 boards per CU (a free-running wave's ~3800 boards at 4096 slots on
@@ -349,7 +359,7 @@ template <class Gm, int F> static int wave_net_f(az_engine* e, int g, bool split
       e->tower_hist[M::HIST]++;
       // the launch holds boards of both forms: price the executed fraction by their shares of the expected batch
       e->next_exec = (first * geo_frac<T8>() + (seen - first) * geo_frac<T7>()) / (double)seen;
-      LAUNCH_ON(e, sn, AZ_K_TOWER, N, (M::template K<false>), cu + (N - first + T7::TB - 1) / T7::TB, T8::THREADS, T8::BYTES, M::net(e), in.envs, in.eslots, in.n_ptr, N, in.X, in.hfeat, cu);
+      LAUNCH_ON(e, sn, AZ_K_TOWER, N, (M::template K<false>), cu + (N - first + T7::TB - 1) / T7::TB, T8::THREADS, T8::BYTES, M::net(e), in.envs, in.eslots, in.n_ptr, N, in.X, in.hfeat, cu, in.stop, in.stop_val);
     }
   }
   if (!mixed) AZCHK((launch_tower<Gm, F, false>(e, sn, tw, N, in)));
@@ -357,9 +367,9 @@ template <class Gm, int F> static int wave_net_f(az_engine* e, int g, bool split
   // (wave_group, azhip.hip) first queues the group's move step and its background search behind k_tree, then the wait for ev_net: both
   // run under this tower.
   const bool fr = e->fr_on && split;
-  if (e->bg_signal) {
-    // the tower has run: the background search of this wave winds up while the heads run.  The word is set from a stream of its own behind
-    // an event (a one-thread launch IN the wave's stream sat 7.6 us between tower and heads)
+  if (e->bg_signal && !tower_stops) {
+    // a form that does not raise the word itself.  The tower has run: the background search of this wave winds up while the heads run.  The
+    // word is set from a stream of its own behind an event (a one-thread launch IN the wave's stream sat 7.6 us between tower and heads)
     HIPCHK(hipEventRecord(e->fr_ev[3], sn));
     HIPCHK(hipStreamWaitEvent(e->fr_s[3], e->fr_ev[3], 0));
     hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, e->fr_s[3], e->d_bg_stop, e->bg_seq);

@@ -533,7 +533,8 @@ struct PairXch {
 template <class T, bool FROM_PLANES, int NT, int TILE0, class X = NoXch>
 __device__ __forceinline__ void tower16_wave(const Net16Dev& net, float* __restrict__ buf, const float* __restrict__ planes,
                                              const uint16_t* __restrict__ nbr, const uint16_t* __restrict__ pos, int cw,
-                                             int lane, int n, int board0, float* __restrict__ hfeat, const X& xch = X{}) {
+                                             int lane, int n, int board0, float* __restrict__ hfeat, const X& xch = X{},
+                                             int* stop = nullptr, int stop_val = 0) {
   using Gm = typename T::Game;
   using G = typename T::Geo;
   constexpr int F = T::FILT, P = Gm::P, C = Gm::C, TB = T::TB, STRIDE = T::STRIDE, R0 = TILE0 * 16;
@@ -650,6 +651,8 @@ __device__ __forceinline__ void tower16_wave(const Net16Dev& net, float* __restr
     if (layer == 1 || layer == 2) AZ_STAMP16(5 + layer);           // 6: layer 2 starts, 7: layer 2 done
   }
   AZ_STAMP16(2);
+  // the stop word of a free-running wave's background search (tower16x2_body): raised on the way into the head convolution
+  if (stop && threadIdx.x == 0) __hip_atomic_store(stop, stop_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   // ---- both 1x1 head convolutions + BN + ReLU as one F => F GEMM ------------------------------------
 #pragma unroll
   for (int t = 0; t < NT; ++t) acc[t] = f32x4v{0.f, 0.f, 0.f, 0.f};
@@ -721,9 +724,20 @@ k_tower16(Net16Dev net, const GEnv* __restrict__ leaf_env, const int* __restrict
 
 // The paired form (T16P): wavefronts 0..CT-1 run tiles 0..10, wavefronts CT..2CT-1 tiles 11..20 of ONE buffer.
 // one workgroup of the paired form on the boards board0 .. board0 + T::TB - 1
+// stop / stop_val (NULL: nothing): the stop word of the background search that a free-running wave runs under this launch (tree.h
+// DView::bg_stop).  The caller hands the pointer only to the workgroups of the launch's LAST round (paired_last_round), and lane 0 of
+// such a workgroup stores the value when it enters the head convolution, the last ~10 us of ITS work.  The last round's workgroups start
+// as CUs come free, so the first of them to get there raises the word 25-55 us before the LAUNCH ends (p10 - median of 400 headline
+// waves; most background launches have done their 32 simulations by then anyway -- the simulations per wave do not change: 8336 with
+// k_set_word, 8334 with this).  The background search (it polls once per simulation) winds up and hands its stream's event to the next
+// wave while the tower's tail and the heads run, so the join no longer trails the tower by a launch and two event hops: tower end to
+// next wave launch 49 -> 37-42 us.  (Raised a layer earlier, on the way into the last residual layer, ~40 us before the end, the wave was as
+// short but the background search lost 2 % of the wave's simulations: profiles/r7/README.md §1.)  Every such workgroup stores the same value
+// (relaxed, agent scope): whichever comes first raises the word, the others change nothing.
 template <class T, bool FROM_PLANES>
 __device__ __forceinline__ void tower16x2_body(const Net16Dev& net, const GEnv* __restrict__ leaf_env, const int* __restrict__ eval_slots, int n,
-                                               const float* __restrict__ X, float* __restrict__ hfeat, int board0, const uint16_t* __restrict__ geo) {
+                                               const float* __restrict__ X, float* __restrict__ hfeat, int board0, const uint16_t* __restrict__ geo,
+                                               int* stop = nullptr, int stop_val = 0) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* buf = lds;
   float* planes = lds + T::BUF;
@@ -732,18 +746,28 @@ __device__ __forceinline__ void tower16x2_body(const Net16Dev& net, const GEnv* 
   tower16_fill<T, FROM_PLANES>(buf, planes, nbr, pos, geo, leaf_env, eval_slots, X, n, board0, threadIdx.x);
   __syncthreads();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (wave < T::CT) tower16_wave<T, FROM_PLANES, T::NT0, 0>(net, buf, planes, nbr, pos, wave, lane, n, board0, hfeat);
+  if (wave < T::CT) tower16_wave<T, FROM_PLANES, T::NT0, 0>(net, buf, planes, nbr, pos, wave, lane, n, board0, hfeat, NoXch{}, stop, stop_val);
   else tower16_wave<T, FROM_PLANES, T::NT1, T::NT0>(net, buf, planes, nbr, pos, wave - T::CT, lane, n, board0, hfeat);
+}
+// the last round of a launch of nwg workgroups, one per CU: the workgroups from the last multiple of num_cu below nwg on.  (NOT every
+// workgroup without a successor num_cu places on: 475 workgroups on 256 CUs leave 37 of the FIRST round without one, and those are done
+// half a tower early.)
+// A launch whose device-side board count is 0 raises nothing -- every workgroup leaves before it gets here -- so the background search
+// under it runs its full count, where the one-thread launch behind the tower would have stopped it: a matter of time only, and only for
+// a wave without a single leaf (the last waves of a draining phase).
+__device__ __forceinline__ int* paired_last_round(int* stop, int wg, int nwg, int num_cu) {
+  return stop && wg >= (nwg - 1) / num_cu * num_cu ? stop : nullptr;
 }
 template <class Gm, int F, bool FROM_PLANES, int NT0 = 11, int NT1 = 10>
 __global__ void __launch_bounds__(2 * T16Threads<F>::V, 1)
 k_tower16x2(Net16Dev net, const GEnv* __restrict__ leaf_env, const int* __restrict__ eval_slots,
-            const int* __restrict__ n_eval_ptr, int n_fixed, const float* __restrict__ X, float* __restrict__ hfeat) {
+            const int* __restrict__ n_eval_ptr, int n_fixed, const float* __restrict__ X, float* __restrict__ hfeat,
+            int* stop, int stop_val, int num_cu) {
   using T = T16P<Gm, F, NT0, NT1>;
   const int n = FROM_PLANES ? n_fixed : *n_eval_ptr;
   const int board0 = blockIdx.x * T::TB;
   if (board0 >= n) return;
-  tower16x2_body<T, FROM_PLANES>(net, leaf_env, eval_slots, n, X, hfeat, board0, net.geo[T::GEO]);
+  tower16x2_body<T, FROM_PLANES>(net, leaf_env, eval_slots, n, X, hfeat, board0, net.geo[T::GEO], paired_last_round(stop, blockIdx.x, (n + T::TB - 1) / T::TB, num_cu), stop_val);
 }
 // (r6) The 8-board form within 176 registers per lane (the compiler takes 198 when it may: 92 B of scratch per lane here, +2 % per launch).
 // A free-running phase runs k_tree's background launch UNDER the tower (azhip.hip wave_group), and a k_tree wavefront (152 registers)
@@ -756,12 +780,13 @@ k_tower16x2(Net16Dev net, const GEnv* __restrict__ leaf_env, const int* __restri
 template <class Gm, int F, bool FROM_PLANES>
 __global__ void __launch_bounds__(2 * T16Threads<F>::V, 1) __attribute__((amdgpu_num_vgpr(88)))
 k_tower16x2c(Net16Dev net, const GEnv* __restrict__ leaf_env, const int* __restrict__ eval_slots,
-             const int* __restrict__ n_eval_ptr, int n_fixed, const float* __restrict__ X, float* __restrict__ hfeat) {
+             const int* __restrict__ n_eval_ptr, int n_fixed, const float* __restrict__ X, float* __restrict__ hfeat,
+             int* stop, int stop_val, int num_cu) {
   using T = T16P<Gm, F, 11, 10>;
   const int n = FROM_PLANES ? n_fixed : *n_eval_ptr;
   const int board0 = blockIdx.x * T::TB;
   if (board0 >= n) return;
-  tower16x2_body<T, FROM_PLANES>(net, leaf_env, eval_slots, n, X, hfeat, board0, net.geo[T::GEO]);
+  tower16x2_body<T, FROM_PLANES>(net, leaf_env, eval_slots, n, X, hfeat, board0, net.geo[T::GEO], paired_last_round(stop, blockIdx.x, (n + T::TB - 1) / T::TB, num_cu), stop_val);
 }
 // (r6) Both paired forms in ONE launch: workgroups 0 .. first - 1 take 8 boards each (21 row tiles), the workgroups behind them 7 (19 tiles).
 // A batch between 15 and 16 boards per CU -- a free-running wave's 3700-3840 boards on 256 CUs -- is two rounds of workgroups either
@@ -770,18 +795,21 @@ k_tower16x2c(Net16Dev net, const GEnv* __restrict__ leaf_env, const int* __restr
 template <class Gm, int F, bool FROM_PLANES>
 __global__ void __launch_bounds__(2 * T16Threads<F>::V, 1)
 k_tower16x2m(Net16Dev net, const GEnv* __restrict__ leaf_env, const int* __restrict__ eval_slots,
-             const int* __restrict__ n_eval_ptr, int n_fixed, const float* __restrict__ X, float* __restrict__ hfeat, int first) {
+             const int* __restrict__ n_eval_ptr, int n_fixed, const float* __restrict__ X, float* __restrict__ hfeat, int first,
+             int* stop, int stop_val) {
   using T8 = T16P<Gm, F, 11, 10>;
   using T7 = T16P<Gm, F, 10, 9>;
   const int n = FROM_PLANES ? n_fixed : *n_eval_ptr;
+  // (first = the number of CUs, at most `first` 7-board workgroups: they are the last round where there are any)
   if ((int)blockIdx.x < first) {
     const int board0 = blockIdx.x * T8::TB;
     if (board0 >= n) return;
-    tower16x2_body<T8, FROM_PLANES>(net, leaf_env, eval_slots, n, X, hfeat, board0, net.geo[T8::GEO]);
+    tower16x2_body<T8, FROM_PLANES>(net, leaf_env, eval_slots, n, X, hfeat, board0, net.geo[T8::GEO],
+                                    n <= first * T8::TB ? stop : nullptr, stop_val);
   } else {
     const int board0 = first * T8::TB + ((int)blockIdx.x - first) * T7::TB;
     if (board0 >= n) return;
-    tower16x2_body<T7, FROM_PLANES>(net, leaf_env, eval_slots, n, X, hfeat, board0, net.geo[T7::GEO]);
+    tower16x2_body<T7, FROM_PLANES>(net, leaf_env, eval_slots, n, X, hfeat, board0, net.geo[T7::GEO], stop, stop_val);
   }
 }
 

@@ -130,7 +130,7 @@ struct DView {
   int* eval_slots;        // [2][eval_stride] evaluation batch -> slot, double-buffered by wave parity like n_eval (a free-running phase's
                           // background search adds to the NEXT wave's batch while the network reads this wave's)
   int eval_stride;
-  const int* bg_stop; int bg_seq;   // background launch: leave when *bg_stop >= bg_seq -- the host's stream sets the word when the wave's tower has run (NULL: run to run_k)
+  const int* bg_stop; int bg_seq;   // background launch: leave when *bg_stop >= bg_seq -- the wave's tower raises the word near its end (a paired form: resnet16.h tower16x2_body) or a one-thread launch behind it does (NULL: run to run_k)
   int* bg_list; int* bg_cnt; // free-running: [2][eval_stride] / [2] the slots a wave's launch left without a question for the network (by wave parity):
                           // the background launch that follows serves exactly these -- a handful of wavefronts instead of one per 8 slots
   int* n_eval;            // [2] leaves of the wave, double-buffered by wave parity (k_tree zeroes the other one)
@@ -1148,6 +1148,17 @@ static __global__ void __launch_bounds__(256) k_slot_records(DView v, int what) 
 }
 // stream-ordered store of one word (the stop signal of a free-running phase's background search)
 static __global__ void k_set_word(int* p, int val) { __hip_atomic_store(p, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// The step report of a free-running phase: everything the host wants to know at a look (fr_round, azhip.hip), written by ONE workgroup
+// (k_step_report, azhip.hip) into pinned host memory in stream order behind the wave -- the phase's words, the error word, the sums of the per-workgroup statistics
+// records (64-bit integers: exact in any order; here record by record within a lane, then lane by lane) and the number of retired slots
+// (finished = 2).  drain (an unbounded phase: the host fetches everything the staging area holds at every look): the reservation word
+// goes back to 0 here, after it has been reported -- nothing reserves until the host launches the next wave, and it does that only after
+// it has fetched the records.  Not after an error: the host then leaves the phase as it is.
+struct StepReport {
+  FRState fr;
+  long long stat[4];
+  int err, retired;
+};
 // node counts of all slots, dense (the host maps pool chunks ahead of the slots, azhip.hip vm_grow)
 static __global__ void __launch_bounds__(256) k_node_counts(DView v, int* out) {
   const int slot = blockIdx.x * blockDim.x + threadIdx.x;
