@@ -202,6 +202,7 @@ SYMBOLS = {
     "az_engine_device_bytes": [_VP, C.POINTER(C.c_int64)],
     "az_engine_release_phase": [_VP],
     "az_comm_gather_push": [_VP, _VP, _VP, C.c_double, C.POINTER(GatherStats)],
+    "az_comm_gather_push_planes": [_VP, _VP, _VP, _VP, _VP, _I32, C.POINTER(GatherStats)],
     "az_comm_broadcast_params": [_VP, _VP, _I32],
     "az_minmax_cfg_init": [C.POINTER(MinMaxCfg)],
     "az_game_heuristic": [_VP, _VP, _I32, _VP],

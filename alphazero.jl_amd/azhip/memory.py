@@ -282,6 +282,7 @@ class PlaneMemoryBuffer:
         h = _C.c_void_p()
         _L.check(_L.lib().az_plane_memory_create(gspec.game_id, int(device), int(capacity), _C.byref(h)))
         self._h = h
+        self._batch = []                    # (game_id or None, len) of every trace pushed since new_batch: batch_games()
 
     def close(self):
         if getattr(self, "_h", None):
@@ -325,14 +326,24 @@ class PlaneMemoryBuffer:
         vp = lambda a: a.ctypes.data_as(_C.c_void_p) if a is not None else None
         _L.check(_L.lib().az_plane_memory_push_samples(self._h, cnt, vp(X), vp(A), vp(P), vp(z), vp(t), vp(nv)))
 
-    def push_trace(self, X, A, π, rewards, white_playing, gamma):
+    def push_trace(self, X, A, π, rewards, white_playing, gamma, game_id=None):
         """push_trace!(mem, trace, gamma) (memory.jl:74-87) for one game in playing order: the planes, mask and π of every position,
-        white's reward after every move and who was to move"""
+        white's reward after every move and who was to move.  game_id: the game's GLOBAL id, remembered with its length for the
+        current batch (batch_games; what Comm.gather_push_planes sends)"""
         cnt, X, A, P = self._arrays(X, A, π)
         r = self._vector("rewards", rewards, cnt, np.float64)
         wp = self._vector("white_playing", np.asarray(white_playing).astype(bool), cnt, np.uint8)
         vp = lambda a: a.ctypes.data_as(_C.c_void_p)
         _L.check(_L.lib().az_plane_memory_push_trace(self._h, cnt, vp(X), vp(A), vp(P), vp(r), vp(wp), float(gamma)))
+        if cnt > 0:
+            self._batch.append((None if game_id is None else int(game_id), cnt))
+
+    def batch_games(self):
+        """(game_ids, game_lens), int32: the traces pushed with a game_id since new_batch / empty, in push order.  ValueError if one
+        of the batch's traces came without an id"""
+        if any(g is None for g, _ in self._batch):
+            raise ValueError("the current batch holds traces pushed without a game_id")
+        return (np.array([g for g, _ in self._batch], dtype=np.int32), np.array([n for _, n in self._batch], dtype=np.int32))
 
     def _lens(self):
         a, b = _C.c_int64(), _C.c_int64()
@@ -357,9 +368,11 @@ class PlaneMemoryBuffer:
 
     def new_batch(self):
         _L.check(_L.lib().az_plane_memory_new_batch(self._h))
+        self._batch = []
 
     def empty(self):
         _L.check(_L.lib().az_plane_memory_empty(self._h))
+        self._batch = []
 
     def set_symmetries(self, xperm, aperm):
         """GI.symmetries of the host's game, declared once (they belong to the game, not to the samples): nsym gather permutations

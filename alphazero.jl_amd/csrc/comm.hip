@@ -9,6 +9,9 @@
 // their game records (56 B per game), straight from the engines' phase buffers into every rank's device buffer, and
 // push_trace! of all games in global game-id order into the rank's az_memory -- no record visits the host, only the
 // game records come back (they carry the counts).  az_comm_broadcast_params = ncclBroadcast of the parameter blob.
+// az_comm_gather_push_planes is the same exchange for a host-stepped game, whose samples are rows of planes in an az_plane_memory
+// (plane_memory.hip): the ranks' current batches travel as records of rb bytes, in rounds that bound the staging, and land in every
+// rank's destination memory in global game-id order (plane_gather.h has the plan, k_pg_pack / k_pg_scatter below move the rows).
 // RCCL is dlopen'ed by path next to the HIP runtime this library uses (a process that also imports PyTorch holds a second,
 // bundled RCCL: binding by soname could hand our communicator to that copy's HIP runtime), on first use only: single-GPU
 // users never load it.  The unique id travels between the processes by whatever the host has (Julia's Distributed, MPI,
@@ -23,6 +26,7 @@
 // is turned into a status word that travels with the first all-gather of a call, so all ranks leave together instead of one
 // rank returning while the others wait inside ncclAllGather for ever; a failing collective aborts the communicator.
 #include "engine.h"
+#include "plane_gather.h"
 
 #include <dlfcn.h>
 
@@ -100,8 +104,14 @@ struct az_comm {
   hipStream_t stream;
   // status / count words of the failure agreement, allocated ONCE at az_comm_init: a collective call must not be able to fail
   // locally (an allocation) before it has entered the first all-gather, or the other ranks would wait in it for ever
-  long long *d_word_send, *d_word_all;             // [3], [3 * world]
+  long long *d_word_send, *d_word_all;             // [COMM_WORDS], [COMM_WORDS * world]
+  // az_comm_gather_push_planes: rows per rank and round forced by az_debug_comm_plane_round_rows (0: the default), the events that
+  // time its kernels (created here for the same reason as the words) and the sums of its last call
+  int64_t plane_round_rows;
+  hipEvent_t ev[4];
+  double pack_ms, scatter_ms;
 };
+static constexpr int COMM_WORDS = 4;               // az_comm_gather_push_planes sends four (count, samples, status, geometry), the others three or one
 static_assert(sizeof(ncclUniqueId) == AZ_COMM_ID_BYTES, "ncclUniqueId size");
 
 extern "C" int az_comm_unique_id(uint8_t* id) {
@@ -130,6 +140,7 @@ extern "C" int az_comm_destroy(az_comm* c) {
   if (c->stream) (void)hipStreamDestroy(c->stream);
   if (c->d_word_send) (void)hipFree(c->d_word_send);
   if (c->d_word_all) (void)hipFree(c->d_word_all);
+  for (hipEvent_t ev : c->ev) if (ev) (void)hipEventDestroy(ev);
   delete c;
   return AZ_OK;
 }
@@ -147,10 +158,13 @@ extern "C" int az_comm_init(int32_t device, int32_t rank, int32_t world, const u
   if (!c) return fail(AZ_ERR_HIP, "out of host memory");
   c->comm = nullptr; c->rank = rank; c->world = world; c->device = device; c->stream = nullptr;
   c->d_word_send = c->d_word_all = nullptr;
+  c->plane_round_rows = 0; c->pack_ms = c->scatter_ms = 0.0;
+  for (hipEvent_t& ev : c->ev) ev = nullptr;
   int st = [&]() -> int {
     HIPCHK(hipStreamCreate(&c->stream));
-    HIPCHK(hipMalloc((void**)&c->d_word_send, 3 * sizeof(long long)));
-    HIPCHK(hipMalloc((void**)&c->d_word_all, (size_t)3 * world * sizeof(long long)));
+    HIPCHK(hipMalloc((void**)&c->d_word_send, COMM_WORDS * sizeof(long long)));
+    HIPCHK(hipMalloc((void**)&c->d_word_all, (size_t)COMM_WORDS * world * sizeof(long long)));
+    for (hipEvent_t& ev : c->ev) HIPCHK(hipEventCreate(&ev));
     ncclUniqueId u;
     memcpy(&u, id, sizeof u);
     RCCLCHK(rc::g.CommInitRank(&c->comm, world, u, rank));
@@ -368,4 +382,237 @@ extern "C" int az_comm_broadcast_params(az_comm* c, az_engine* e, int32_t root) 
   AZCHK(st);
   // Network.copy(nn; on_gpu = true, test_mode = true) on every rank: the kernels want their packed fragments
   return az_net_set_params(e, h.data(), n);
+}
+
+// ---- plane samples: az_comm_gather_push_planes ---------------------------------------------------------------------------------------
+// A record = [RW row words, padded to 8 bytes][ND doubles][n]: rb = pg::record_bytes bytes, 8-byte aligned.  Both kernels follow
+// k_pm_store: one wavefront per row, lanes over words.  V is the widest word both sides of the ROW copy are aligned to: ring rows are
+// 4 RW bytes apart, records rb bytes (uint4 for Tic-tac-toe, uint2 for Mancala and Go, one word for Connect Four's odd RW); the doubles
+// and n go as 8-byte words.
+template <typename V> struct PgVec { static constexpr int WORDS = (int)(sizeof(V) / 4); };
+
+// Row i of the round = row s = base + i of the rank's id-sorted batch: game g = find_game(prefix, s), batch sample j = src[g] + (s -
+// prefix[g]) in push order, ring slot (seq0 + j) % cap with seq0 = total - B (the batch may straddle the ring's end).
+template <typename V>
+__global__ void __launch_bounds__(64 * PM_WAVES) k_pg_pack(const float* __restrict__ XA, const double* __restrict__ D, const long long* __restrict__ N,
+                                                           long long cap, long long seq0, long long base, long long nrows,
+                                                           const long long* __restrict__ prefix, const long long* __restrict__ src, int ng,
+                                                           int RW, int ND, long long rb, unsigned char* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const long long i = (long long)blockIdx.x * PM_WAVES + (threadIdx.x >> 6);
+  if (i >= nrows) return;
+  const long long s = base + i;
+  const int g = pg::find_game(prefix, ng, s);
+  const size_t slot = (size_t)((seq0 + src[g] + (s - prefix[g])) % cap);
+  unsigned char* rec = out + (size_t)i * (size_t)rb;
+  const V* xs = (const V*)(XA + slot * RW);
+  V* xd = (V*)rec;
+  const int nv = RW / PgVec<V>::WORDS;
+  for (int w = lane; w < nv; w += 64) xd[w] = xs[w];
+  if ((RW & 1) && lane == 0) ((unsigned int*)rec)[RW] = 0u;          // the padding word travels as zero
+  const unsigned long long* ds = (const unsigned long long*)(D + slot * ND);
+  unsigned long long* dd = (unsigned long long*)rec + (RW + 1) / 2;
+  for (int w = lane; w < ND; w += 64) dd[w] = ds[w];
+  if (lane == 0) dd[ND] = (unsigned long long)N[slot];
+}
+// One wavefront per received row: segment r = row / R of the round holds rank r's rows [base, base + R) of ITS sorted batch, the ones
+// at or past B[r] being padding.  q = start[r][g] + offset is the sample's position in the id-ordered sequence of all T samples:
+// q < skip would be overwritten within this very call (k_pm_store's skip), the others land in slot (total + q) % cap.  q is a
+// bijection onto [0, T): no slot is written twice, no atomics.
+template <typename V>
+__global__ void __launch_bounds__(64 * PM_WAVES) k_pg_scatter(const unsigned char* __restrict__ in, long long R, long long base, int W,
+                                                              const long long* __restrict__ B, const long long* __restrict__ goff,
+                                                              const long long* __restrict__ prefix_all, const long long* __restrict__ start_all,
+                                                              long long skip, long long total, long long cap, int RW, int ND, long long rb,
+                                                              float* __restrict__ XA, double* __restrict__ D, long long* __restrict__ N) {
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * PM_WAVES + (threadIdx.x >> 6);
+  if (row >= (long long)W * R) return;
+  const int r = (int)(row / R);
+  const long long s = base + row % R;
+  if (s >= B[r]) return;
+  const long long g0 = goff[r];
+  const long long* prefix = prefix_all + g0 + r;                      // rank r's games + 1 prefix sums
+  const int g = pg::find_game(prefix, (int)(goff[r + 1] - g0), s);
+  const long long q = start_all[g0 + g] + (s - prefix[g]);
+  if (q < skip) return;
+  const size_t slot = (size_t)((total + q) % cap);
+  const unsigned char* rec = in + (size_t)row * (size_t)rb;
+  const V* xs = (const V*)rec;
+  V* xd = (V*)(XA + slot * RW);
+  const int nv = RW / PgVec<V>::WORDS;
+  for (int w = lane; w < nv; w += 64) xd[w] = xs[w];
+  const unsigned long long* ds = (const unsigned long long*)rec + (RW + 1) / 2;
+  unsigned long long* dd = (unsigned long long*)(D + slot * ND);
+  for (int w = lane; w < ND; w += 64) dd[w] = ds[w];
+  if (lane == 0) N[slot] = (long long)ds[ND];
+}
+
+extern "C" int az_debug_comm_plane_round_rows(az_comm* c, int64_t rows) {
+  if (!c) return fail(AZ_ERR_BAD_ARG, "NULL communicator");
+  if (rows < 0) return fail(AZ_ERR_BAD_ARG, "rows must be >= 0");
+  c->plane_round_rows = rows;
+  return AZ_OK;
+}
+extern "C" int az_debug_comm_plane_kernel_ms(az_comm* c, double* pack_ms, double* scatter_ms) {
+  if (!c) return fail(AZ_ERR_BAD_ARG, "NULL communicator");
+  if (pack_ms) *pack_ms = c->pack_ms;
+  if (scatter_ms) *scatter_ms = c->scatter_ms;
+  return AZ_OK;
+}
+
+extern "C" int az_comm_gather_push_planes(az_comm* c, az_plane_memory* src, az_plane_memory* dst, const int32_t* game_ids, const int32_t* game_lens,
+                                          int32_t num_games, az_gather_stats* stats) {
+  if (!c) return fail(AZ_ERR_BAD_ARG, "NULL communicator");
+  COMM_ALIVE(c);
+  if (hipSetDevice(c->device) != hipSuccess) { abort_comm(c); return fail(AZ_ERR_HIP, "hipSetDevice(%d) failed; communicator aborted", c->device); }
+  // local validation first; its verdict travels with the counts and the geometry (az_comm_gather_push)
+  long long B = 0;
+  int local = [&]() -> int {
+    if (!src) return fail(AZ_ERR_BAD_ARG, "NULL source memory");
+    if (dst == src) return fail(AZ_ERR_BAD_ARG, "the destination is the source memory: an outbox cannot receive its own batch");
+    if (src->device != c->device || (dst && dst->device != c->device)) return fail(AZ_ERR_BAD_ARG, "source / destination memory and communicator are on different devices");
+    if (dst && (dst->xs != src->xs || dst->nA != src->nA)) return fail(AZ_ERR_BAD_ARG, "source and destination memory differ in geometry (%d + %d and %d + %d words per row)", src->xs, src->nA, dst->xs, dst->nA);
+    if (num_games < 0 || (num_games > 0 && (!game_ids || !game_lens))) return fail(AZ_ERR_BAD_ARG, num_games < 0 ? "num_games must be >= 0" : "NULL game table");
+    for (int k = 0; k < num_games; ++k) {
+      if (game_lens[k] < 1) return fail(AZ_ERR_BAD_ARG, "game %d of the table (id %d) has length %d: must be >= 1", k, (int)game_ids[k], (int)game_lens[k]);
+      if (game_ids[k] < 0) return fail(AZ_ERR_BAD_ARG, "game %d of the table has the negative id %d", k, (int)game_ids[k]);
+      B += game_lens[k];
+    }
+    if (B != src->cur_batch) return fail(AZ_ERR_BAD_ARG, "the table's lengths sum to %lld, the source's current batch holds %lld samples", B, (long long)src->cur_batch);
+    if (B > src->cap) return fail(AZ_ERR_STATE, "the source's batch of %lld samples was partly overwritten (capacity %lld)", B, (long long)src->cap);
+    HIPCHK(hipStreamSynchronize(src->stream));
+    if (dst) HIPCHK(hipStreamSynchronize(dst->stream));
+    return AZ_OK;
+  }();
+  std::string local_msg = local != AZ_OK ? az_last_error() : "";
+  const auto t0 = std::chrono::steady_clock::now();
+  const int W = c->world;
+  const long long ng = local == AZ_OK ? num_games : 0;
+  if (local != AZ_OK) B = 0;
+  std::vector<void*> tmp;
+  bool in_collective = false;
+  c->pack_ms = c->scatter_ms = 0.0;
+  int st = [&]() -> int {
+    // 1. counts, status and geometry of every rank
+    long long hc[COMM_WORDS] = {ng, B, (long long)local, src ? ((long long)src->xs << 16) | (long long)src->nA : 0LL};
+    long long *d_send = c->d_word_send, *d_all = c->d_word_all;       // allocated at az_comm_init: nothing can fail before the all-gather
+    in_collective = true;
+    HIPCHK(hipMemcpyAsync(d_send, hc, sizeof hc, hipMemcpyHostToDevice, c->stream));
+    RCCLCHK(rc::g.AllGather(d_send, d_all, COMM_WORDS, ncclInt64, c->comm, c->stream));
+    std::vector<long long> all((size_t)COMM_WORDS * W);
+    HIPCHK(hipMemcpyAsync(all.data(), d_all, sizeof(long long) * all.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    in_collective = false;
+    if (local != AZ_OK) return fail(local, "%s", local_msg.c_str());   // a failing rank reports its own reason
+    long long maxg = 1, maxB = 1, totg = 0;
+    for (int r = 0; r < W; ++r) {
+      const long long* w = &all[(size_t)COMM_WORDS * r];
+      if (w[2] != AZ_OK) return fail(AZ_ERR_COMM, "rank %d cannot take part in the plane gather (status %lld); nothing was exchanged", r, w[2]);
+      maxg = std::max(maxg, w[0]); maxB = std::max(maxB, w[1]); totg += w[0];
+    }
+    for (int r = 1; r < W; ++r)
+      if (all[(size_t)COMM_WORDS * r + 3] != all[3]) return fail(AZ_ERR_BAD_ARG, "rank %d's plane geometry differs from rank 0's; nothing was exchanged", r);
+    const int RW = src->RW, ND = src->ND;
+    const long long rb = pg::record_bytes(RW, ND);
+    long long R = pg::default_round_rows(W, rb);
+    if (c->plane_round_rows > 0) R = std::min<long long>(R, c->plane_round_rows);
+    R = (maxB + (maxB + R - 1) / R - 1) / ((maxB + R - 1) / R);         // the same number of rounds, evenly filled: the last one sends little padding
+    // 2. buffers, sized by what all ranks hold together: a rank that cannot allocate them says so before anything is exchanged
+    pg::Game *d_tsend = nullptr, *d_tall = nullptr;
+    unsigned char *d_rsend = nullptr, *d_rall = nullptr;
+    long long *d_plan = nullptr;
+    const size_t n_prefix = (size_t)(totg + W), n_start = (size_t)std::max<long long>(totg, 1), n_src = (size_t)std::max<long long>(ng, 1);
+    const size_t n_plan = n_prefix + n_start + (size_t)(W + 1) + (size_t)W + n_src;   // prefix_all, start_all, goff, B, src
+    int ast = [&]() -> int {
+      AZCHK(mem_alloc(&tmp, &d_tsend, (size_t)maxg)); AZCHK(mem_alloc(&tmp, &d_tall, (size_t)maxg * W));
+      AZCHK(mem_alloc(&tmp, &d_rsend, (size_t)(R * rb))); AZCHK(mem_alloc(&tmp, &d_rall, (size_t)(R * rb) * W));
+      AZCHK(mem_alloc(&tmp, &d_plan, n_plan));
+      return AZ_OK;
+    }();
+    if (W > 1) {
+      std::string amsg = ast != AZ_OK ? az_last_error() : "";
+      int bad = -1;
+      in_collective = true;
+      AZCHK(agree(c, ast, d_send, d_all, &bad));
+      in_collective = false;
+      if (bad >= 0) return ast != AZ_OK ? fail(ast, "%s", amsg.c_str()) : fail(AZ_ERR_COMM, "rank %d could not allocate the gather buffers; nothing was exchanged", bad);
+    } else AZCHK(ast);
+    // 3. the game tables (8 B per game, padded to the largest rank), then the plan: the same on every rank
+    std::vector<pg::Game> tsend((size_t)maxg, pg::Game{0, 0});
+    for (long long k = 0; k < ng; ++k) tsend[(size_t)k] = pg::Game{game_ids[k], game_lens[k]};
+    std::vector<pg::Game> tall((size_t)maxg * W);
+    in_collective = true;
+    HIPCHK(hipMemcpyAsync(d_tsend, tsend.data(), sizeof(pg::Game) * tsend.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(d_rsend, 0, (size_t)(R * rb), c->stream));   // what a rank with nothing left sends
+    RCCLCHK(rc::g.AllGather(d_tsend, d_tall, (size_t)maxg, ncclInt64, c->comm, c->stream));
+    HIPCHK(hipMemcpyAsync(tall.data(), d_tall, sizeof(pg::Game) * tall.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    in_collective = false;
+    std::vector<std::vector<pg::Game>> tables((size_t)W);
+    for (int r = 0; r < W; ++r) tables[(size_t)r].assign(tall.begin() + (size_t)r * maxg, tall.begin() + (size_t)r * maxg + (size_t)all[(size_t)COMM_WORDS * r]);
+    const pg::Plan plan = pg::make_plan(tables, R, dst ? (long long)dst->cap : 0);
+    if (plan.dup) return fail(AZ_ERR_BAD_ARG, "game id %d occurs twice in the ranks' tables (ids are global and must be distinct); nothing was pushed", (int)plan.dup_id);
+    std::vector<long long> hplan(n_plan, 0);
+    long long *h_prefix = hplan.data(), *h_start = h_prefix + n_prefix, *h_goff = h_start + n_start, *h_B = h_goff + (W + 1), *h_src = h_B + W;
+    long long g0 = 0;
+    for (int r = 0; r < W; ++r) {
+      const pg::RankPlan& rp = plan.ranks[(size_t)r];
+      h_goff[r] = g0; h_B[r] = rp.B;
+      std::copy(rp.prefix.begin(), rp.prefix.end(), h_prefix + g0 + r);
+      std::copy(rp.start.begin(), rp.start.end(), h_start + g0);
+      g0 += (long long)rp.start.size();
+    }
+    h_goff[W] = g0;
+    const pg::RankPlan& mine = plan.ranks[(size_t)c->rank];
+    std::copy(mine.src.begin(), mine.src.end(), h_src);
+    const long long *d_prefix = d_plan, *d_start = d_prefix + n_prefix, *d_goff = d_start + n_start, *d_B = d_goff + (W + 1), *d_src = d_B + W;
+    const long long* d_myprefix = d_prefix + h_goff[c->rank] + c->rank;
+    // 4. rounds: pack -> all-gather -> scatter, R rows per rank; every rank runs plan.rounds of them
+    const int vec = (RW % 4 == 0 && rb % 16 == 0) ? 4 : RW % 2 == 0 ? 2 : 1;
+    const long long seq0 = src->total - B;
+    in_collective = true;
+    HIPCHK(hipMemcpyAsync(d_plan, hplan.data(), sizeof(long long) * n_plan, hipMemcpyHostToDevice, c->stream));
+    for (long long k = 0; k < plan.rounds; ++k) {
+      const long long base = k * R, nrows = pg::round_rows_of(plan, c->rank, k);
+      HIPCHK(hipEventRecord(c->ev[0], c->stream));
+      if (nrows > 0) {
+#define PG_PACK(V) hipLaunchKernelGGL(k_pg_pack<V>, dim3(pm_grid(nrows)), dim3(64 * PM_WAVES), 0, c->stream, src->d_XA, src->d_D, src->d_n, (long long)src->cap, \
+                                      seq0, base, nrows, d_myprefix, d_src, (int)ng, RW, ND, rb, d_rsend)
+        if (vec == 4) PG_PACK(uint4); else if (vec == 2) PG_PACK(uint2); else PG_PACK(unsigned int);
+#undef PG_PACK
+        HIPCHK(hipGetLastError());
+      }
+      HIPCHK(hipEventRecord(c->ev[1], c->stream));
+      RCCLCHK(rc::g.AllGather(d_rsend, d_rall, (size_t)(R * rb), ncclInt8, c->comm, c->stream));
+      HIPCHK(hipEventRecord(c->ev[2], c->stream));
+      if (dst && plan.T > plan.skip) {
+#define PG_SCATTER(V) hipLaunchKernelGGL(k_pg_scatter<V>, dim3(pm_grid((long long)W * R)), dim3(64 * PM_WAVES), 0, c->stream, d_rall, R, base, W, d_B, d_goff, \
+                                         d_prefix, d_start, plan.skip, (long long)dst->total, (long long)dst->cap, RW, ND, rb, dst->d_XA, dst->d_D, dst->d_n)
+        if (vec == 4) PG_SCATTER(uint4); else if (vec == 2) PG_SCATTER(uint2); else PG_SCATTER(unsigned int);
+#undef PG_SCATTER
+        HIPCHK(hipGetLastError());
+      }
+      HIPCHK(hipEventRecord(c->ev[3], c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));                          // the events and the send buffer are the next round's too
+      float pm = 0.f, sm = 0.f;
+      HIPCHK(hipEventElapsedTime(&pm, c->ev[0], c->ev[1]));
+      HIPCHK(hipEventElapsedTime(&sm, c->ev[2], c->ev[3]));
+      c->pack_ms += pm; c->scatter_ms += sm;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    in_collective = false;
+    if (dst) { dst->total += plan.T; dst->cur_batch += plan.T; }       // push_trace! of every game: mem.cur_batch_size += n
+    if (stats) {
+      memset(stats, 0, sizeof *stats);
+      stats->games = totg; stats->moves = plan.T; stats->ranks = W;
+      stats->bytes = (int64_t)W * (COMM_WORDS * 8 + maxg * (long long)sizeof(pg::Game) + plan.rounds * R * rb);
+      stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      stats->gather_ms = std::max(0.0, stats->total_ms - c->scatter_ms);  // everything but the push into the memory
+    }
+    return AZ_OK;
+  }();
+  if (st != AZ_OK && in_collective) abort_comm(c);
+  for (void* p : tmp) (void)hipFree(p);
+  return st;
 }

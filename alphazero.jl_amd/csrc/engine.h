@@ -357,6 +357,15 @@ struct az_plane_memory {
   int nsym;                          // 0: none declared
   unsigned short* d_perm;            // [AZ_PLANE_MAX_SYMMETRIES][RW], rows [0, nsym) valid
 };
+static constexpr int PM_WAVES = 4;    // wavefronts per workgroup of the plane kernels (plane_memory.hip, comm.hip): one sample / pair / group each
+static inline unsigned pm_grid(long long n) { return (unsigned)((n + PM_WAVES - 1) / PM_WAVES); }
+// Debug seams of comm.hip (not in azhip.h, no environment switch).  az_debug_comm_plane_round_rows: az_comm_gather_push_planes sends at
+// most `rows` records per rank and round (0: the default of plane_gather.h; never more than it) -- the same value on every rank.
+// az_debug_comm_plane_kernel_ms: HIP-event time of k_pg_pack and k_pg_scatter, summed over the rounds of the communicator's last
+// az_comm_gather_push_planes (tools/plane_gather_bench.py).
+struct az_comm;
+extern "C" int az_debug_comm_plane_round_rows(az_comm* c, int64_t rows);
+extern "C" int az_debug_comm_plane_kernel_ms(az_comm* c, double* pack_ms, double* scatter_ms);
 // the weight convert_samples gives a sample seen n times (learning.jl:17-25): every data-set builder's
 __device__ __forceinline__ float sample_weight(int policy, long long n) {
   return policy == AZ_WEIGHT_CONSTANT ? 1.0f : policy == AZ_WEIGHT_LOG ? (float)(az_log2((double)n) + 1.0) : (float)n;

@@ -25,9 +25,6 @@
 
 #define PLANE_MEMORY(m) if (!(m)) return fail(AZ_ERR_BAD_ARG, "plane memory is NULL"); HIPCHK(hipSetDevice((m)->device))
 
-static constexpr int PM_WAVES = 4;                                   // wavefronts per workgroup: one sample / pair / group each
-static inline unsigned pm_grid(long long n) { return (unsigned)((n + PM_WAVES - 1) / PM_WAVES); }
-
 // ---- push: check the staged samples, then store them into the ring ----------------------------------------------------------------
 enum { PM_NONFINITE = 1, PM_NVIS = 2, PM_A01 = 3, PM_NOLEGAL = 4, PM_PNEG = 5, PM_PILLEGAL = 6 };
 // One wavefront per sample, lanes over the words.  bad = the smallest (sample << 3 | clause) that failed (k_ds_check's encoding).

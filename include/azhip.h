@@ -657,6 +657,30 @@ int az_comm_destroy(az_comm* c);
  * where `m` is not NULL, runs push_trace! (src/memory.jl:74-87) for ALL games in global game-id order into m: every rank
  * that passes a memory ends up with the same samples a single-GPU run of all the games would have pushed. */
 int az_comm_gather_push(az_comm* c, az_engine* e, az_memory* m, double gamma, az_gather_stats* stats);
+/* az_comm_gather_push for a host-stepped game: collective over all ranks of c (same failure agreement).  `src` is this rank's outbox:
+ * its current batch is its newest B = sum(game_lens) samples, num_games consecutive runs in push order, run k being the game_lens[k]
+ * (>= 1) samples of game game_ids[k] (>= 0) as az_plane_memory_push_trace stored them.  B must equal the raw count push_trace has
+ * advanced since new_batch, and none of the batch may have been overwritten (B <= capacity); num_games = 0 with NULL arrays is a valid
+ * contribution.  Game ids are global and must be distinct over all ranks.  Where `dst` is not NULL it ends up as if ONE process had
+ * called az_plane_memory_push_trace on it for every game of every rank in ascending game id: the runs are appended in id order, the
+ * samples of a run keep the order src stores them in (push_trace has already reversed them), every word of X, A, pi, z, t and n is
+ * bit-identical, length and cur_batch_size advance by the total T over all ranks; when T exceeds dst's capacity only the newest
+ * `capacity` samples are stored, and the ring wraps where it must.  dst == NULL takes part and stores nothing; src is never modified;
+ * dst == src is refused.  src, dst and c must be on one device; src and dst must have one geometry, the same on every rank.
+ * Symmetries belong to a memory and are not transported; samples are not checked again (they were when pushed).
+ *   exchange   a sample travels device to device as one record of rb = 8 ceil(4 RW / 8) + 8 (nA + 2) + 8 bytes (RW = C*H*W + nA row
+ *              words padded to 8 bytes, the doubles, n: 2304 bytes for 9x9 Go), in rounds of at most R rows per rank with
+ *              W * R * rb <= 256 MiB of staging per rank; every rank runs ceil(max_r B_r / R) rounds.
+ *   failures   every local reason to refuse (NULL src, wrong device, geometry, B mismatch, an overwritten batch, a length < 1, an
+ *              id < 0) travels as a status word with the first all-gather, a failed allocation of the staging (sized by the largest
+ *              rank) with a second one: the failing rank returns its own error, the others AZ_ERR_COMM naming the rank, nothing is
+ *              exchanged and the communicator stays usable.  Ranks of different geometry: AZ_ERR_BAD_ARG on every rank.  A duplicate
+ *              game id, on one rank or across ranks, is found after the game tables have been gathered: every rank returns
+ *              AZ_ERR_BAD_ARG naming the id, and nothing is pushed anywhere.
+ *   stats      games, moves (= samples), bytes, gather_ms (everything but the push into dst), total_ms and ranks; the tree fields
+ *              and replaced_games are 0. */
+int az_comm_gather_push_planes(az_comm* c, az_plane_memory* src, az_plane_memory* dst, const int32_t* game_ids, const int32_t* game_lens,
+                               int32_t num_games, az_gather_stats* stats);
 /* Collective (same failure agreement as az_comm_gather_push).  ncclBroadcast of `root`'s parameter blob, then az_net_set_params on every rank (the network shipped to the
  * workers before a phase, src/training.jl:278-282). */
 int az_comm_broadcast_params(az_comm* c, az_engine* e, int32_t root);

@@ -287,5 +287,6 @@ const UNBOUND = Dict(
   :az_plane_memory_set_symmetries => "see az_plane_memory_create; a Julia host has GI.symmetries and the reference's augment_with_symmetries",
   :az_plane_memory_num_symmetries => "see az_plane_memory_create",
   :az_dataset_create_from_plane_memory_sym => "builds from an az_plane_memory, which is unbound (see az_plane_memory_create)",
+  :az_comm_gather_push_planes => "gathers from and into an az_plane_memory, which is unbound (see az_plane_memory_create)",
 )
 
