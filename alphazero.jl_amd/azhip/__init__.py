@@ -18,6 +18,7 @@ from . import solver as Solver
 from . import pons as Pons
 from .play import MctsPlayer, NetworkPlayer, PlayerWithTemperature, TwoPlayers, flipped_colors, play_game
 from .trace import Trace
+from .host_tree import HostSteppedEnv, HostTree
 from .memory import Dataset, MemoryBuffer, PlaneMemoryBuffer, TensorDataset, TrainingSample, push_trace
 from .simulations import Simulator, record_trace, self_play_measurements, simulate, simulate_distributed
 from .training import SelfPlayParams, SelfPlayReport, broadcast_params, self_play_step

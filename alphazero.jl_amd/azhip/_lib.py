@@ -114,6 +114,31 @@ class SolverCfg(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("weak", C.c_int32), ("node_budget", C.c_int64)]
 
 
+HOST_TREE_MAX_ACTIONS = 128                 # AZ_HOST_TREE_MAX_ACTIONS
+HT_PLAY, HT_ROOT, HT_FULL, HT_DEPTH = 0, 1, 2, 3   # az_host_tree_request_kind
+
+
+class HostTreeCfg(C.Structure):
+    """az_host_tree_cfg: the MctsParams the device trees of a host-stepped game use"""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("gamma", C.c_double), ("cpuct", C.c_double),
+                ("dirichlet_noise_eps", C.c_double), ("dirichlet_noise_alpha", C.c_double), ("prior_temperature", C.c_double),
+                ("seed", C.c_uint64)]
+
+
+class HostTreeRequest(C.Structure):
+    _fields_ = [("worker", C.c_int32), ("node", C.c_int32), ("action", C.c_int32), ("kind", C.c_int32)]
+
+
+class HostTreeReply(C.Structure):
+    _fields_ = [("key", C.c_uint64 * 2), ("white_reward", C.c_float), ("terminal", C.c_uint8), ("white_playing", C.c_uint8),
+                ("reserved", C.c_uint8 * 2)]
+
+
+class HostTreeStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("simulations", "nodes_traversed", "evaluations", "transposition_hits", "sims_without_host",
+                                         "max_nodes", "max_edge_slots", "max_path", "steps")]
+
+
 PROGRESS_CB = C.CFUNCTYPE(None, C.c_void_p)
 
 # every symbol include/azhip.h declares: name -> argtypes (restype is int unless noted)
@@ -217,13 +242,22 @@ SYMBOLS = {
     "az_solver_table_clear": [_VP],
     "az_solver_table_info": [_VP, C.POINTER(_I32), C.POINTER(_I64), C.POINTER(_I64)],
     "az_c4_solve_table": [_VP, C.POINTER(SolverCfg), _VP, _VP, _I32, _VP, _VP, _VP],
+    "az_host_tree_cfg_init": [C.POINTER(HostTreeCfg)],
+    "az_host_tree_create": [_VP, _I32, _I32, _I32, _I32, _I32, _I32, C.POINTER(HostTreeCfg), C.POINTER(_VP)],
+    "az_host_tree_destroy": [_VP],
+    "az_host_tree_explore": [_VP, _I32, _VP, _VP, _VP, _I32],
+    "az_host_tree_step": [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(_I32), _VP],
+    "az_host_tree_root_stats": [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP],
+    "az_host_tree_advance": [_VP, _I32, _VP, _VP],
+    "az_host_tree_reset": [_VP, _I32, _VP],
+    "az_host_tree_get_stats": [_VP, C.POINTER(HostTreeStats)],
 }
 
 # az_struct_id order of include/azhip.h
 STRUCTS = [("az_engine_cfg", EngineCfg), ("az_move_rec", MoveRec), ("az_game_rec", GameRec), ("az_trace_buf", TraceBuf),
            ("az_selfplay_stats", SelfplayStats), ("az_sample", Sample), ("az_dataset_info", DatasetInfo),
            ("az_learning_status_t", LearningStatusRec), ("az_train_cfg", TrainCfg), ("az_gather_stats", GatherStats), ("az_prof", Prof),
-           ("az_minmax_cfg", MinMaxCfg), ("az_solver_cfg", SolverCfg)]
+           ("az_minmax_cfg", MinMaxCfg), ("az_solver_cfg", SolverCfg), ("az_host_tree_cfg", HostTreeCfg), ("az_host_tree_stats", HostTreeStats)]
 _lib = None
 
 

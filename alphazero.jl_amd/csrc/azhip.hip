@@ -35,6 +35,8 @@ extern "C" int az_abi_struct_size(int32_t which) {
     case AZ_STRUCT_PROF: return (int)sizeof(az_prof);
     case AZ_STRUCT_MINMAX_CFG: return (int)sizeof(az_minmax_cfg);
     case AZ_STRUCT_SOLVER_CFG: return (int)sizeof(az_solver_cfg);
+    case AZ_STRUCT_HOST_TREE_CFG: return (int)sizeof(az_host_tree_cfg);
+    case AZ_STRUCT_HOST_TREE_STATS: return (int)sizeof(az_host_tree_stats);
   }
   return -1;
 }
@@ -796,6 +798,9 @@ static int seam_launch(az_engine* e, bool from_planes, int m) {
   if (split_gave_up(e)) AZCHK(launch());
   return AZ_OK;
 }
+
+// host_tree.hip: the seam on the m rows already in d_X / d_A (the launch az_net_forward makes), results in d_P / d_V
+int net_seam_planes(az_engine* e, int m) { return seam_launch(e, true, m); }
 
 extern "C" int az_net_forward(az_engine* e, const float* X, const float* A, int32_t N, float* P, float* V, float* Pinv) {
   ENGINE(e);

@@ -303,6 +303,10 @@ inline int prof_end(az_engine* e, hipStream_t st, int cls) {
 // azhip.hip: waits for the engine's streams and turns a device-side error code (tree.h DERR_*, resnet16.h DERR_EXCHANGE) into a status
 int check_device_error(az_engine* e);
 
+// azhip.hip: one launch of the network seam on the engine's stream over the m <= nn_cap rows in d_X / d_A (what az_net_forward launches); P in d_P
+// (stride gi.A), V in d_V.  The device trees of a host-stepped game (host_tree.hip) evaluate their new states with it.
+int net_seam_planes(az_engine* e, int m);
+
 // azhip.hip: how many streams of this process may launch split towers on `device` at the same time (all engines with 128 filters)
 int split_streams_on_device(int device);
 

@@ -17,7 +17,14 @@
 //   g++ -O2 -std=c++17 -Iinclude examples/host_stepped_go9.cpp -Lalphazero.jl_amd/csrc -lazhip -lpthread ...
 //       -Wl,-rpath,$PWD/alphazero.jl_amd/csrc -o examples/host_stepped_go9      (or: make -C examples)
 //   examples/host_stepped_go9 [--workers 512] [--sims 1600] [--seconds 8] [--threads 0=all usable] [--arena-gb 0=auto] [--fp32] [--blocks 10] [--filters 128]
-//                             [--train-steps 0]
+//                             [--train-steps 0] [--device-trees [--tree-gb 48]]
+//
+// --device-trees (off by default) moves the search trees into HBM (az_host_tree_*, engine mode): the device selects, expands, backs
+// up and evaluates new states; the host keeps only `Go` states by (worker, node id) and answers "play this action in this node's
+// state" -- one play + encode per simulation at most instead of one per ply, and P / V never cross the bus.  Same workers, same
+// moves rule, same network; the JSON line says "mode": "device-trees" and adds the time inside az_host_tree_step, the HIP-event
+// time of its tree kernels and the tree's own statistics.  The workers form two halves, each with its own engine and tree, that take turns
+// between the device and the host as they do with host trees.
 //
 // --train-steps N closes the iteration on the GPU: the positions of the games that FINISHED during play become the (W, X, A, P, V)
 // tensors of convert_samples (src/learning.jl:17-51: constant weights, the visit frequencies of the move's search, the game's
@@ -254,7 +261,7 @@ struct Worker {
   }
 };
 
-struct Opt { bool dry = false; int workers = 512, sims = 1600, threads = 0, blocks = 10, filters = 128, bf16 = 1, train_steps = 0; double seconds = 8.0, cpuct = 2.0, eps = 0.25, alpha = 0.03, arena_gb = 0.0; };
+struct Opt { bool dry = false; int workers = 512, sims = 1600, threads = 0, blocks = 10, filters = 128, bf16 = 1, train_steps = 0; double seconds = 8.0, cpuct = 2.0, eps = 0.25, alpha = 0.03, arena_gb = 0.0; bool device_trees = false; double tree_gb = 48.0; };
 
 // select (mcts.jl:199-217) until an unseen or a terminal state
 void descend(Worker& w, const Opt& o) {
@@ -422,6 +429,188 @@ int usable_threads() {
   return std::min(n, 64);
 }
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// ---- --device-trees: the trees live in HBM (az_host_tree_*, engine mode); the host keeps Go states by node id and answers requests
+extern "C" int az_debug_host_tree_profile(az_host_tree* t, int32_t on);                          // debug seams of csrc/host_tree.hip:
+extern "C" int az_debug_host_tree_kernel_ms(az_host_tree* t, double* ms, int64_t* steps);        // HIP-event time of a step's tree kernels
+struct DWorker {
+  Go root;
+  std::vector<Go> states;      // by node id of this worker's device tree
+  std::mt19937_64 rng;
+  uint32_t game_id = 0;
+  long long games = 0, moves = 0;
+};
+// One half of the workers: its own engine (stream, network buffers) and tree, so that a helper thread can sit in its
+// az_host_tree_step while the pool answers the other half's requests -- the seam's two sides overlap as they do with host trees.
+struct Half {
+  az_engine* e = nullptr; az_host_tree* t = nullptr;
+  int lo = 0, cnt = 0, nrep = 0, nreq = 0, status = AZ_OK;
+  double call_s = 0;
+  std::vector<int32_t> newn, act, fin, adv, adv_a, rst, arm, pend_w, rslot, rN;
+  std::vector<uint32_t> ug, um;
+  std::vector<az_host_tree_request> req;
+  std::vector<az_host_tree_reply> rep;
+  std::vector<float> X, M;
+  std::vector<Go> pend;
+  std::vector<uint8_t> asked;
+  void size(int n) {
+    cnt = n; newn.resize(n); act.resize(n); pend_w.resize(n); rslot.resize(n); rN.resize((size_t)n * A); ug.resize(n); um.resize(n); req.resize(n); rep.resize(n);
+    X.resize((size_t)n * C * P); M.resize((size_t)n * A); pend.resize(n); asked.resize(n);
+  }
+};
+int run_device_trees(const Opt& o, az_engine* const engines[2], Pool& pool) {
+  const int W = o.workers;
+  // per node: 82 edge slots of 31 bytes, the node's 29 bytes, two table entries
+  const double per_node = (double)A * 31 + 29 + 8;
+  const int nodes = (int)std::max(256.0, std::min(1048576.0, o.tree_gb * 1073741824.0 / W / per_node));
+  az_host_tree_cfg tc;
+  if (az_host_tree_cfg_init(&tc) != AZ_OK) return 1;
+  tc.cpuct = o.cpuct; tc.dirichlet_noise_eps = o.eps; tc.dirichlet_noise_alpha = o.alpha; tc.seed = 2026;
+  std::vector<DWorker> ws((size_t)W);
+  for (int i = 0; i < W; ++i) { ws[i].rng.seed(1000 + i); ws[i].root.reset(); ws[i].game_id = (uint32_t)i; }
+  Half hv[2];
+  auto destroy = [&] { for (Half& h : hv) if (h.t) az_host_tree_destroy(h.t); };
+  auto fail_tree = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, az_last_error()); destroy(); return 1; };
+  hv[0].lo = 0; hv[0].size(W / 2); hv[1].lo = W / 2; hv[1].size(W - W / 2);
+  for (int k = 0; k < 2; ++k) {
+    hv[k].e = engines[k];
+    if (az_host_tree_create(hv[k].e, 0, A, hv[k].cnt, nodes, nodes * A, 2 * P + 2, &tc, &hv[k].t) != AZ_OK) return fail_tree("az_host_tree_create");
+    az_debug_host_tree_profile(hv[k].t, 1);
+  }
+  // workers of a half are numbered from 0 in its tree
+  auto explore = [&](Half& h, const std::vector<int32_t>& who) {
+    for (size_t k = 0; k < who.size(); ++k) { h.ug[k] = ws[h.lo + who[k]].game_id; h.um[k] = (uint32_t)ws[h.lo + who[k]].root.nmoves; }
+    return who.empty() ? (int)AZ_OK : az_host_tree_explore(h.t, (int32_t)who.size(), who.data(), h.ug.data(), h.um.data(), o.sims);
+  };
+  // the blocking call (helper thread): absorb the half's replies, carry its workers to their next questions
+  auto step = [&](Half& h) {
+    const double c0 = now();
+    h.status = az_host_tree_step(h.t, h.nrep, h.rep.data(), h.X.data(), h.M.data(), nullptr, nullptr, h.req.data(), &h.nreq, h.newn.data());
+    if (h.status != AZ_OK) fprintf(stderr, "az_host_tree_step: %s\n", az_last_error());
+    h.call_s = now() - c0;
+  };
+  // the host's share after a step: keep the new states, play the moves of the workers whose search is complete, answer the requests
+  auto answer = [&](Half& h) -> int {
+    pool.run(h.nrep, [&](int i) {
+      if (h.newn[i] < 0) return;
+      std::vector<Go>& st = ws[h.lo + h.pend_w[i]].states;
+      if (st.size() <= (size_t)h.newn[i]) st.resize((size_t)h.newn[i] + 1);
+      st[(size_t)h.newn[i]] = h.pend[i];
+    });
+    std::fill(h.asked.begin(), h.asked.end(), 0);
+    h.fin.clear(); h.adv.clear(); h.adv_a.clear(); h.rst.clear(); h.arm.clear();
+    h.nrep = 0;
+    int stopped = 0;
+    for (int k = 0; k < h.nreq; ++k) {
+      h.asked[h.req[k].worker] = 1;
+      if (h.req[k].kind == AZ_HT_FULL || h.req[k].kind == AZ_HT_DEPTH) { h.rst.push_back(h.req[k].worker); h.arm.push_back(h.req[k].worker); ++stopped; h.rslot[k] = -1; }
+      else h.rslot[k] = h.nrep++;
+    }
+    for (int i = 0; i < h.cnt; ++i) if (!h.asked[i]) h.fin.push_back(i);
+    if (!h.fin.empty()) {
+      if (az_host_tree_root_stats(h.t, (int32_t)h.fin.size(), h.fin.data(), h.rN.data(), nullptr, nullptr, nullptr, nullptr) != AZ_OK) return -1;
+      pool.run((int)h.fin.size(), [&](int k) {                     // policy + move as make_move: temperature 1 for 20 moves, then the most visited
+        DWorker& w = ws[h.lo + h.fin[k]];
+        const int32_t* Nv = &h.rN[(size_t)k * A];
+        long long tot = 0;
+        for (int a = 0; a < A; ++a) tot += Nv[a];
+        int a = PASS;
+        if (tot > 0) {
+          if (w.root.nmoves < 20) {
+            std::uniform_real_distribution<double> u(0.0, 1.0);
+            const double x = u(w.rng) * (double)tot; double c = 0;
+            int last = PASS;
+            for (int b = 0; b < A; ++b) { if (!Nv[b]) continue; last = b; c += Nv[b]; if (c > x) break; }
+            a = last;
+          } else a = (int)(std::max_element(Nv, Nv + A) - Nv);
+        }
+        w.root.play(a); w.moves++;
+        h.act[h.fin[k]] = a;
+      });
+      for (int32_t i : h.fin) {
+        DWorker& w = ws[h.lo + i];
+        if (w.root.over()) { w.root.reset(); w.games++; w.game_id += (uint32_t)W; h.rst.push_back(i); }   // reset_every = 1
+        else { h.adv.push_back(i); h.adv_a.push_back(h.act[i]); }
+        h.arm.push_back(i);
+      }
+    }
+    for (int32_t i : h.rst) ws[h.lo + i].states.clear();
+    if (!h.adv.empty() && az_host_tree_advance(h.t, (int32_t)h.adv.size(), h.adv.data(), h.adv_a.data()) != AZ_OK) return -1;
+    if (!h.rst.empty() && az_host_tree_reset(h.t, (int32_t)h.rst.size(), h.rst.data()) != AZ_OK) return -1;
+    if (explore(h, h.arm) != AZ_OK) return -1;
+    pool.run(h.nreq, [&](int k) {                                  // the answers: one play + encode per request
+      const int r = h.rslot[k];
+      if (r < 0) return;
+      DWorker& w = ws[h.lo + h.req[k].worker];
+      Go g = h.req[k].kind == AZ_HT_ROOT ? w.root : w.states[(size_t)h.req[k].node];
+      if (h.req[k].kind == AZ_HT_PLAY) g.play(h.req[k].action);
+      az_host_tree_reply& y = h.rep[r];
+      y.key[0] = g.key(); y.key[1] = (uint64_t)g.nmoves; y.white_reward = (float)g.white_reward(); y.terminal = g.over(); y.white_playing = g.to_play == 1;
+      y.reserved[0] = y.reserved[1] = 0;
+      if (!y.terminal) g.planes(&h.X[(size_t)r * C * P], &h.M[(size_t)r * A]);
+      h.pend[r] = g; h.pend_w[r] = h.req[k].worker;
+    });
+    return stopped;
+  };
+  std::vector<int32_t> all;
+  for (Half& h : hv) { all.resize((size_t)h.cnt); for (int i = 0; i < h.cnt; ++i) all[i] = i; if (explore(h, all) != AZ_OK) return fail_tree("az_host_tree_explore"); }
+  long long full_resets = 0, steps = 0, requests = 0;
+  double t_step = 0, t_host = 0, t_wait = 0, t_meas0 = 0;
+  az_host_tree_stats s0[2] = {}, s1[2] = {};
+  double k0[2] = {0, 0}, k1[2] = {0, 0}; int64_t ks0[2] = {0, 0}, ks1[2] = {0, 0};
+  bool warm = true, have[2] = {false, false};
+  Helper helper;
+  const double t_start = now();
+  for (;;) {
+    double host = 0, wait = 0;
+    for (int k = 0; k < 2; ++k) {
+      // the device on half k, the host on the other half
+      Half& h = hv[k]; Half& other = hv[1 - k];
+      helper.start([&] { step(h); });
+      const double a0 = now();
+      if (have[1 - k]) { const int r = answer(other); if (r < 0) { helper.wait(); return fail_tree("device trees"); } full_resets += r; have[1 - k] = false; }
+      const double a1 = now();
+      helper.wait();
+      const double a2 = now();
+      if (h.status != AZ_OK) { destroy(); return 1; }
+      have[k] = true;
+      host += a1 - a0; wait += a2 - a1;
+      ++steps; requests += h.nrep; t_step += h.call_s;
+    }
+    const double t4 = now();
+    if (warm) {
+      if (t4 - t_start > std::min(2.0, 0.25 * o.seconds)) {
+        warm = false; t_meas0 = t4; t_step = t_host = t_wait = 0; steps = requests = 0;
+        for (int k = 0; k < 2; ++k) { az_host_tree_get_stats(hv[k].t, &s0[k]); az_debug_host_tree_kernel_ms(hv[k].t, &k0[k], &ks0[k]); }
+      }
+      continue;
+    }
+    t_host += host; t_wait += wait;
+    if (t4 - t_meas0 >= o.seconds) break;
+  }
+  const double wall = now() - t_meas0;
+  long long games = 0, moves = 0, sims = 0, trav = 0, evals = 0, thits = 0, nohost = 0, maxn = 0, ksteps = 0;
+  double kms = 0;
+  for (int k = 0; k < 2; ++k) {
+    az_host_tree_get_stats(hv[k].t, &s1[k]); az_debug_host_tree_kernel_ms(hv[k].t, &k1[k], &ks1[k]);
+    sims += s1[k].simulations - s0[k].simulations; trav += s1[k].nodes_traversed - s0[k].nodes_traversed; evals += s1[k].evaluations - s0[k].evaluations;
+    thits += s1[k].transposition_hits - s0[k].transposition_hits; nohost += s1[k].sims_without_host - s0[k].sims_without_host;
+    maxn = std::max<long long>(maxn, s1[k].max_nodes); kms += k1[k] - k0[k]; ksteps += ks1[k] - ks0[k];
+  }
+  for (auto& w : ws) { games += w.games; moves += w.moves; }
+  char kernel[96] = "";
+  az_net_last_kernel(engines[0], kernel, sizeof kernel);
+  printf("{\"mode\": \"device-trees\", \"workload\": \"9x9 Go-shaped host game (stand-in rules, 82 actions, 9x9x4 planes), device trees (az_host_tree, engine mode, two halves that take turns) answered by %d host threads, %d workers, %d sims/move, ResNet %dx%d %s\", "
+         "\"value\": %.1f, \"unit\": \"sims/s\", \"seconds\": %.2f, \"host_busy_share\": %.3f, \"step_wait_share\": %.3f, \"step_call_share\": %.3f, \"tree_kernel_ms_per_step\": %.4f, \"tree_kernel_share\": %.4f, "
+         "\"steps\": %lld, \"requests_per_step\": %.1f, \"boards_per_launch\": %.1f, \"avg_exploration_depth\": %.2f, \"evaluations\": %lld, \"transposition_hits\": %lld, "
+         "\"sims_without_host\": %lld, \"games_finished\": %lld, \"moves\": %lld, \"largest_tree_nodes\": %lld, \"nodes_per_worker\": %d, \"tree_full_resets\": %lld, \"kernel\": \"%s\", \"threads\": %d, "
+         "\"rules\": \"host stand-in, NOT OpenSpiel's (absent from the reference tree): no parity claim\"}\n",
+         o.threads, W, o.sims, o.blocks, o.filters, o.bf16 ? "bf16" : "fp32", sims / wall, wall, t_host / wall, t_wait / wall, t_step / wall,
+         ksteps ? kms / (double)ksteps : 0.0, kms * 1e-3 / wall, steps, steps ? (double)requests / steps : 0.0, steps ? (double)evals / steps : 0.0,
+         sims ? (double)trav / sims : 0.0, evals, thits, nohost, games, moves, maxn, nodes, full_resets, kernel, o.threads);
+  destroy();
+  return 0;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -433,6 +622,8 @@ int main(int argc, char** argv) {
     else if (is("--arena-gb")) o.arena_gb = atof(argv[++i]);
     else if (is("--blocks")) o.blocks = atoi(argv[++i]); else if (is("--filters")) o.filters = atoi(argv[++i]);
     else if (is("--train-steps")) o.train_steps = atoi(argv[++i]);
+    else if (is("--tree-gb")) o.tree_gb = atof(argv[++i]);
+    else if (!strcmp(argv[i], "--device-trees")) o.device_trees = true;
     else if (!strcmp(argv[i], "--fp32")) o.bf16 = 0;
     else if (!strcmp(argv[i], "--dry")) o.dry = true;            // no GPU: MCTS.RandomOracle in place of the network (host ceiling, CPU tests)
     else { fprintf(stderr, "unknown option %s\n", argv[i]); return 1; }
@@ -440,6 +631,7 @@ int main(int argc, char** argv) {
   // a phase is workers x ~10 us of work: beyond ~64 workers per thread the synchronisation costs more than the threads bring
   // (1024 workers on the 256-CPU MI355X host: 16 threads 0.98 M sims/s, 32: 0.86 M, 64: 0.37 M)
   if (o.threads <= 0) o.threads = std::max(1, std::min({usable_threads(), 16, o.workers / 64}));
+  if (o.device_trees && (o.dry || o.train_steps > 0)) { fprintf(stderr, "--device-trees keeps the trees on the GPU: it runs neither with --dry nor with --train-steps\n"); return 1; }
   init_zobrist();
   az_engine_cfg cfg;
   az_engine* e = nullptr;
@@ -451,9 +643,10 @@ int main(int argc, char** argv) {
   if (st != AZ_OK) { fprintf(stderr, "az_engine_create: status %d: %s\n", st, az_last_error()); return st == AZ_ERR_HIP ? 2 : 1; }
   int64_t np = 0;
   if (!o.dry) az_net_num_params(e, &np);
+  std::vector<float> blob;
   if (!o.dry) {
     // synthetic weights in the blob layout of include/azhip.h: uniform(-s, s) convolutions / dense layers, batch norm near identity
-    std::vector<float> blob((size_t)np);
+    blob.resize((size_t)np);
     std::mt19937 r(2026);
     std::uniform_real_distribution<float> u(-1.f, 1.f);
     const int F = o.filters;
@@ -471,6 +664,14 @@ int main(int argc, char** argv) {
   }
   const int W = o.workers;
   Pool pool(o.threads);
+  if (o.device_trees) {                                              // a second engine with the same network: one per half (stream, network buffers)
+    az_engine* e2 = nullptr;
+    if ((st = az_engine_create(&cfg, &e2)) != AZ_OK || (st = az_net_set_params(e2, blob.data(), np)) != AZ_OK) { fprintf(stderr, "second engine: status %d: %s\n", st, az_last_error()); return 1; }
+    az_engine* const engines[2] = {e, e2};
+    const int rc = run_device_trees(o, engines, pool);
+    az_engine_destroy(e2); az_engine_destroy(e);
+    return rc;
+  }
   if (o.arena_gb <= 0.0) {
     // 2 M simulations/s x 1.4 KB per node = 2.8 GB/s of tree: enough for the run (trees are only reset when a game ends), at most a
     // quarter of what the host has available

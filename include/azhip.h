@@ -153,7 +153,7 @@ int az_abi_version(void);
 typedef enum {
   AZ_STRUCT_ENGINE_CFG = 0, AZ_STRUCT_MOVE_REC = 1, AZ_STRUCT_GAME_REC = 2, AZ_STRUCT_TRACE_BUF = 3, AZ_STRUCT_SELFPLAY_STATS = 4,
   AZ_STRUCT_SAMPLE = 5, AZ_STRUCT_DATASET_INFO = 6, AZ_STRUCT_LEARNING_STATUS = 7, AZ_STRUCT_TRAIN_CFG = 8, AZ_STRUCT_GATHER_STATS = 9,
-  AZ_STRUCT_PROF = 10, AZ_STRUCT_MINMAX_CFG = 11, AZ_STRUCT_SOLVER_CFG = 12
+  AZ_STRUCT_PROF = 10, AZ_STRUCT_MINMAX_CFG = 11, AZ_STRUCT_SOLVER_CFG = 12, AZ_STRUCT_HOST_TREE_CFG = 13, AZ_STRUCT_HOST_TREE_STATS = 14
 } az_struct_id;
 int az_abi_struct_size(int32_t which);
 
@@ -590,6 +590,96 @@ int az_plane_memory_num_symmetries(az_plane_memory* m, int32_t* nsym);
  * symmetries were declared for this memory (game.jl:332), and when n1 > 2^31 - 1. */
 int az_dataset_create_from_plane_memory_sym(az_plane_memory* m, int32_t which, int32_t use_symmetries, int32_t use_position_averaging,
                                             int32_t weighing_policy, az_dataset** out);
+
+/* ---- device search trees for a host-stepped game: MCTS.Env (src/mcts.jl:124-226) whose rules the caller owns --------------------
+ * W independent per-worker trees in HBM.  The device selects, expands, backs up and looks transpositions up; the host is asked at
+ * most one question per simulation -- "play this action in this node's state" -- and answers with the key, the reward and, for a
+ * state the worker has not met, what the network sees of it.  An edge that has been walked once is remembered (child node or
+ * terminal, the mover's reward, whether the player changed), so the rules are consulted once per (state, action) and worker.
+ *   oracle        engine mode (e != NULL: a ResNet engine with its parameters set, num_actions == the engine's): the rows of the
+ *                 non-terminal replies are evaluated by the engine's network on the device, in reply order, in ONE launch of the
+ *                 seam az_net_forward uses; P / V never leave the device.  Host-oracle mode (e == NULL): the caller supplies P (full
+ *                 width) and V with each non-terminal reply (MCTS.RandomOracle-style players; exact tests without a network).
+ *   state key     128 bits the host chooses; both words are compared.  Two states with one key are the caller's affair, as with a Dict.
+ *   node          by RANK among the available actions (mcts.jl:78-87): P (Float32), W (Float64), N (Int32), the action id, and the
+ *                 memo of the edge: child node, terminal flag, the mover's reward (Float64 of the Float32 given), pswitch; per node
+ *                 Vest and white_playing.  Node ids count from 0 per worker in creation order; az_host_tree_reset restarts them.
+ *   scores        (mcts.jl:180-188) Ntot = sum N (integer); s = sqrt(Float64(Ntot)); Q = W / Float64(max(N, 1)); Pd = Float64(P), at the
+ *                 root (empty path) with eps != 0: Pd = (1 - eps) * Pd + eps * eta[rank]; score = Q + ((cpuct * Pd) * s) / Float64(N + 1);
+ *                 the first maximum is taken.  Every step is one IEEE Float64 operation, no contraction.
+ *   noise         eta = az_dirichlet over the root's n with the stream (seed, game id, move, AZ_RNG_NOISE) of az_numerics.h, drawn on
+ *                 the device the first time the root is selected from after an az_host_tree_explore; not drawn when eps == 0.
+ *   backup        (mcts.jl:216-223) a new node's value is q = Float64(Vest), a terminal state's 0.0; then, last path entry first:
+ *                 qn = pswitch ? -q : q; q = r + gamma * qn; W += q; N += 1.
+ *   protocol      az_host_tree_explore arms workers with a quota of simulations; every az_host_tree_step absorbs the replies to the
+ *                 requests of the step before (same order: worker order, compacted) and carries every armed worker to its next
+ *                 request or to the end of its quota, in one call with one synchronisation.  A reply to AZ_HT_PLAY describes the
+ *                 state after the move: terminal -> the simulation is backed up with 0.0; a key the worker's table holds -> the edge
+ *                 is linked to that node (a transposition; an evaluation made for it is discarded and counted) and the simulation
+ *                 goes on from there in the same step, as run_simulation! would; otherwise the node is created and the simulation
+ *                 backed up.  Edges known to lead to a node are descended, edges known to be terminal finish the simulation on the
+ *                 device.  A worker whose root is unknown (first explore, after a reset, after an advance along an unwalked edge)
+ *                 asks AZ_HT_ROOT: describe the root state; a new root's first simulation returns Vest, as in the reference.
+ *   requests      {worker, node, action (full index), kind}.  AZ_HT_FULL (node pool or edge pool exhausted) and AZ_HT_DEPTH (the path
+ *                 would exceed max_depth) are reports, not questions: the simulation is abandoned, nothing of it is stored or backed
+ *                 up, the worker is disarmed, other workers are untouched, and no reply is given for them.  new_nodes[i] = the node
+ *                 reply i created or was linked to (-1 for a terminal reply, and where the pools were exhausted).
+ *   refusals      checked before anything is stored, az_last_error() names the offender: a reply count other than the outstanding
+ *                 requests', a non-finite reward or V, a terminal root, an A row with no legal action or entries outside {0, 1},
+ *                 P < 0 or not finite or P > 0 where A == 0 (host-oracle mode), a worker index out of range, az_host_tree_explore
+ *                 on an armed worker (or naming one twice), root_stats / advance / reset on an armed worker (AZ_ERR_STATE), an
+ *                 advance by an action the root does not have.  The tree is unchanged and the outstanding requests stay outstanding.
+ * Not built: prior_temperature != 1 (refused by az_host_tree_create), more than AZ_HOST_TREE_MAX_ACTIONS actions, freeing the
+ * subtrees an advance leaves unreachable (the tree is kept, as the reference keeps it between the moves of a game). */
+#define AZ_HOST_TREE_MAX_ACTIONS 128
+typedef struct az_host_tree az_host_tree;
+typedef struct {
+  int32_t struct_size;        /* sizeof(az_host_tree_cfg), set by az_host_tree_cfg_init */
+  int32_t reserved;           /* 0 */
+  double gamma, cpuct, dirichlet_noise_eps, dirichlet_noise_alpha;   /* MctsParams (src/params.jl:49-57) */
+  double prior_temperature;   /* must be 1 */
+  uint64_t seed;
+} az_host_tree_cfg;
+typedef enum { AZ_HT_PLAY = 0, AZ_HT_ROOT = 1, AZ_HT_FULL = 2, AZ_HT_DEPTH = 3 } az_host_tree_request_kind;
+typedef struct { int32_t worker, node, action, kind; } az_host_tree_request;   /* AZ_HT_ROOT: node = action = -1 */
+typedef struct {
+  uint64_t key[2];            /* the state after the move (AZ_HT_PLAY) / the root state (AZ_HT_ROOT) */
+  float white_reward;         /* GI.white_reward after the move; ignored for AZ_HT_ROOT */
+  uint8_t terminal;           /* GI.game_terminated */
+  uint8_t white_playing;      /* GI.white_playing of that state */
+  uint8_t reserved[2];
+} az_host_tree_reply;
+typedef struct {
+  int64_t simulations;            /* completed (src/mcts.jl:242) */
+  int64_t nodes_traversed;        /* src/mcts.jl:222 */
+  int64_t evaluations;            /* non-terminal replies = rows the oracle evaluated */
+  int64_t transposition_hits;     /* of them: the key was already in the worker's table, the evaluation was discarded */
+  int64_t sims_without_host;      /* simulations that began and ended on the device without a request */
+  int64_t max_nodes, max_edge_slots, max_path;   /* high-water marks over the workers (they survive a reset) */
+  int64_t steps;                  /* az_host_tree_step calls that launched */
+} az_host_tree_stats;
+int az_host_tree_cfg_init(az_host_tree_cfg* cfg);   /* gamma 1, cpuct 1, eps 0, alpha 1, prior_temperature 1, seed 0 */
+/* num_actions 1..AZ_HOST_TREE_MAX_ACTIONS, num_workers 1..2^20, nodes_per_worker >= 1, edge_slots_per_worker >= num_actions,
+ * max_depth >= 1.  Engine mode: num_workers must not exceed what one network launch of the engine takes; the engine must outlive the
+ * tree, and the tree uses the engine's stream.  `device` is ignored in engine mode (the engine's is taken). */
+int az_host_tree_create(az_engine* e_or_null, int32_t device, int32_t num_actions, int32_t num_workers, int32_t nodes_per_worker,
+                        int32_t edge_slots_per_worker, int32_t max_depth, const az_host_tree_cfg* cfg, az_host_tree** out);
+int az_host_tree_destroy(az_host_tree* t);
+/* MCTS.explore!(env, game, nsims) begins for n workers: each gets a quota of nsims >= 1 simulations and the noise stream of
+ * (seed, game_ids[i], moves[i]).  Nothing runs until the next az_host_tree_step. */
+int az_host_tree_explore(az_host_tree* t, int32_t n, const int32_t* workers, const uint32_t* game_ids, const uint32_t* moves, int32_t nsims);
+/* One step ("protocol" above).  replies [nreplies]; X [nreplies][C][H][W] (engine mode only, the layout of az_net_forward), A
+ * [nreplies][num_actions], P [nreplies][num_actions] and V [nreplies] (host-oracle mode only) are indexed by reply; the rows of
+ * terminal replies are not read.  requests and new_nodes must hold num_workers entries; *nrequests = requests written. */
+int az_host_tree_step(az_host_tree* t, int32_t nreplies, const az_host_tree_reply* replies, const float* X, const float* A, const float* P,
+                      const float* V, az_host_tree_request* requests, int32_t* nrequests, int32_t* new_nodes);
+/* tree[root] of n workers by FULL action index (unavailable: 0): N [n][num_actions], W, P, Vest [n], root_node [n] (-1 and zeros
+ * where the root is unknown); any pointer may be NULL.  What MCTS.policy (mcts.jl:255-271) and the explorer need. */
+int az_host_tree_root_stats(az_host_tree* t, int32_t n, const int32_t* workers, int32_t* N, double* W, float* P, float* Vest, int32_t* root_node);
+/* The root becomes the child the edge `actions[i]` leads to if that is a known node, else unknown; the tree is kept. */
+int az_host_tree_advance(az_host_tree* t, int32_t n, const int32_t* workers, const int32_t* actions);
+int az_host_tree_reset(az_host_tree* t, int32_t n, const int32_t* workers);   /* MCTS.reset!: the tree is emptied, node ids restart at 0, counters are kept */
+int az_host_tree_get_stats(az_host_tree* t, az_host_tree_stats* stats);
 
 /* ---- the optimiser step (src/learning.jl:123-141, src/networks/flux.jl:68-95) --------------- */
 typedef struct az_trainer az_trainer;   /* Trainer (src/learning.jl:98-121): network in train mode + optimiser state */

@@ -288,5 +288,14 @@ const UNBOUND = Dict(
   :az_plane_memory_num_symmetries => "see az_plane_memory_create",
   :az_dataset_create_from_plane_memory_sym => "builds from an az_plane_memory, which is unbound (see az_plane_memory_create)",
   :az_comm_gather_push_planes => "gathers from and into an az_plane_memory, which is unbound (see az_plane_memory_create)",
+  :az_host_tree_cfg_init => "device search trees of a host-stepped game: az_host_tree / az_host_tree_cfg / az_host_tree_request / az_host_tree_reply / az_host_tree_stats have no ccall rule (tests/test_julia_glue_static.py HANDLES, JL_OK) and no Julia was at hand to run a binding against src/openspiel.jl; azhip/host_tree.py is the tested host",
+  :az_host_tree_create => "see az_host_tree_cfg_init",
+  :az_host_tree_destroy => "see az_host_tree_cfg_init",
+  :az_host_tree_explore => "see az_host_tree_cfg_init; MCTS.explore! of the reference serves a Julia host until the binding exists",
+  :az_host_tree_step => "see az_host_tree_cfg_init; takes arrays of az_host_tree_reply / az_host_tree_request records",
+  :az_host_tree_root_stats => "see az_host_tree_cfg_init; MCTS.policy's inputs",
+  :az_host_tree_advance => "see az_host_tree_cfg_init",
+  :az_host_tree_reset => "see az_host_tree_cfg_init; MCTS.reset!",
+  :az_host_tree_get_stats => "see az_host_tree_cfg_init",
 )
 
