@@ -19,6 +19,11 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 extern "C" const char* az_last_error(void) { return g_err.c_str(); }
+extern "C" int az_debug_scratch_live_bytes(int64_t* bytes) {       // engine.h Scratch
+  if (!bytes) return fail(AZ_ERR_BAD_ARG, "NULL argument");
+  *bytes = (int64_t)scratch_live_bytes.load();
+  return AZ_OK;
+}
 extern "C" int az_abi_version(void) { return AZ_ABI_VERSION; }
 extern "C" int az_abi_struct_size(int32_t which) {
   switch (which) {
@@ -550,10 +555,7 @@ extern "C" int az_engine_create(const az_engine_cfg* c, az_engine** out) {
   *out = nullptr;
   GameInfo gi;
   AZCHK(check_cfg(c, &gi));
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (c->device < 0 || c->device >= ndev) return fail(AZ_ERR_BAD_ARG, "device %d not available (%d visible)", c->device, ndev);
-  HIPCHK(hipSetDevice(c->device));
+  AZCHK(use_device(c->device));
   az_engine* e = new (std::nothrow) az_engine();                      // (e->env: reads the creation-time overrides)
   if (!e) return fail(AZ_ERR_HIP, "out of host memory");
   e->cfg = *c; e->gi = gi; e->device = c->device;
@@ -718,7 +720,7 @@ extern "C" int az_net_set_params(az_engine* e, const float* blob, int64_t n) {
   const NetLayout lay = net_layout(e->gi, c);
   if (!blob || n != (int64_t)lay.total) return fail(AZ_ERR_BAD_ARG, "parameter blob has %lld values, expected %zu", (long long)n, lay.total);
   e->blob.assign(blob, blob + n);
-  if (!e->net_maps) e->net_maps.reset(new NetMaps(lay, c.net_bf16 != 0));
+  if (!e->net_maps) { e->net_maps.reset(new NetMaps(lay, c.net_bf16 != 0)); e->trainable = trainable_mask(lay); }
   const NetMaps& M = *e->net_maps;
   const NetHost h = net_host(lay, M, blob, c.net_bf16 != 0);
   AZCHK(sync_all(e));

@@ -98,18 +98,18 @@ static int load() {
     if (_r != ncclSuccess) return fail(AZ_ERR_COMM, "%s failed: %s (%s:%d)", #x, rc::g.GetErrorString(_r), __FILE__, __LINE__); \
   } while (0)
 
-struct az_comm {
-  ncclComm_t comm;
-  int rank, world, device;
-  hipStream_t stream;
+struct az_comm {                                    // every member starts here: az_comm_destroy takes a half-made record apart
+  ncclComm_t comm = nullptr;
+  int rank = 0, world = 1, device = 0;
+  hipStream_t stream = nullptr;
   // status / count words of the failure agreement, allocated ONCE at az_comm_init: a collective call must not be able to fail
   // locally (an allocation) before it has entered the first all-gather, or the other ranks would wait in it for ever
-  long long *d_word_send, *d_word_all;             // [COMM_WORDS], [COMM_WORDS * world]
+  long long *d_word_send = nullptr, *d_word_all = nullptr;   // [COMM_WORDS], [COMM_WORDS * world]
   // az_comm_gather_push_planes: rows per rank and round forced by az_debug_comm_plane_round_rows (0: the default), the events that
   // time its kernels (created here for the same reason as the words) and the sums of its last call
-  int64_t plane_round_rows;
-  hipEvent_t ev[4];
-  double pack_ms, scatter_ms;
+  int64_t plane_round_rows = 0;
+  hipEvent_t ev[4] = {};
+  double pack_ms = 0.0, scatter_ms = 0.0;
 };
 static constexpr int COMM_WORDS = 4;               // az_comm_gather_push_planes sends four (count, samples, status, geometry), the others three or one
 static_assert(sizeof(ncclUniqueId) == AZ_COMM_ID_BYTES, "ncclUniqueId size");
@@ -150,16 +150,10 @@ extern "C" int az_comm_init(int32_t device, int32_t rank, int32_t world, const u
   *out = nullptr;
   if (world < 1 || rank < 0 || rank >= world) return fail(AZ_ERR_BAD_ARG, "rank %d of %d", rank, world);
   AZCHK(rc::load());
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(AZ_ERR_BAD_ARG, "device %d not available (%d visible)", device, ndev);
-  HIPCHK(hipSetDevice(device));
+  AZCHK(use_device(device));
   az_comm* c = new (std::nothrow) az_comm();
   if (!c) return fail(AZ_ERR_HIP, "out of host memory");
-  c->comm = nullptr; c->rank = rank; c->world = world; c->device = device; c->stream = nullptr;
-  c->d_word_send = c->d_word_all = nullptr;
-  c->plane_round_rows = 0; c->pack_ms = c->scatter_ms = 0.0;
-  for (hipEvent_t& ev : c->ev) ev = nullptr;
+  c->rank = rank; c->world = world; c->device = device;
   int st = [&]() -> int {
     HIPCHK(hipStreamCreate(&c->stream));
     HIPCHK(hipMalloc((void**)&c->d_word_send, COMM_WORDS * sizeof(long long)));
@@ -185,29 +179,67 @@ static __global__ void k_pack_moves(const az_move_rec* __restrict__ phase, const
   for (int k = threadIdx.x; k < cnt[g] * 4; k += blockDim.x) d[k] = s[k];
 }
 
-// One int64 per rank: AZ_OK or the first local failure.  Every rank learns whether ALL ranks can go on (max |status|).
-static int agree(az_comm* c, int local_status, long long* d_send, long long* d_all, int* worst_rank) {
-  const int W = c->world;
-  long long v = local_status;
-  HIPCHK(hipMemcpyAsync(d_send, &v, sizeof v, hipMemcpyHostToDevice, c->stream));
-  RCCLCHK(rc::g.AllGather(d_send, d_all, 1, ncclInt64, c->comm, c->stream));
-  std::vector<long long> all((size_t)W);
-  HIPCHK(hipMemcpyAsync(all.data(), d_all, sizeof(long long) * W, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  *worst_rank = -1;
-  for (int r = 0; r < W; ++r) if (all[r] != AZ_OK && *worst_rank < 0) *worst_rank = r;
-  return AZ_OK;
-}
+// ---- the failure agreement ----------------------------------------------------------------------------------------------------------
 // a collective failed half way: the other ranks may be inside it -- tear the communicator down so that they fail too
 static void abort_comm(az_comm* c) {
   if (c->comm && rc::g.CommAbort) { (void)rc::g.CommAbort(c->comm); c->comm = nullptr; }
 }
 #define COMM_ALIVE(c) if (!(c)->comm) return fail(AZ_ERR_COMM, "the communicator was aborted by an earlier failed collective")
+// A collective step: what `body` issues is what the other ranks wait for, so a failure inside it aborts the communicator.  Whatever
+// an entry point does outside a step fails locally and leaves the communicator alone -- where a failure happens decides, nothing else.
+template <class F> static int collective(az_comm* c, F&& body) {
+  const int st = body();
+  if (st != AZ_OK) abort_comm(c);
+  return st;
+}
+// every collective call's first step after its argument checks
+static int comm_device(az_comm* c) {
+  return collective(c, [&]() -> int {
+    if (hipSetDevice(c->device) != hipSuccess) return fail(AZ_ERR_HIP, "hipSetDevice(%d) failed; communicator aborted", c->device);
+    return AZ_OK;
+  });
+}
+// What a rank found wrong before an exchange; its status word travels, its message stays for the rank's own report.
+struct Verdict {
+  int status;
+  std::string msg;
+  explicit Verdict(int st) : status(st), msg(st != AZ_OK ? az_last_error() : "") {}
+};
+// One exchange: nw <= COMM_WORDS words of every rank, all[nw * r ..) = rank r's.  The words live in buffers allocated at az_comm_init,
+// so nothing can fail locally before the all-gather.
+static int exchange_words(az_comm* c, const long long* words, int nw, std::vector<long long>* all) {
+  all->resize((size_t)nw * c->world);
+  return collective(c, [&]() -> int {
+    HIPCHK(hipMemcpyAsync(c->d_word_send, words, sizeof(long long) * nw, hipMemcpyHostToDevice, c->stream));
+    RCCLCHK(rc::g.AllGather(c->d_word_send, c->d_word_all, (size_t)nw, ncclInt64, c->comm, c->stream));
+    HIPCHK(hipMemcpyAsync(all->data(), c->d_word_all, sizeof(long long) * all->size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return AZ_OK;
+  });
+}
+// After an exchange whose word `at` is each rank's status: a failing rank reports its own reason, the others name the first rank that
+// failed through others(rank, its status word); AZ_OK when every rank is fine.  All ranks leave together either way.
+template <class F> static int settle(const Verdict& mine, const std::vector<long long>& all, int nw, int at, F&& others) {
+  if (mine.status != AZ_OK) return fail(mine.status, "%s", mine.msg.c_str());
+  for (size_t r = 0; r * nw < all.size(); ++r)
+    if (all[r * nw + at] != AZ_OK) return others((int)r, all[r * nw + at]);
+  return AZ_OK;
+}
+// The buffers of a gather are sized by the largest rank: a rank that cannot allocate them says so before anything is exchanged.
+// One rank has nobody to tell.
+static int agree_allocated(az_comm* c, int alloc_status) {
+  if (c->world == 1) return alloc_status;
+  const Verdict own(alloc_status);
+  const long long word = alloc_status;
+  std::vector<long long> all;
+  AZCHK(exchange_words(c, &word, 1, &all));
+  return settle(own, all, 1, 0, [](int r, long long) { return fail(AZ_ERR_COMM, "rank %d could not allocate the gather buffers; nothing was exchanged", r); });
+}
 
 extern "C" int az_comm_gather_push(az_comm* c, az_engine* e, az_memory* m, double gamma, az_gather_stats* stats) {
   if (!c) return fail(AZ_ERR_BAD_ARG, "NULL communicator");
   COMM_ALIVE(c);
-  if (hipSetDevice(c->device) != hipSuccess) { abort_comm(c); return fail(AZ_ERR_HIP, "hipSetDevice(%d) failed; communicator aborted", c->device); }
+  AZCHK(comm_device(c));
   // local validation first; its verdict travels with the counts, so that every rank returns together (never one rank
   // leaving while the others sit in ncclAllGather)
   int local = AZ_OK;
@@ -217,7 +249,7 @@ extern "C" int az_comm_gather_push(az_comm* c, az_engine* e, az_memory* m, doubl
   else if (e->running) local = fail(AZ_ERR_STATE, "self-play in progress");
   else if (!e->d_phase) local = fail(AZ_ERR_STATE, "the engine holds no device-resident phase (az_selfplay_run first)");
   else local = sync_all(e);
-  std::string local_msg = local != AZ_OK ? az_last_error() : "";
+  const Verdict own(local);
   const auto t0 = std::chrono::steady_clock::now();
   const int W = c->world;
   const size_t ng = local == AZ_OK ? e->ph_games.size() : 0;
@@ -234,46 +266,27 @@ extern "C" int az_comm_gather_push(az_comm* c, az_engine* e, az_memory* m, doubl
     gsend[i] = r; gsend[i].first_move = (int32_t)nm;
     nm += r.num_moves;
   }
-  std::vector<void*> tmp;
-  auto cleanup = [&]() { for (void* p : tmp) (void)hipFree(p); };
-  bool in_collective = false;
-  int st = [&]() -> int {
-    // 1. counts and status of every rank
-    long long hc[3] = {(long long)ng, nm, (long long)local};
-    long long *d_cnt_send = c->d_word_send, *d_cnt_all = c->d_word_all;   // allocated at az_comm_init: nothing can fail before the all-gather
-    in_collective = true;
-    HIPCHK(hipMemcpyAsync(d_cnt_send, hc, sizeof hc, hipMemcpyHostToDevice, c->stream));
-    RCCLCHK(rc::g.AllGather(d_cnt_send, d_cnt_all, 3, ncclInt64, c->comm, c->stream));
-    std::vector<long long> all((size_t)3 * W);
-    HIPCHK(hipMemcpyAsync(all.data(), d_cnt_all, sizeof(long long) * 3 * W, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    in_collective = false;
-    long long maxg = 1, maxm = 1, totg = 0, totm = 0;
-    if (local != AZ_OK) return fail(local, "%s", local_msg.c_str());   // a failing rank reports its own reason
-    for (int r = 0; r < W; ++r) {
-      if (all[3 * r + 2] != AZ_OK) {
-        return fail(AZ_ERR_COMM, "rank %d cannot take part in the gather (status %lld); nothing was exchanged", r, all[3 * r + 2]);
-      }
-      maxg = std::max(maxg, all[3 * r]); maxm = std::max(maxm, all[3 * r + 1]); totg += all[3 * r]; totm += all[3 * r + 1];
-    }
-    // 2. this rank's records packed in game-id order, then the two all-gathers (equal, padded segments per rank)
-    az_move_rec *d_msend = nullptr, *d_mall = nullptr; az_game_rec *d_gsend = nullptr, *d_gall = nullptr; long long *d_src = nullptr, *d_dst = nullptr; int* d_n = nullptr;
-    int ast = [&]() -> int {
-      AZCHK(mem_alloc(&tmp, &d_msend, (size_t)maxm)); AZCHK(mem_alloc(&tmp, &d_mall, (size_t)maxm * W));
-      AZCHK(mem_alloc(&tmp, &d_gsend, (size_t)maxg)); AZCHK(mem_alloc(&tmp, &d_gall, (size_t)maxg * W));
-      AZCHK(mem_alloc(&tmp, &d_src, std::max<size_t>(ng, 1))); AZCHK(mem_alloc(&tmp, &d_dst, std::max<size_t>(ng, 1))); AZCHK(mem_alloc(&tmp, &d_n, std::max<size_t>(ng, 1)));
-      return AZ_OK;
-    }();
-    if (W > 1) {                       // the buffers are sized by the largest rank: a rank that cannot allocate them says so first
-      std::string amsg = ast != AZ_OK ? az_last_error() : "";
-      int bad = -1;
-      in_collective = true;
-      AZCHK(agree(c, ast, d_cnt_send, d_cnt_all, &bad));
-      in_collective = false;
-      if (bad >= 0) return bad == c->rank || ast != AZ_OK ? fail(ast != AZ_OK ? ast : AZ_ERR_COMM, "%s", ast != AZ_OK ? amsg.c_str() : "another rank failed")
-                                                            : fail(AZ_ERR_COMM, "rank %d could not allocate the gather buffers; nothing was exchanged", bad);
-    } else AZCHK(ast);
-    in_collective = true;
+  // 1. counts and status of every rank
+  const long long hc[3] = {(long long)ng, nm, (long long)local};
+  std::vector<long long> all;
+  AZCHK(exchange_words(c, hc, 3, &all));
+  AZCHK(settle(own, all, 3, 2, [](int r, long long status) {
+    return fail(AZ_ERR_COMM, "rank %d cannot take part in the gather (status %lld); nothing was exchanged", r, status);
+  }));
+  long long maxg = 1, maxm = 1, totg = 0, totm = 0;
+  for (int r = 0; r < W; ++r) { maxg = std::max(maxg, all[3 * r]); maxm = std::max(maxm, all[3 * r + 1]); totg += all[3 * r]; totm += all[3 * r + 1]; }
+  // 2. this rank's records packed in game-id order, then the two all-gathers (equal, padded segments per rank)
+  Scratch tmp;
+  az_move_rec *d_msend = nullptr, *d_mall = nullptr; az_game_rec *d_gsend = nullptr, *d_gall = nullptr; long long *d_src = nullptr, *d_dst = nullptr; int* d_n = nullptr;
+  AZCHK(agree_allocated(c, [&]() -> int {
+    AZCHK(tmp.alloc(&d_msend, (size_t)maxm)); AZCHK(tmp.alloc(&d_mall, (size_t)maxm * W));
+    AZCHK(tmp.alloc(&d_gsend, (size_t)maxg)); AZCHK(tmp.alloc(&d_gall, (size_t)maxg * W));
+    AZCHK(tmp.alloc(&d_src, std::max<size_t>(ng, 1))); AZCHK(tmp.alloc(&d_dst, std::max<size_t>(ng, 1))); AZCHK(tmp.alloc(&d_n, std::max<size_t>(ng, 1)));
+    return AZ_OK;
+  }()));
+  // 3. the game records (56 B per game) tell where every game's records sit in the gathered buffer
+  std::vector<az_game_rec> gall((size_t)maxg * W);
+  AZCHK(collective(c, [&]() -> int {
     if (ng) {
       HIPCHK(hipMemcpyAsync(d_src, src.data(), sizeof(long long) * ng, hipMemcpyHostToDevice, c->stream));
       HIPCHK(hipMemcpyAsync(d_dst, dst.data(), sizeof(long long) * ng, hipMemcpyHostToDevice, c->stream));
@@ -283,70 +296,65 @@ extern "C" int az_comm_gather_push(az_comm* c, az_engine* e, az_memory* m, doubl
     }
     RCCLCHK(rc::g.AllGather(d_msend, d_mall, (size_t)maxm * sizeof(az_move_rec), ncclInt8, c->comm, c->stream));
     RCCLCHK(rc::g.AllGather(d_gsend, d_gall, (size_t)maxg * sizeof(az_game_rec), ncclInt8, c->comm, c->stream));
-    // 3. the game records (56 B per game) tell where every game's records sit in the gathered buffer
-    std::vector<az_game_rec> gall((size_t)maxg * W);
     HIPCHK(hipMemcpyAsync(gall.data(), d_gall, sizeof(az_game_rec) * gall.size(), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipGetLastError());
-    in_collective = false;
-    const auto t1 = std::chrono::steady_clock::now();
-    struct Ref { int32_t id; long long first; int n; };
-    std::vector<Ref> refs;
-    refs.reserve((size_t)totg);
+    return AZ_OK;
+  }));
+  const auto t1 = std::chrono::steady_clock::now();
+  struct Ref { int32_t id; long long first; int n; };
+  std::vector<Ref> refs;
+  refs.reserve((size_t)totg);
+  for (int r = 0; r < W; ++r)
+    for (long long i = 0; i < all[3 * r]; ++i) {
+      const az_game_rec& gr = gall[(size_t)r * maxg + i];
+      refs.push_back({gr.game_id, (long long)r * maxm + gr.first_move, gr.num_moves});   // rank r's segment starts at r * maxm
+    }
+  std::sort(refs.begin(), refs.end(), [](const Ref& a, const Ref& b) { return a.id < b.id; });
+  if (m) {
+    std::vector<long long> first(refs.size());
+    std::vector<int> n(refs.size());
+    for (size_t i = 0; i < refs.size(); ++i) { first[i] = refs[i].first; n[i] = refs[i].n; }
+    AZCHK(memory_push_device(m, d_mall, first, n, gamma));
+  }
+  if (stats) {
+    stats->games = totg; stats->moves = totm;
+    stats->bytes = (int64_t)W * (maxm * (long long)sizeof(az_move_rec) + maxg * (long long)sizeof(az_game_rec) + 24);
+    stats->gather_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    // Report.SelfPlay wants mean depth and the largest tree over ALL games (training.jl:293-296), not the rank's own
+    long long sims = 0, trav = 0, nodes = 0, repl = 0;
     for (int r = 0; r < W; ++r)
       for (long long i = 0; i < all[3 * r]; ++i) {
         const az_game_rec& gr = gall[(size_t)r * maxg + i];
-        refs.push_back({gr.game_id, (long long)r * maxm + gr.first_move, gr.num_moves});   // rank r's segment starts at r * maxm
+        repl += (gr.game_id & AZ_REPLACEMENT_GAME_BIT) != 0;
+        sims += gr.total_simulations; trav += gr.total_nodes_traversed; nodes = std::max<long long>(nodes, gr.nodes);
       }
-    std::sort(refs.begin(), refs.end(), [](const Ref& a, const Ref& b) { return a.id < b.id; });
-    if (m) {
-      std::vector<long long> first(refs.size());
-      std::vector<int> n(refs.size());
-      for (size_t i = 0; i < refs.size(); ++i) { first[i] = refs[i].first; n[i] = refs[i].n; }
-      AZCHK(memory_push_device(m, d_mall, first, n, gamma));
-    }
-    if (stats) {
-      stats->games = totg; stats->moves = totm;
-      stats->bytes = (int64_t)W * (maxm * (long long)sizeof(az_move_rec) + maxg * (long long)sizeof(az_game_rec) + 24);
-      stats->gather_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-      stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      // Report.SelfPlay wants mean depth and the largest tree over ALL games (training.jl:293-296), not the rank's own
-      long long sims = 0, trav = 0, nodes = 0, repl = 0;
+    double dsum = 0.0;                 // mean over games of each game's average depth, in global game-id order
+    {
+      std::vector<std::pair<int32_t, double>> dep;
+      dep.reserve((size_t)totg);
       for (int r = 0; r < W; ++r)
         for (long long i = 0; i < all[3 * r]; ++i) {
           const az_game_rec& gr = gall[(size_t)r * maxg + i];
-          repl += (gr.game_id & AZ_REPLACEMENT_GAME_BIT) != 0;
-          sims += gr.total_simulations; trav += gr.total_nodes_traversed; nodes = std::max<long long>(nodes, gr.nodes);
+          dep.push_back({gr.game_id, gr.total_simulations ? (double)gr.total_nodes_traversed / (double)gr.total_simulations : 0.0});
         }
-      double dsum = 0.0;                 // mean over games of each game's average depth, in global game-id order
-      {
-        std::vector<std::pair<int32_t, double>> dep;
-        dep.reserve((size_t)totg);
-        for (int r = 0; r < W; ++r)
-          for (long long i = 0; i < all[3 * r]; ++i) {
-            const az_game_rec& gr = gall[(size_t)r * maxg + i];
-            dep.push_back({gr.game_id, gr.total_simulations ? (double)gr.total_nodes_traversed / (double)gr.total_simulations : 0.0});
-          }
-        std::sort(dep.begin(), dep.end(), [](const std::pair<int32_t, double>& a, const std::pair<int32_t, double>& b) { return a.first < b.first; });
-        for (const auto& d : dep) dsum += d.second;
-      }
-      stats->ranks = W;
-      stats->total_simulations = sims; stats->total_nodes_traversed = trav; stats->max_nodes = nodes;
-      stats->mean_game_depth = totg ? dsum / (double)totg : 0.0;
-      stats->replaced_games = repl;
+      std::sort(dep.begin(), dep.end(), [](const std::pair<int32_t, double>& a, const std::pair<int32_t, double>& b) { return a.first < b.first; });
+      for (const auto& d : dep) dsum += d.second;
     }
-    return AZ_OK;
-  }();
-  if (st != AZ_OK && in_collective) abort_comm(c);
-  cleanup();
-  return st;
+    stats->ranks = W;
+    stats->total_simulations = sims; stats->total_nodes_traversed = trav; stats->max_nodes = nodes;
+    stats->mean_game_depth = totg ? dsum / (double)totg : 0.0;
+    stats->replaced_games = repl;
+  }
+  return AZ_OK;
 }
 
 extern "C" int az_comm_broadcast_params(az_comm* c, az_engine* e, int32_t root) {
   if (!c) return fail(AZ_ERR_BAD_ARG, "NULL communicator");
   COMM_ALIVE(c);
   if (root < 0 || root >= c->world) return fail(AZ_ERR_BAD_ARG, "root %d of %d", root, c->world);   // the same argument on every rank
-  if (hipSetDevice(c->device) != hipSuccess) { abort_comm(c); return fail(AZ_ERR_HIP, "hipSetDevice(%d) failed; communicator aborted", c->device); }
+  AZCHK(comm_device(c));
   int local = AZ_OK;
   int64_t n = 0;
   if (!e) local = fail(AZ_ERR_BAD_ARG, "NULL engine");
@@ -354,32 +362,27 @@ extern "C" int az_comm_broadcast_params(az_comm* c, az_engine* e, int32_t root) 
   else if (e->cfg.oracle != AZ_ORACLE_RESNET) local = fail(AZ_ERR_STATE, "engine was created without the ResNet oracle");
   else if (c->rank == root && !e->net_loaded) local = fail(AZ_ERR_STATE, "the root has no parameters loaded");
   else local = az_net_num_params(e, &n);
-  std::string local_msg = local != AZ_OK ? az_last_error() : "";
-  std::vector<void*> tmp;
   std::vector<float> h;
-  bool in_collective = false;
-  int st = [&]() -> int {
-    long long *d_s = c->d_word_send, *d_all = c->d_word_all;
+  {                                  // the staging buffer is freed before the engine allocates its packed copies
+    Scratch tmp;
     float* d = nullptr;
-    if (local == AZ_OK) { local = mem_alloc(&tmp, &d, (size_t)n); if (local != AZ_OK) local_msg = az_last_error(); }
-    int bad = -1;
-    in_collective = true;
-    AZCHK(agree(c, local, d_s, d_all, &bad));
-    in_collective = false;
-    if (local != AZ_OK) return fail(local, "%s", local_msg.c_str());
-    if (bad >= 0) return fail(AZ_ERR_COMM, "rank %d cannot take part in the broadcast%s; nothing was sent", bad, bad == root ? " (the root has no parameters?)" : "");
+    if (local == AZ_OK) local = tmp.alloc(&d, (size_t)n);
+    const Verdict own(local);
+    const long long word = local;
+    std::vector<long long> all;
+    AZCHK(exchange_words(c, &word, 1, &all));
+    AZCHK(settle(own, all, 1, 0, [&](int r, long long) {
+      return fail(AZ_ERR_COMM, "rank %d cannot take part in the broadcast%s; nothing was sent", r, r == root ? " (the root has no parameters?)" : "");
+    }));
     h.resize((size_t)n);
-    in_collective = true;
-    if (c->rank == root) HIPCHK(hipMemcpyAsync(d, e->blob.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    RCCLCHK(rc::g.Broadcast(d, d, (size_t)n, ncclFloat32, root, c->comm, c->stream));
-    HIPCHK(hipMemcpyAsync(h.data(), d, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    in_collective = false;
-    return AZ_OK;
-  }();
-  if (st != AZ_OK && in_collective) abort_comm(c);
-  for (void* p : tmp) (void)hipFree(p);
-  AZCHK(st);
+    AZCHK(collective(c, [&]() -> int {
+      if (c->rank == root) HIPCHK(hipMemcpyAsync(d, e->blob.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+      RCCLCHK(rc::g.Broadcast(d, d, (size_t)n, ncclFloat32, root, c->comm, c->stream));
+      HIPCHK(hipMemcpyAsync(h.data(), d, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      return AZ_OK;
+    }));
+  }
   // Network.copy(nn; on_gpu = true, test_mode = true) on every rank: the kernels want their packed fragments
   return az_net_set_params(e, h.data(), n);
 }
@@ -465,7 +468,7 @@ extern "C" int az_comm_gather_push_planes(az_comm* c, az_plane_memory* src, az_p
                                           int32_t num_games, az_gather_stats* stats) {
   if (!c) return fail(AZ_ERR_BAD_ARG, "NULL communicator");
   COMM_ALIVE(c);
-  if (hipSetDevice(c->device) != hipSuccess) { abort_comm(c); return fail(AZ_ERR_HIP, "hipSetDevice(%d) failed; communicator aborted", c->device); }
+  AZCHK(comm_device(c));
   // local validation first; its verdict travels with the counts and the geometry (az_comm_gather_push)
   long long B = 0;
   int local = [&]() -> int {
@@ -485,93 +488,79 @@ extern "C" int az_comm_gather_push_planes(az_comm* c, az_plane_memory* src, az_p
     if (dst) HIPCHK(hipStreamSynchronize(dst->stream));
     return AZ_OK;
   }();
-  std::string local_msg = local != AZ_OK ? az_last_error() : "";
+  const Verdict own(local);
   const auto t0 = std::chrono::steady_clock::now();
   const int W = c->world;
   const long long ng = local == AZ_OK ? num_games : 0;
   if (local != AZ_OK) B = 0;
-  std::vector<void*> tmp;
-  bool in_collective = false;
   c->pack_ms = c->scatter_ms = 0.0;
-  int st = [&]() -> int {
-    // 1. counts, status and geometry of every rank
-    long long hc[COMM_WORDS] = {ng, B, (long long)local, src ? ((long long)src->xs << 16) | (long long)src->nA : 0LL};
-    long long *d_send = c->d_word_send, *d_all = c->d_word_all;       // allocated at az_comm_init: nothing can fail before the all-gather
-    in_collective = true;
-    HIPCHK(hipMemcpyAsync(d_send, hc, sizeof hc, hipMemcpyHostToDevice, c->stream));
-    RCCLCHK(rc::g.AllGather(d_send, d_all, COMM_WORDS, ncclInt64, c->comm, c->stream));
-    std::vector<long long> all((size_t)COMM_WORDS * W);
-    HIPCHK(hipMemcpyAsync(all.data(), d_all, sizeof(long long) * all.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    in_collective = false;
-    if (local != AZ_OK) return fail(local, "%s", local_msg.c_str());   // a failing rank reports its own reason
-    long long maxg = 1, maxB = 1, totg = 0;
-    for (int r = 0; r < W; ++r) {
-      const long long* w = &all[(size_t)COMM_WORDS * r];
-      if (w[2] != AZ_OK) return fail(AZ_ERR_COMM, "rank %d cannot take part in the plane gather (status %lld); nothing was exchanged", r, w[2]);
-      maxg = std::max(maxg, w[0]); maxB = std::max(maxB, w[1]); totg += w[0];
-    }
-    for (int r = 1; r < W; ++r)
-      if (all[(size_t)COMM_WORDS * r + 3] != all[3]) return fail(AZ_ERR_BAD_ARG, "rank %d's plane geometry differs from rank 0's; nothing was exchanged", r);
-    const int RW = src->RW, ND = src->ND;
-    const long long rb = pg::record_bytes(RW, ND);
-    long long R = pg::default_round_rows(W, rb);
-    if (c->plane_round_rows > 0) R = std::min<long long>(R, c->plane_round_rows);
-    R = (maxB + (maxB + R - 1) / R - 1) / ((maxB + R - 1) / R);         // the same number of rounds, evenly filled: the last one sends little padding
-    // 2. buffers, sized by what all ranks hold together: a rank that cannot allocate them says so before anything is exchanged
-    pg::Game *d_tsend = nullptr, *d_tall = nullptr;
-    unsigned char *d_rsend = nullptr, *d_rall = nullptr;
-    long long *d_plan = nullptr;
-    const size_t n_prefix = (size_t)(totg + W), n_start = (size_t)std::max<long long>(totg, 1), n_src = (size_t)std::max<long long>(ng, 1);
-    const size_t n_plan = n_prefix + n_start + (size_t)(W + 1) + (size_t)W + n_src;   // prefix_all, start_all, goff, B, src
-    int ast = [&]() -> int {
-      AZCHK(mem_alloc(&tmp, &d_tsend, (size_t)maxg)); AZCHK(mem_alloc(&tmp, &d_tall, (size_t)maxg * W));
-      AZCHK(mem_alloc(&tmp, &d_rsend, (size_t)(R * rb))); AZCHK(mem_alloc(&tmp, &d_rall, (size_t)(R * rb) * W));
-      AZCHK(mem_alloc(&tmp, &d_plan, n_plan));
-      return AZ_OK;
-    }();
-    if (W > 1) {
-      std::string amsg = ast != AZ_OK ? az_last_error() : "";
-      int bad = -1;
-      in_collective = true;
-      AZCHK(agree(c, ast, d_send, d_all, &bad));
-      in_collective = false;
-      if (bad >= 0) return ast != AZ_OK ? fail(ast, "%s", amsg.c_str()) : fail(AZ_ERR_COMM, "rank %d could not allocate the gather buffers; nothing was exchanged", bad);
-    } else AZCHK(ast);
-    // 3. the game tables (8 B per game, padded to the largest rank), then the plan: the same on every rank
-    std::vector<pg::Game> tsend((size_t)maxg, pg::Game{0, 0});
-    for (long long k = 0; k < ng; ++k) tsend[(size_t)k] = pg::Game{game_ids[k], game_lens[k]};
-    std::vector<pg::Game> tall((size_t)maxg * W);
-    in_collective = true;
+  // 1. counts, status and geometry of every rank
+  const long long hc[COMM_WORDS] = {ng, B, (long long)local, src ? ((long long)src->xs << 16) | (long long)src->nA : 0LL};
+  std::vector<long long> all;
+  AZCHK(exchange_words(c, hc, COMM_WORDS, &all));
+  AZCHK(settle(own, all, COMM_WORDS, 2, [](int r, long long status) {
+    return fail(AZ_ERR_COMM, "rank %d cannot take part in the plane gather (status %lld); nothing was exchanged", r, status);
+  }));
+  long long maxg = 1, maxB = 1, totg = 0;
+  for (int r = 0; r < W; ++r) {
+    const long long* w = &all[(size_t)COMM_WORDS * r];
+    maxg = std::max(maxg, w[0]); maxB = std::max(maxB, w[1]); totg += w[0];
+  }
+  for (int r = 1; r < W; ++r)
+    if (all[(size_t)COMM_WORDS * r + 3] != all[3]) return fail(AZ_ERR_BAD_ARG, "rank %d's plane geometry differs from rank 0's; nothing was exchanged", r);
+  const int RW = src->RW, ND = src->ND;
+  const long long rb = pg::record_bytes(RW, ND);
+  long long R = pg::default_round_rows(W, rb);
+  if (c->plane_round_rows > 0) R = std::min<long long>(R, c->plane_round_rows);
+  R = (maxB + (maxB + R - 1) / R - 1) / ((maxB + R - 1) / R);         // the same number of rounds, evenly filled: the last one sends little padding
+  // 2. buffers, sized by what all ranks hold together: a rank that cannot allocate them says so before anything is exchanged
+  pg::Game *d_tsend = nullptr, *d_tall = nullptr;
+  unsigned char *d_rsend = nullptr, *d_rall = nullptr;
+  long long *d_plan = nullptr;
+  const size_t n_prefix = (size_t)(totg + W), n_start = (size_t)std::max<long long>(totg, 1), n_src = (size_t)std::max<long long>(ng, 1);
+  const size_t n_plan = n_prefix + n_start + (size_t)(W + 1) + (size_t)W + n_src;   // prefix_all, start_all, goff, B, src
+  Scratch tmp;
+  AZCHK(agree_allocated(c, [&]() -> int {
+    AZCHK(tmp.alloc(&d_tsend, (size_t)maxg)); AZCHK(tmp.alloc(&d_tall, (size_t)maxg * W));
+    AZCHK(tmp.alloc(&d_rsend, (size_t)(R * rb))); AZCHK(tmp.alloc(&d_rall, (size_t)(R * rb) * W));
+    AZCHK(tmp.alloc(&d_plan, n_plan));
+    return AZ_OK;
+  }()));
+  // 3. the game tables (8 B per game, padded to the largest rank), then the plan: the same on every rank
+  std::vector<pg::Game> tsend((size_t)maxg, pg::Game{0, 0});
+  for (long long k = 0; k < ng; ++k) tsend[(size_t)k] = pg::Game{game_ids[k], game_lens[k]};
+  std::vector<pg::Game> tall((size_t)maxg * W);
+  AZCHK(collective(c, [&]() -> int {
     HIPCHK(hipMemcpyAsync(d_tsend, tsend.data(), sizeof(pg::Game) * tsend.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemsetAsync(d_rsend, 0, (size_t)(R * rb), c->stream));   // what a rank with nothing left sends
     RCCLCHK(rc::g.AllGather(d_tsend, d_tall, (size_t)maxg, ncclInt64, c->comm, c->stream));
     HIPCHK(hipMemcpyAsync(tall.data(), d_tall, sizeof(pg::Game) * tall.size(), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    in_collective = false;
-    std::vector<std::vector<pg::Game>> tables((size_t)W);
-    for (int r = 0; r < W; ++r) tables[(size_t)r].assign(tall.begin() + (size_t)r * maxg, tall.begin() + (size_t)r * maxg + (size_t)all[(size_t)COMM_WORDS * r]);
-    const pg::Plan plan = pg::make_plan(tables, R, dst ? (long long)dst->cap : 0);
-    if (plan.dup) return fail(AZ_ERR_BAD_ARG, "game id %d occurs twice in the ranks' tables (ids are global and must be distinct); nothing was pushed", (int)plan.dup_id);
-    std::vector<long long> hplan(n_plan, 0);
-    long long *h_prefix = hplan.data(), *h_start = h_prefix + n_prefix, *h_goff = h_start + n_start, *h_B = h_goff + (W + 1), *h_src = h_B + W;
-    long long g0 = 0;
-    for (int r = 0; r < W; ++r) {
-      const pg::RankPlan& rp = plan.ranks[(size_t)r];
-      h_goff[r] = g0; h_B[r] = rp.B;
-      std::copy(rp.prefix.begin(), rp.prefix.end(), h_prefix + g0 + r);
-      std::copy(rp.start.begin(), rp.start.end(), h_start + g0);
-      g0 += (long long)rp.start.size();
-    }
-    h_goff[W] = g0;
-    const pg::RankPlan& mine = plan.ranks[(size_t)c->rank];
-    std::copy(mine.src.begin(), mine.src.end(), h_src);
-    const long long *d_prefix = d_plan, *d_start = d_prefix + n_prefix, *d_goff = d_start + n_start, *d_B = d_goff + (W + 1), *d_src = d_B + W;
-    const long long* d_myprefix = d_prefix + h_goff[c->rank] + c->rank;
-    // 4. rounds: pack -> all-gather -> scatter, R rows per rank; every rank runs plan.rounds of them
-    const int vec = (RW % 4 == 0 && rb % 16 == 0) ? 4 : RW % 2 == 0 ? 2 : 1;
-    const long long seq0 = src->total - B;
-    in_collective = true;
+    return AZ_OK;
+  }));
+  std::vector<std::vector<pg::Game>> tables((size_t)W);
+  for (int r = 0; r < W; ++r) tables[(size_t)r].assign(tall.begin() + (size_t)r * maxg, tall.begin() + (size_t)r * maxg + (size_t)all[(size_t)COMM_WORDS * r]);
+  const pg::Plan plan = pg::make_plan(tables, R, dst ? (long long)dst->cap : 0);
+  if (plan.dup) return fail(AZ_ERR_BAD_ARG, "game id %d occurs twice in the ranks' tables (ids are global and must be distinct); nothing was pushed", (int)plan.dup_id);
+  std::vector<long long> hplan(n_plan, 0);
+  long long *h_prefix = hplan.data(), *h_start = h_prefix + n_prefix, *h_goff = h_start + n_start, *h_B = h_goff + (W + 1), *h_src = h_B + W;
+  long long g0 = 0;
+  for (int r = 0; r < W; ++r) {
+    const pg::RankPlan& rp = plan.ranks[(size_t)r];
+    h_goff[r] = g0; h_B[r] = rp.B;
+    std::copy(rp.prefix.begin(), rp.prefix.end(), h_prefix + g0 + r);
+    std::copy(rp.start.begin(), rp.start.end(), h_start + g0);
+    g0 += (long long)rp.start.size();
+  }
+  h_goff[W] = g0;
+  const pg::RankPlan& mine = plan.ranks[(size_t)c->rank];
+  std::copy(mine.src.begin(), mine.src.end(), h_src);
+  const long long *d_prefix = d_plan, *d_start = d_prefix + n_prefix, *d_goff = d_start + n_start, *d_B = d_goff + (W + 1), *d_src = d_B + W;
+  const long long* d_myprefix = d_prefix + h_goff[c->rank] + c->rank;
+  // 4. rounds: pack -> all-gather -> scatter, R rows per rank; every rank runs plan.rounds of them
+  const int vec = (RW % 4 == 0 && rb % 16 == 0) ? 4 : RW % 2 == 0 ? 2 : 1;
+  const long long seq0 = src->total - B;
+  const auto rounds = [&]() -> int {
     HIPCHK(hipMemcpyAsync(d_plan, hplan.data(), sizeof(long long) * n_plan, hipMemcpyHostToDevice, c->stream));
     for (long long k = 0; k < plan.rounds; ++k) {
       const long long base = k * R, nrows = pg::round_rows_of(plan, c->rank, k);
@@ -601,18 +590,16 @@ extern "C" int az_comm_gather_push_planes(az_comm* c, az_plane_memory* src, az_p
       c->pack_ms += pm; c->scatter_ms += sm;
     }
     HIPCHK(hipStreamSynchronize(c->stream));
-    in_collective = false;
-    if (dst) { dst->total += plan.T; dst->cur_batch += plan.T; }       // push_trace! of every game: mem.cur_batch_size += n
-    if (stats) {
-      memset(stats, 0, sizeof *stats);
-      stats->games = totg; stats->moves = plan.T; stats->ranks = W;
-      stats->bytes = (int64_t)W * (COMM_WORDS * 8 + maxg * (long long)sizeof(pg::Game) + plan.rounds * R * rb);
-      stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      stats->gather_ms = std::max(0.0, stats->total_ms - c->scatter_ms);  // everything but the push into the memory
-    }
     return AZ_OK;
-  }();
-  if (st != AZ_OK && in_collective) abort_comm(c);
-  for (void* p : tmp) (void)hipFree(p);
-  return st;
+  };
+  AZCHK(collective(c, rounds));
+  if (dst) { dst->total += plan.T; dst->cur_batch += plan.T; }       // push_trace! of every game: mem.cur_batch_size += n
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    stats->games = totg; stats->moves = plan.T; stats->ranks = W;
+    stats->bytes = (int64_t)W * (COMM_WORDS * 8 + maxg * (long long)sizeof(pg::Game) + plan.rounds * R * rb);
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stats->gather_ms = std::max(0.0, stats->total_ms - c->scatter_ms);  // everything but the push into the memory
+  }
+  return AZ_OK;
 }

@@ -1,9 +1,12 @@
 // engine.h -- what the translation units of libazhip.so share: the engine record, error / launch macros, the
-// profiling helpers and the entry points of net.hip (network launches) used by azhip.hip, memory.hip and train.hip.
+// profiling helpers, the entry points of net.hip (network launches) used by azhip.hip, memory.hip and train.hip, the records of
+// the replay memories and their data set (with the one function that makes an empty az_dataset), the check that makes a device
+// current (use_device) and the scoped owner of a call's device scratch (Scratch).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -147,6 +150,7 @@ struct az_engine {
   bool net_loaded = false;
   std::vector<float> blob;
   std::unique_ptr<const NetMaps> net_maps;   // net_layout.h: the index maps of the arrays below; they depend on cfg only, so the first az_net_set_params builds them for all
+  std::vector<unsigned char> trainable;      // net_layout.h trainable_mask: built with net_maps; the regularisation sum of az_learning_status walks it
   NetDev net = {};
   Net16bDev net16b = {};         // bf16 fragments (cfg.net_bf16)
   Net16Dev net16 = {};           // k_tower16 fragments (64 filters)
@@ -323,43 +327,101 @@ int net_launch(az_engine* e, hipStream_t st, bool from_planes, float* hfeat, con
 // the network part of one search wave of slot group g (at most nmax leaves)
 int net_wave(az_engine* e, int g, bool split, int nmax);
 
-// ---- replay memory records shared by memory.hip and train.hip -------------------------------------------------
+// ---- devices and device memory ---------------------------------------------------------------------------------------------------
+// "is `device` a visible device; make it current": every creator's first step
+inline int use_device(int device) {
+  int ndev = 0;
+  HIPCHK(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return fail(AZ_ERR_BAD_ARG, "device %d not available (%d visible)", device, ndev);
+  HIPCHK(hipSetDevice(device));
+  return AZ_OK;
+}
+// n elements of device memory (at least 16 bytes), remembered in *keep when given: the owner frees what `keep` lists
+template <class T> inline int mem_alloc(std::vector<void*>* keep, T** p, size_t n) {
+  void* q = nullptr;
+  size_t bytes = std::max<size_t>(n * sizeof(T), 16);
+  hipError_t r = hipMalloc(&q, bytes);
+  if (r != hipSuccess) return fail(AZ_ERR_HIP, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(r));
+  if (keep) keep->push_back(q);
+  *p = (T*)q;
+  return AZ_OK;
+}
+// The device memory of ONE call: alloc() as mem_alloc, the destructor frees (in allocation order) on whichever path the call leaves,
+// so its body is straight-line code with AZCHK / HIPCHK.  Declare it before the first use of its memory and let it live until the
+// stream has been waited for.  scratch_live_bytes: what all Scratch objects of the process hold right now (az_debug_scratch_live_bytes;
+// 0 between calls, or a call leaked).
+inline std::atomic<long long> scratch_live_bytes{0};
+class Scratch {
+ public:
+  Scratch() = default;
+  Scratch(const Scratch&) = delete;
+  Scratch& operator=(const Scratch&) = delete;
+  ~Scratch() {
+    for (void* p : held) (void)hipFree(p);
+    scratch_live_bytes -= bytes;
+  }
+  template <class T> int alloc(T** p, size_t n) {
+    AZCHK(mem_alloc(&held, p, n));
+    const long long b = (long long)std::max<size_t>(n * sizeof(T), 16);
+    bytes += b; scratch_live_bytes += b;
+    return AZ_OK;
+  }
+ private:
+  std::vector<void*> held;
+  long long bytes = 0;
+};
+// Debug seam (not in azhip.h, no environment switch; azhip.hip): the process-wide count above.  tests/test_scratch_gpu.py reads 0 after
+// calls that succeed and calls that are refused half way.
+extern "C" int az_debug_scratch_live_bytes(int64_t* bytes);
+
+// ---- replay memory records shared by memory.hip, plane_memory.hip, comm.hip and train.hip -------------------------------------
+// Every member has its initial value here, as az_engine's: a creator fills the record step by step and the record's destroy takes it
+// apart at any point in between.
 struct az_memory {
-  int game, device;
-  GameInfo gi;
-  hipStream_t stream;
-  az_sample* d_buf;
-  int64_t cap, total, cur_batch;     // total = samples pushed since the last empty!; sample of sequence q sits at q % cap
+  int game = 0, device = 0;
+  GameInfo gi = {};
+  hipStream_t stream = nullptr;
+  az_sample* d_buf = nullptr;
+  int64_t cap = 0, total = 0, cur_batch = 0;   // total = samples pushed since the last empty!; sample of sequence q sits at q % cap
 };
 struct az_dataset {
-  int game, device;
-  GameInfo gi;
-  hipStream_t stream;
-  int64_t n, sum_n;
-  double Wtot;
-  float Wmean, Hp;
-  az_sample* d_samples;
-  GEnv* d_envs;
-  float *d_W, *d_X, *d_A, *d_P, *d_V;
+  int game = 0, device = 0;
+  GameInfo gi = {};
+  hipStream_t stream = nullptr;
+  int64_t n = 0, sum_n = 0;
+  double Wtot = 0.0;
+  float Wmean = 0.f, Hp = 0.f;
+  az_sample* d_samples = nullptr;
+  GEnv* d_envs = nullptr;
+  float *d_W = nullptr, *d_X = nullptr, *d_A = nullptr, *d_P = nullptr, *d_V = nullptr;
   std::vector<void*> allocs;
-  bool own_stream = false;           // az_dataset_create_from_tensors: no memory behind it whose stream it could share; d_samples and d_envs are NULL
+  bool own_stream = false;           // made from tensors or planes: no memory behind it whose stream it could share; d_samples and d_envs are NULL
 };
+// The empty data set every builder starts from (az_dataset_destroy takes it from here at any stage).  share != NULL: the data set
+// works on that stream, its memory's; otherwise it owns the stream its builder creates for it.
+inline int dataset_new(int game, int device, const GameInfo& gi, hipStream_t share, az_dataset** out) {
+  az_dataset* d = new (std::nothrow) az_dataset();
+  if (!d) return fail(AZ_ERR_HIP, "out of host memory");
+  d->game = game; d->device = device; d->gi = gi; d->stream = share; d->own_stream = !share;
+  *out = d;
+  return AZ_OK;
+}
 // plane_memory.hip: MemoryBuffer for a host-stepped game.  A sample is what the network sees -- the row (X, A) of RW = C*H*W + nA
 // Float32 words -- plus ND = nA + 2 doubles (pi by full action index, z, t) and n.
 struct az_plane_memory {
-  int game, device;
-  GameInfo gi;
-  hipStream_t stream;
-  int xs, nA, RW, ND;
-  float* d_XA;                       // [cap][RW]
-  double* d_D;                       // [cap][ND]
-  long long* d_n;                    // [cap]
-  int64_t cap, total, cur_batch;     // as az_memory
-  int hash_bits;                     // 128; az_debug_plane_memory_hash_bits lowers it
+  int game = 0, device = 0;
+  GameInfo gi = {};
+  hipStream_t stream = nullptr;
+  int xs = 0, nA = 0, RW = 0, ND = 0;
+  float* d_XA = nullptr;             // [cap][RW]
+  double* d_D = nullptr;             // [cap][ND]
+  long long* d_n = nullptr;          // [cap]
+  int64_t cap = 0, total = 0, cur_batch = 0;   // as az_memory
+  int hash_bits = 128;               // az_debug_plane_memory_hash_bits lowers it
   // GI.symmetries as the host declared them (az_plane_memory_set_symmetries): symmetry k as ONE gather over the row's RW words,
   // perm[k][w] = xperm[k][w] for w < xs, xs + aperm[k][w - xs] after; 16 bits hold an index below RW <= xs + 126
-  int nsym;                          // 0: none declared
-  unsigned short* d_perm;            // [AZ_PLANE_MAX_SYMMETRIES][RW], rows [0, nsym) valid
+  int nsym = 0;                      // 0: none declared
+  unsigned short* d_perm = nullptr;  // [AZ_PLANE_MAX_SYMMETRIES][RW], rows [0, nsym) valid
 };
 static constexpr int PM_WAVES = 4;    // wavefronts per workgroup of the plane kernels (plane_memory.hip, comm.hip): one sample / pair / group each
 static inline unsigned pm_grid(long long n) { return (unsigned)((n + PM_WAVES - 1) / PM_WAVES); }
@@ -374,17 +436,21 @@ extern "C" int az_debug_comm_plane_kernel_ms(az_comm* c, double* pack_ms, double
 __device__ __forceinline__ float sample_weight(int policy, long long n) {
   return policy == AZ_WEIGHT_CONSTANT ? 1.0f : policy == AZ_WEIGHT_LOG ? (float)(az_log2((double)n) + 1.0) : (float)n;
 }
+// What is wrong with a sample of caller-supplied tensors: k_ds_check (memory.hip) and k_pm_check (plane_memory.hip) leave the smallest
+// (sample << 3 | clause) that failed in one word that starts as ~0, so the message does not depend on scheduling.  Clause 2 is the
+// checker's own (W <= 0 there, n < 1 here): its text comes from the caller.
+enum SampleFault { SF_NONFINITE = 1, SF_OWN = 2, SF_A01 = 3, SF_NOLEGAL = 4, SF_PNEG = 5, SF_PILLEGAL = 6 };
+__device__ __forceinline__ void sample_fault_raise(unsigned long long* bad, long long sample, int clause) {
+  atomicMin(bad, ((unsigned long long)sample << 3) | (unsigned long long)clause);
+}
+inline int sample_fault_status(unsigned long long bad, const char* own_clause) {
+  if (bad == ~0ull) return AZ_OK;
+  const char* const what[] = {"", "a non-finite value", own_clause, "an entry of A outside {0, 1}", "no legal action (a row of A without a 1)",
+                              "P < 0", "P > 0 where A == 0 (the loss takes the logarithm of the masked policy there)"};
+  return fail(AZ_ERR_BAD_ARG, "sample %lld: %s", (long long)(bad >> 3), what[bad & 7]);
+}
 // memory.hip: checks the (W, X, A, P, V) tensors of a data set on the device as az_dataset_create_from_tensors documents
 // (AZ_ERR_BAD_ARG naming the first offending sample) and sets Wtot, Wmean and Hp from them
 int dataset_tensor_stats(az_dataset* d, hipStream_t st);
 // push_trace! (memory.jl:74-87) of ng games whose move records are ALREADY on the device: game g = d_moves[first[g] .. +cnt[g])
 int memory_push_device(az_memory* m, const az_move_rec* d_moves, const std::vector<long long>& first, const std::vector<int>& cnt, double gamma);
-template <class T> inline int mem_alloc(std::vector<void*>* keep, T** p, size_t n) {
-  void* q = nullptr;
-  size_t bytes = std::max<size_t>(n * sizeof(T), 16);
-  hipError_t r = hipMalloc(&q, bytes);
-  if (r != hipSuccess) return fail(AZ_ERR_HIP, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(r));
-  if (keep) keep->push_back(q);
-  *p = (T*)q;
-  return AZ_OK;
-}

@@ -431,10 +431,7 @@ extern "C" int az_host_tree_create(az_engine* e, int32_t device, int32_t num_act
     if (num_workers > e->nn_cap) return fail(AZ_ERR_BAD_ARG, "num_workers = %d above the %d rows one network launch of the engine takes", num_workers, e->nn_cap);
     device = e->device;
   }
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(AZ_ERR_BAD_ARG, "device %d outside 0..%d", device, ndev - 1);
-  HIPCHK(hipSetDevice(device));
+  AZCHK(use_device(device));
   az_host_tree* t = new (std::nothrow) az_host_tree;
   if (!t) return fail(AZ_ERR_HIP, "out of host memory");
   t->e = e; t->device = device; t->cfg = *cfg;

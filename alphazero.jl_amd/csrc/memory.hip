@@ -69,10 +69,6 @@ __global__ void k_mem_keys(const az_sample* __restrict__ s, long long n, unsigne
   if (i >= n) return;
   k0[i] = s[i].key[0]; k1[i] = s[i].key[1]; idx[i] = (unsigned int)i;
 }
-__global__ void k_mem_gather_u64(const unsigned long long* __restrict__ src, const unsigned int* __restrict__ idx, long long n, unsigned long long* dst) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = src[idx[i]];
-}
 __global__ void k_mem_heads(const az_sample* __restrict__ s, const unsigned int* __restrict__ order, long long n, int* head) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -243,11 +239,9 @@ __global__ void __launch_bounds__(256) k_batch_sums(const double* __restrict__ t
 }
 
 struct DevReducer {                     // deterministic sum of doubles (prims.h: fixed tiles, fixed tree)
+  Scratch mem;
   double* tmp = nullptr;
-  int init(long long nmax, hipStream_t) {
-    HIPCHK(hipMalloc((void**)&tmp, sizeof(double) * prims::sum_tmp_doubles(nmax)));
-    return AZ_OK;
-  }
+  int init(long long nmax, hipStream_t) { return mem.alloc(&tmp, prims::sum_tmp_doubles(nmax)); }
   int sum(const double* d_in, long long n, hipStream_t st, double* out) {
     double* d_res = nullptr;
     HIPCHK(prims::sum_doubles(d_in, n, tmp, &d_res, st));
@@ -262,7 +256,6 @@ struct DevReducer {                     // deterministic sum of doubles (prims.h
     HIPCHK(hipStreamSynchronize(st));
     return AZ_OK;
   }
-  ~DevReducer() { if (tmp) (void)hipFree(tmp); }
 };
 
 #define MEMORY(m) if (!(m)) return fail(AZ_ERR_BAD_ARG, "memory is NULL"); HIPCHK(hipSetDevice((m)->device))
@@ -274,19 +267,16 @@ extern "C" int az_memory_create(int32_t game, int32_t device, int64_t capacity, 
   if (!game_info(game, &gi)) return fail(AZ_ERR_BAD_ARG, "unknown game id %d", game);
   if (game == AZ_GAME_GO9_PLANES) return fail(AZ_ERR_BAD_ARG, "game id %d is a network-only tensor geometry (no device twin): the device replay memory needs the game's state keys; az_dataset_create_from_tensors takes the converted samples of such a game", game);
   if (capacity < 1 || capacity > (1LL << 31) - 1) return fail(AZ_ERR_BAD_ARG, "capacity must be in 1..2^31-1");
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(AZ_ERR_BAD_ARG, "device %d not available (%d visible)", device, ndev);
-  HIPCHK(hipSetDevice(device));
+  AZCHK(use_device(device));
   az_memory* m = new (std::nothrow) az_memory();
   if (!m) return fail(AZ_ERR_HIP, "out of host memory");
-  m->game = game; m->device = device; m->gi = gi; m->cap = capacity; m->total = 0; m->cur_batch = 0; m->d_buf = nullptr; m->stream = nullptr;
+  m->game = game; m->device = device; m->gi = gi; m->cap = capacity;
   int st = [&]() -> int {
     HIPCHK(hipStreamCreate(&m->stream));
     AZCHK(mem_alloc<az_sample>(nullptr, &m->d_buf, (size_t)capacity));
     return AZ_OK;
   }();
-  if (st != AZ_OK) { if (m->stream) (void)hipStreamDestroy(m->stream); delete m; return st; }
+  if (st != AZ_OK) { az_memory_destroy(m); return st; }
   *out = m;
   return AZ_OK;
 }
@@ -305,21 +295,15 @@ int memory_push_device(az_memory* m, const az_move_rec* d_moves, const std::vect
   long long tot = 0;
   for (int g = 0; g < ng; ++g) { seq0[g] = m->total + tot; tot += cnt[g]; }
   long long *d_first, *d_seq; int* d_cnt;
-  std::vector<void*> tmp;
-  auto cleanup = [&]() { for (void* p : tmp) (void)hipFree(p); };
-  int st = [&]() -> int {
-    AZCHK(mem_alloc(&tmp, &d_first, ng)); AZCHK(mem_alloc(&tmp, &d_cnt, ng)); AZCHK(mem_alloc(&tmp, &d_seq, ng));
-    HIPCHK(hipMemcpyAsync(d_first, first.data(), sizeof(long long) * ng, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(d_cnt, cnt.data(), sizeof(int) * ng, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(d_seq, seq0.data(), sizeof(long long) * ng, hipMemcpyHostToDevice, m->stream));
-    const long long min_seq = std::max<long long>(0, m->total + tot - m->cap);
-    DISPATCH_GAME(m->game, hipLaunchKernelGGL((k_mem_push<Gm>), dim3((ng + 255) / 256), dim3(256), 0, m->stream, d_moves, d_first, d_cnt, d_seq, ng, gamma, m->d_buf, (long long)m->cap, min_seq));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    HIPCHK(hipGetLastError());
-    return AZ_OK;
-  }();
-  cleanup();
-  AZCHK(st);
+  Scratch tmp;
+  AZCHK(tmp.alloc(&d_first, ng)); AZCHK(tmp.alloc(&d_cnt, ng)); AZCHK(tmp.alloc(&d_seq, ng));
+  HIPCHK(hipMemcpyAsync(d_first, first.data(), sizeof(long long) * ng, hipMemcpyHostToDevice, m->stream));
+  HIPCHK(hipMemcpyAsync(d_cnt, cnt.data(), sizeof(int) * ng, hipMemcpyHostToDevice, m->stream));
+  HIPCHK(hipMemcpyAsync(d_seq, seq0.data(), sizeof(long long) * ng, hipMemcpyHostToDevice, m->stream));
+  const long long min_seq = std::max<long long>(0, m->total + tot - m->cap);
+  DISPATCH_GAME(m->game, hipLaunchKernelGGL((k_mem_push<Gm>), dim3((ng + 255) / 256), dim3(256), 0, m->stream, d_moves, d_first, d_cnt, d_seq, ng, gamma, m->d_buf, (long long)m->cap, min_seq));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  HIPCHK(hipGetLastError());
   m->total += tot;
   m->cur_batch += tot;                                             // mem.cur_batch_size += n, memory.jl:86
   return AZ_OK;
@@ -337,13 +321,10 @@ extern "C" int az_memory_push(az_memory* m, const az_trace_buf* tr, double gamma
     first[g] = r.first_move; cnt[g] = r.num_moves;
   }
   az_move_rec* d_moves = nullptr;
-  HIPCHK(hipMalloc((void**)&d_moves, sizeof(az_move_rec) * (size_t)std::max<int64_t>(tr->num_moves, 1)));
-  int st = [&]() -> int {
-    HIPCHK(hipMemcpyAsync(d_moves, tr->moves, sizeof(az_move_rec) * (size_t)tr->num_moves, hipMemcpyHostToDevice, m->stream));
-    return memory_push_device(m, d_moves, first, cnt, gamma);
-  }();
-  (void)hipFree(d_moves);
-  return st;
+  Scratch tmp;
+  AZCHK(tmp.alloc(&d_moves, (size_t)tr->num_moves));
+  HIPCHK(hipMemcpyAsync(d_moves, tr->moves, sizeof(az_move_rec) * (size_t)tr->num_moves, hipMemcpyHostToDevice, m->stream));
+  return memory_push_device(m, d_moves, first, cnt, gamma);
 }
 // push_trace! for every game of the engine's last self-play phase, in game-id order, straight from the engine's
 // device-resident move records (src/training.jl:284-299 -> src/memory.jl:74-87 without the 64 B per position ever
@@ -403,70 +384,61 @@ static int dataset_build(az_memory* m, az_dataset* d, int which, bool use_sym, b
   const int nsym = use_sym ? Gm::NSYM : 0;
   const int64_t n1 = n0 * (1 + nsym);
   if (n1 > (1LL << 31) - 1) return fail(AZ_ERR_CAPACITY, "data set too large");
-  std::vector<void*> tmp;
-  auto cleanup = [&]() { for (void* p : tmp) (void)hipFree(p); };
-  int rc = [&]() -> int {
-    az_sample* s1;
-    AZCHK(mem_alloc(&tmp, &s1, (size_t)n1));
-    if (n0) hipLaunchKernelGGL(k_mem_gather, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, m->d_buf, (long long)m->cap, seq0, (long long)n0, s1);
-    if (nsym && n0) hipLaunchKernelGGL((k_mem_augment<Gm>), dim3((unsigned)((n0 * nsym + 255) / 256)), dim3(256), 0, st, s1, (long long)n0, s1);
-    int64_t n2 = n1;
-    if (merge && n1 > 0) {
-      unsigned long long *k0, *k1, *ks, *ks2; unsigned int *i0, *i1, *i2; int *head, *seg;
-      AZCHK(mem_alloc(&tmp, &k0, (size_t)n1)); AZCHK(mem_alloc(&tmp, &k1, (size_t)n1)); AZCHK(mem_alloc(&tmp, &ks, (size_t)n1)); AZCHK(mem_alloc(&tmp, &ks2, (size_t)n1));
-      AZCHK(mem_alloc(&tmp, &i0, (size_t)n1)); AZCHK(mem_alloc(&tmp, &i1, (size_t)n1)); AZCHK(mem_alloc(&tmp, &i2, (size_t)n1));
-      AZCHK(mem_alloc(&tmp, &head, (size_t)n1)); AZCHK(mem_alloc(&tmp, &seg, (size_t)n1));
-      const unsigned gb = (unsigned)((n1 + 255) / 256);
-      hipLaunchKernelGGL(k_mem_keys, dim3(gb), dim3(256), 0, st, s1, (long long)n1, k0, k1, i0);
-      // LSD: stable sort by key[1], then by key[0] -> ascending (key[0], key[1], buffer index)
-      int* stmp;
-      AZCHK(mem_alloc(&tmp, &stmp, std::max(prims::sort_tmp_ints(n1), prims::scan_tmp_ints(n1))));
-      HIPCHK(prims::sort_pairs(k1, ks, i0, i1, n1, stmp, st));        // (k1, i0) are the sort's ping-pong partner: not used again
-      hipLaunchKernelGGL(k_mem_gather_u64, dim3(gb), dim3(256), 0, st, k0, i1, (long long)n1, ks2);
-      HIPCHK(prims::sort_pairs(ks2, ks, i1, i2, n1, stmp, st));
-      hipLaunchKernelGGL(k_mem_heads, dim3(gb), dim3(256), 0, st, s1, i2, (long long)n1, head);
-      HIPCHK(prims::scan_ints(head, seg, n1, true, stmp, st));
-      int nseg = 0;
-      HIPCHK(hipMemcpyAsync(&nseg, seg + (n1 - 1), sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      n2 = nseg;
-      AZCHK(mem_alloc(&d->allocs, &d->d_samples, (size_t)n2));
-      static_assert(sizeof(az_sample) == 14 * 8, "k_mem_merge walks az_sample as 14 words");
-      int* long_count; long long* long_list;
-      const long long max_long = n1 / MERGE_LONG + 1;
-      AZCHK(mem_alloc(&tmp, &long_count, 1)); AZCHK(mem_alloc(&tmp, &long_list, (size_t)(2 * max_long)));
-      HIPCHK(hipMemsetAsync(long_count, 0, sizeof(int), st));
-      hipLaunchKernelGGL(k_mem_merge, dim3((unsigned)((n1 * 16 + 255) / 256)), dim3(256), 0, st, s1, i2, head, seg, (long long)n1, d->d_samples, long_count, long_list);
-      hipLaunchKernelGGL(k_mem_merge_long, dim3((unsigned)max_long), dim3(14 * 64), 0, st, s1, i2, seg, long_count, long_list, d->d_samples);
-    } else {
-      AZCHK(mem_alloc(&d->allocs, &d->d_samples, (size_t)n2));
-      if (n2) HIPCHK(hipMemcpyAsync(d->d_samples, s1, sizeof(az_sample) * (size_t)n2, hipMemcpyDeviceToDevice, st));
-    }
-    d->n = n2;
-    AZCHK(mem_alloc(&d->allocs, &d->d_envs, (size_t)n2)); AZCHK(mem_alloc(&d->allocs, &d->d_W, (size_t)n2)); AZCHK(mem_alloc(&d->allocs, &d->d_V, (size_t)n2));
-    AZCHK(mem_alloc(&d->allocs, &d->d_A, (size_t)n2 * Gm::A)); AZCHK(mem_alloc(&d->allocs, &d->d_P, (size_t)n2 * Gm::A));
-    AZCHK(mem_alloc(&d->allocs, &d->d_X, (size_t)n2 * Gm::C * Gm::P));
-    d->sum_n = 0; d->Wtot = 0.0; d->Wmean = 0.f; d->Hp = 0.f;
-    if (n2) {
-      double *tw, *thp; long long* tn;
-      AZCHK(mem_alloc(&tmp, &tw, (size_t)n2)); AZCHK(mem_alloc(&tmp, &thp, (size_t)n2)); AZCHK(mem_alloc(&tmp, &tn, (size_t)n2));
-      hipLaunchKernelGGL((k_mem_convert<Gm>), dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, d->d_samples, (long long)n2, policy, d->d_envs, d->d_W, d->d_A, d->d_P, d->d_V, tw, thp, tn);
-      const long long ne = (long long)n2 * Gm::C * Gm::P;
-      hipLaunchKernelGGL((k_mem_planes<Gm>), dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, d->d_envs, (long long)n2, d->d_X);
-      DevReducer red;
-      AZCHK(red.init(n2, st));
-      double sw, shp; long long sn;
-      AZCHK(red.sum(tw, n2, st, &sw)); AZCHK(red.sum(thp, n2, st, &shp)); AZCHK(red.sum(tn, n2, st, &sn));
-      d->Wtot = sw; d->sum_n = (int64_t)sn;
-      d->Wmean = (float)(sw / (double)n2);                         // mean(W), learning.jl:110
-      d->Hp = (float)(-shp / sw);                                  // entropy_wmean(P, W), learning.jl:111
-    }
+  Scratch tmp;
+  az_sample* s1;
+  AZCHK(tmp.alloc(&s1, (size_t)n1));
+  if (n0) hipLaunchKernelGGL(k_mem_gather, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, m->d_buf, (long long)m->cap, seq0, (long long)n0, s1);
+  if (nsym && n0) hipLaunchKernelGGL((k_mem_augment<Gm>), dim3((unsigned)((n0 * nsym + 255) / 256)), dim3(256), 0, st, s1, (long long)n0, s1);
+  int64_t n2 = n1;
+  if (merge && n1 > 0) {
+    unsigned long long *k0, *k1, *ks, *ks2; unsigned int *i0, *i1, *i2; int *head, *seg;
+    AZCHK(tmp.alloc(&k0, (size_t)n1)); AZCHK(tmp.alloc(&k1, (size_t)n1)); AZCHK(tmp.alloc(&ks, (size_t)n1)); AZCHK(tmp.alloc(&ks2, (size_t)n1));
+    AZCHK(tmp.alloc(&i0, (size_t)n1)); AZCHK(tmp.alloc(&i1, (size_t)n1)); AZCHK(tmp.alloc(&i2, (size_t)n1));
+    AZCHK(tmp.alloc(&head, (size_t)n1)); AZCHK(tmp.alloc(&seg, (size_t)n1));
+    const unsigned gb = (unsigned)((n1 + 255) / 256);
+    hipLaunchKernelGGL(k_mem_keys, dim3(gb), dim3(256), 0, st, s1, (long long)n1, k0, k1, i0);
+    int* stmp;
+    AZCHK(tmp.alloc(&stmp, std::max(prims::sort_tmp_ints(n1), prims::scan_tmp_ints(n1))));
+    HIPCHK(prims::order_by_key(k0, k1, i0, ks, ks2, i1, i2, n1, stmp, st));   // i2: ascending (key[0], key[1], buffer index)
+    hipLaunchKernelGGL(k_mem_heads, dim3(gb), dim3(256), 0, st, s1, i2, (long long)n1, head);
+    HIPCHK(prims::scan_ints(head, seg, n1, true, stmp, st));
+    int nseg = 0;
+    HIPCHK(hipMemcpyAsync(&nseg, seg + (n1 - 1), sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    return AZ_OK;
-  }();
-  cleanup();
-  return rc;
+    n2 = nseg;
+    AZCHK(mem_alloc(&d->allocs, &d->d_samples, (size_t)n2));
+    static_assert(sizeof(az_sample) == 14 * 8, "k_mem_merge walks az_sample as 14 words");
+    int* long_count; long long* long_list;
+    const long long max_long = n1 / MERGE_LONG + 1;
+    AZCHK(tmp.alloc(&long_count, 1)); AZCHK(tmp.alloc(&long_list, (size_t)(2 * max_long)));
+    HIPCHK(hipMemsetAsync(long_count, 0, sizeof(int), st));
+    hipLaunchKernelGGL(k_mem_merge, dim3((unsigned)((n1 * 16 + 255) / 256)), dim3(256), 0, st, s1, i2, head, seg, (long long)n1, d->d_samples, long_count, long_list);
+    hipLaunchKernelGGL(k_mem_merge_long, dim3((unsigned)max_long), dim3(14 * 64), 0, st, s1, i2, seg, long_count, long_list, d->d_samples);
+  } else {
+    AZCHK(mem_alloc(&d->allocs, &d->d_samples, (size_t)n2));
+    if (n2) HIPCHK(hipMemcpyAsync(d->d_samples, s1, sizeof(az_sample) * (size_t)n2, hipMemcpyDeviceToDevice, st));
+  }
+  d->n = n2;
+  AZCHK(mem_alloc(&d->allocs, &d->d_envs, (size_t)n2)); AZCHK(mem_alloc(&d->allocs, &d->d_W, (size_t)n2)); AZCHK(mem_alloc(&d->allocs, &d->d_V, (size_t)n2));
+  AZCHK(mem_alloc(&d->allocs, &d->d_A, (size_t)n2 * Gm::A)); AZCHK(mem_alloc(&d->allocs, &d->d_P, (size_t)n2 * Gm::A));
+  AZCHK(mem_alloc(&d->allocs, &d->d_X, (size_t)n2 * Gm::C * Gm::P));
+  if (n2) {
+    double *tw, *thp; long long* tn;
+    AZCHK(tmp.alloc(&tw, (size_t)n2)); AZCHK(tmp.alloc(&thp, (size_t)n2)); AZCHK(tmp.alloc(&tn, (size_t)n2));
+    hipLaunchKernelGGL((k_mem_convert<Gm>), dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, d->d_samples, (long long)n2, policy, d->d_envs, d->d_W, d->d_A, d->d_P, d->d_V, tw, thp, tn);
+    const long long ne = (long long)n2 * Gm::C * Gm::P;
+    hipLaunchKernelGGL((k_mem_planes<Gm>), dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, d->d_envs, (long long)n2, d->d_X);
+    DevReducer red;
+    AZCHK(red.init(n2, st));
+    double sw, shp; long long sn;
+    AZCHK(red.sum(tw, n2, st, &sw)); AZCHK(red.sum(thp, n2, st, &shp)); AZCHK(red.sum(tn, n2, st, &sn));
+    d->Wtot = sw; d->sum_n = (int64_t)sn;
+    d->Wmean = (float)(sw / (double)n2);                         // mean(W), learning.jl:110
+    d->Hp = (float)(-shp / sw);                                  // entropy_wmean(P, W), learning.jl:111
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  return AZ_OK;
 }
 
 extern "C" int az_dataset_destroy(az_dataset* d) {
@@ -484,9 +456,8 @@ extern "C" int az_dataset_create(az_memory* m, int32_t which, int32_t use_symmet
   *out = nullptr;
   if (which != 0 && which != 1) return fail(AZ_ERR_BAD_ARG, "which must be 0 (get_experience) or 1 (last_batch)");
   if (weighing_policy < AZ_WEIGHT_CONSTANT || weighing_policy > AZ_WEIGHT_LINEAR) return fail(AZ_ERR_BAD_ARG, "unknown samples_weighing_policy %d", weighing_policy);
-  az_dataset* d = new (std::nothrow) az_dataset();
-  if (!d) return fail(AZ_ERR_HIP, "out of host memory");
-  d->game = m->game; d->device = m->device; d->gi = m->gi; d->stream = m->stream; d->n = 0;
+  az_dataset* d = nullptr;
+  AZCHK(dataset_new(m->game, m->device, m->gi, m->stream, &d));
   int st = AZ_OK;
   switch (m->game) {
     case AZ_GAME_CONNECT_FOUR: st = dataset_build<ConnectFour>(m, d, which, use_symmetries != 0, use_position_averaging != 0, weighing_policy); break;
@@ -500,8 +471,7 @@ extern "C" int az_dataset_create(az_memory* m, int32_t which, int32_t use_symmet
 }
 // A data set made from the (W, X, A, P, V) tensors of convert_samples (learning.jl:17-51) that a host computed itself: one thread
 // per sample checks what the loss relies on and leaves the sample's terms of Wtot and of Hp = entropy_wmean(P, W) (learning.jl:63,111).
-// bad = the smallest (sample << 3 | clause) that failed, so the message does not depend on scheduling.
-enum { DS_NONFINITE = 1, DS_W = 2, DS_A01 = 3, DS_NOLEGAL = 4, DS_PNEG = 5, DS_PILLEGAL = 6 };
+// What fails raises its SampleFault clause (engine.h); the checker's own clause is W <= 0.
 __global__ void __launch_bounds__(256) k_ds_check(const float* __restrict__ W, const float* __restrict__ X, const float* __restrict__ A, const float* __restrict__ P,
                                                   const float* __restrict__ V, long long n, int xs, int nA, unsigned long long* __restrict__ bad,
                                                   double* __restrict__ t_w, double* __restrict__ t_hp) {
@@ -522,39 +492,31 @@ __global__ void __launch_bounds__(256) k_ds_check(const float* __restrict__ W, c
     pill = pill || (p > 0.0f && m == 0.0f);
     hp += (double)(p * az_logf(p + 1.1920929e-07f) * w);             // the term k_mem_convert leaves for a memory-made data set
   }
-  const int code = !finite ? DS_NONFINITE : !(w > 0.0f) ? DS_W : !a01 ? DS_A01 : legal == 0 ? DS_NOLEGAL : pneg ? DS_PNEG : pill ? DS_PILLEGAL : 0;
-  if (code) atomicMin(bad, ((unsigned long long)i << 3) | (unsigned long long)code);
+  const int code = !finite ? SF_NONFINITE : !(w > 0.0f) ? SF_OWN : !a01 ? SF_A01 : legal == 0 ? SF_NOLEGAL : pneg ? SF_PNEG : pill ? SF_PILLEGAL : 0;
+  if (code) sample_fault_raise(bad, i, code);
   t_w[i] = (double)w; t_hp[i] = code ? 0.0 : hp;
 }
 int dataset_tensor_stats(az_dataset* d, hipStream_t st) {
   const int64_t n = d->n;
   const size_t xs = (size_t)d->gi.C * d->gi.P, nA = (size_t)d->gi.A, N = (size_t)n;
-  std::vector<void*> tmp;
-  int rc = [&]() -> int {
-    unsigned long long* d_bad; double *tw, *thp;
-    AZCHK(mem_alloc(&tmp, &d_bad, 1)); AZCHK(mem_alloc(&tmp, &tw, N)); AZCHK(mem_alloc(&tmp, &thp, N));
-    HIPCHK(hipMemsetAsync(d_bad, 0xff, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_ds_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d->d_W, d->d_X, d->d_A, d->d_P, d->d_V, (long long)n, (int)xs, (int)nA, d_bad, tw, thp);
-    unsigned long long bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    if (bad != ~0ull) {
-      static const char* const what[] = {"", "a non-finite value", "W <= 0", "an entry of A outside {0, 1}", "no legal action (a row of A without a 1)",
-                                         "P < 0", "P > 0 where A == 0 (the loss takes the logarithm of the masked policy there)"};
-      return fail(AZ_ERR_BAD_ARG, "sample %lld: %s", (long long)(bad >> 3), what[bad & 7]);
-    }
-    DevReducer red;                                                  // the reducer of dataset_build: the same tiles and tree for the same n
-    AZCHK(red.init(n, st));
-    double sw, shp;
-    AZCHK(red.sum(tw, n, st, &sw)); AZCHK(red.sum(thp, n, st, &shp));
-    d->Wtot = sw;
-    d->Wmean = (float)(sw / (double)n);                              // mean(W), learning.jl:110
-    d->Hp = (float)(-shp / sw);                                      // entropy_wmean(P, W), learning.jl:111
-    return AZ_OK;
-  }();
-  for (void* p : tmp) (void)hipFree(p);
-  return rc;
+  Scratch tmp;
+  unsigned long long* d_bad; double *tw, *thp;
+  AZCHK(tmp.alloc(&d_bad, 1)); AZCHK(tmp.alloc(&tw, N)); AZCHK(tmp.alloc(&thp, N));
+  HIPCHK(hipMemsetAsync(d_bad, 0xff, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_ds_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d->d_W, d->d_X, d->d_A, d->d_P, d->d_V, (long long)n, (int)xs, (int)nA, d_bad, tw, thp);
+  unsigned long long bad = 0;
+  HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  AZCHK(sample_fault_status(bad, "W <= 0"));
+  DevReducer red;                                                    // the reducer of dataset_build: the same tiles and tree for the same n
+  AZCHK(red.init(n, st));
+  double sw, shp;
+  AZCHK(red.sum(tw, n, st, &sw)); AZCHK(red.sum(thp, n, st, &shp));
+  d->Wtot = sw;
+  d->Wmean = (float)(sw / (double)n);                                // mean(W), learning.jl:110
+  d->Hp = (float)(-shp / sw);                                        // entropy_wmean(P, W), learning.jl:111
+  return AZ_OK;
 }
 extern "C" int az_dataset_create_from_tensors(int32_t game, int32_t device, int64_t n, const float* W, const float* X, const float* A,
                                               const float* P, const float* V, az_dataset** out) {
@@ -564,14 +526,10 @@ extern "C" int az_dataset_create_from_tensors(int32_t game, int32_t device, int6
   if (!game_info(game, &gi)) return fail(AZ_ERR_BAD_ARG, "unknown game id %d", game);
   if (n < 1 || n > (1LL << 31) - 1) return fail(AZ_ERR_BAD_ARG, "n must be in 1..2^31-1");
   if (!W || !X || !A || !P || !V) return fail(AZ_ERR_BAD_ARG, "NULL tensor");
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(AZ_ERR_BAD_ARG, "device %d not available (%d visible)", device, ndev);
-  HIPCHK(hipSetDevice(device));
-  az_dataset* d = new (std::nothrow) az_dataset();
-  if (!d) return fail(AZ_ERR_HIP, "out of host memory");
-  d->game = game; d->device = device; d->gi = gi; d->stream = nullptr; d->own_stream = true; d->n = n; d->sum_n = n;
-  d->Wtot = 0.0; d->Wmean = 0.f; d->Hp = 0.f; d->d_samples = nullptr; d->d_envs = nullptr;
+  AZCHK(use_device(device));
+  az_dataset* d = nullptr;
+  AZCHK(dataset_new(game, device, gi, nullptr, &d));
+  d->n = n; d->sum_n = n;
   int rc = [&]() -> int {
     HIPCHK(hipStreamCreate(&d->stream));
     hipStream_t st = d->stream;
@@ -614,18 +572,12 @@ extern "C" int az_dataset_read(az_dataset* d, int64_t first, int64_t count, az_s
   return AZ_OK;
 }
 
-// Sum of squares of the trainable parameters (Flux.params: all but the BatchNorm running statistics), host side
+// Sum of squares of the trainable parameters (Flux.params: all but the BatchNorm running statistics), host side: one accumulator
+// over the blob in ascending order
 static double reg_sum_trainable(const az_engine* e) {
-  const GameInfo& gi = e->gi;
-  const size_t P = gi.P, F = e->cfg.num_filters, npf = e->cfg.num_policy_head_filters, nvf = e->cfg.num_value_head_filters;
-  const float* b = e->blob.data();
+  const std::vector<unsigned char>& trainable = e->trainable;
   double s = 0.0;
-  auto take = [&](size_t c) { for (size_t i = 0; i < c; ++i) s += (double)b[i] * (double)b[i]; b += c; };
-  auto skip = [&](size_t c) { b += c; };
-  take(9 * (size_t)gi.C * F); take(F); take(2 * F); skip(2 * F);
-  for (int l = 0; l < 2 * e->cfg.num_blocks; ++l) { take(9 * F * F); take(F); take(2 * F); skip(2 * F); }
-  take(F * npf); take(npf); take(2 * npf); skip(2 * npf); take((size_t)gi.A * P * npf); take(gi.A);
-  take(F * nvf); take(nvf); take(2 * nvf); skip(2 * nvf); take(F * P * nvf); take(F); take(F); take(1);
+  for (size_t i = 0; i < trainable.size(); ++i) if (trainable[i]) s += (double)e->blob[i] * (double)e->blob[i];
   return s;
 }
 
@@ -636,57 +588,52 @@ static int learning_status_run(az_engine* e, az_dataset* d, double l2, double ci
   const int nA = d->gi.A;
   const size_t xs = (size_t)d->gi.C * d->gi.P;
   hipStream_t st = e->stream;
-  std::vector<void*> tmp;
-  auto cleanup = [&]() { for (void* p : tmp) (void)hipFree(p); };
-  int rc = [&]() -> int {
-    float *Ph, *Vh, *Pinv; double *tkl, *thn, *tmse, *tinv, *tw;
-    AZCHK(mem_alloc(&tmp, &Ph, (size_t)n * nA)); AZCHK(mem_alloc(&tmp, &Vh, (size_t)n)); AZCHK(mem_alloc(&tmp, &Pinv, (size_t)n));
-    AZCHK(mem_alloc(&tmp, &tkl, (size_t)n)); AZCHK(mem_alloc(&tmp, &thn, (size_t)n)); AZCHK(mem_alloc(&tmp, &tmse, (size_t)n)); AZCHK(mem_alloc(&tmp, &tinv, (size_t)n));
-    AZCHK(mem_alloc(&tmp, &tw, (size_t)n));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    // Network.forward_normalized (network.jl:264-271) in test mode on the device-resident states, nn_cap at a time
-    const int64_t nchunks = (n + e->nn_cap - 1) / e->nn_cap;
-    std::vector<int> counts((size_t)nchunks);
-    for (int64_t c = 0; c < nchunks; ++c) counts[c] = (int)std::min<int64_t>(e->nn_cap, n - c * e->nn_cap);
-    int* d_counts;
-    AZCHK(mem_alloc(&tmp, &d_counts, (size_t)nchunks));
-    HIPCHK(hipMemcpyAsync(d_counts, counts.data(), sizeof(int) * (size_t)nchunks, hipMemcpyHostToDevice, st));
-    for (int64_t c = 0; c < nchunks; ++c) {
-      const int64_t off = c * e->nn_cap;
-      if (d->d_envs) AZCHK(net_launch(e, st, false, e->d_hfeat, d->d_envs + off, e->d_iota, d_counts + c, counts[c], nullptr, nullptr, Ph + (size_t)off * nA, Vh + off, Pinv + off, nA));
-      else AZCHK(net_launch(e, st, true, e->d_hfeat, nullptr, nullptr, nullptr, counts[c], d->d_X + (size_t)off * xs, d->d_A + (size_t)off * nA, Ph + (size_t)off * nA, Vh + off, Pinv + off, nA));
-    }
-    HIPCHK(hipStreamSynchronize(st));                              // `counts` must outlive the copy
-    hipLaunchKernelGGL(k_loss_terms, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d->d_W, d->d_P, d->d_V, Ph, Vh, Pinv, (long long)n, nA, (float)renorm, tkl, thn, tmse, tinv);
-    hipLaunchKernelGGL(k_f32_to_f64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d->d_W, (long long)n, tw);
-    if (batch > n) batch = n;
-    const int64_t nb = (n + batch - 1) / batch;                    // DataLoader(partial = true), learning.jl:171-176
-    double* d_sums;
-    AZCHK(mem_alloc(&tmp, &d_sums, (size_t)nb * 5));
-    hipLaunchKernelGGL(k_batch_sums, dim3((unsigned)nb), dim3(256), 0, st, tw, tkl, thn, tmse, tinv, (long long)n, (long long)batch, d_sums);
-    std::vector<double> sums((size_t)nb * 5);
-    HIPCHK(hipMemcpyAsync(sums.data(), d_sums, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const float Lreg = l2 == 0.0 ? 0.f : (float)((double)(float)l2 * reg_sum_trainable(e));
-    double aL = 0., aLp = 0., aLv = 0., aLreg = 0., aLinv = 0., aHn = 0., aw = 0.;
-    for (int64_t b = 0; b < nb; ++b) {
-      const int64_t m = std::min<int64_t>(batch, n - b * batch);
-      const double bw = sums[b * 5], kl = sums[b * 5 + 1], hn = sums[b * 5 + 2], mse = sums[b * 5 + 3], inv = sums[b * 5 + 4];
-      const float Lp = (float)(-kl / bw) - d->Hp;
-      const float Lv = (float)(mse / bw);
-      const float Linv = cinv == 0.0 ? 0.f : (float)cinv * (float)(inv / bw);
-      const float L = ((float)(bw / (double)m) / d->Wmean) * (Lp + Lv + Lreg + Linv);
-      const float Hn = (float)(-hn / bw);
-      aL += (double)L * bw; aLp += (double)Lp * bw; aLv += (double)Lv * bw; aLreg += (double)Lreg * bw;
-      aLinv += (double)Linv * bw; aHn += (double)Hn * bw; aw += bw;
-    }
-    out->L = (float)(aL / aw); out->Lp = (float)(aLp / aw); out->Lv = (float)(aLv / aw); out->Lreg = (float)(aLreg / aw);
-    out->Linv = (float)(aLinv / aw); out->Hp = d->Hp; out->Hpnet = (float)(aHn / aw);
-    HIPCHK(hipGetLastError());
-    return AZ_OK;
-  }();
-  cleanup();
-  return rc;
+  Scratch tmp;
+  float *Ph, *Vh, *Pinv; double *tkl, *thn, *tmse, *tinv, *tw;
+  AZCHK(tmp.alloc(&Ph, (size_t)n * nA)); AZCHK(tmp.alloc(&Vh, (size_t)n)); AZCHK(tmp.alloc(&Pinv, (size_t)n));
+  AZCHK(tmp.alloc(&tkl, (size_t)n)); AZCHK(tmp.alloc(&thn, (size_t)n)); AZCHK(tmp.alloc(&tmse, (size_t)n)); AZCHK(tmp.alloc(&tinv, (size_t)n));
+  AZCHK(tmp.alloc(&tw, (size_t)n));
+  HIPCHK(hipStreamSynchronize(d->stream));
+  // Network.forward_normalized (network.jl:264-271) in test mode on the device-resident states, nn_cap at a time
+  const int64_t nchunks = (n + e->nn_cap - 1) / e->nn_cap;
+  std::vector<int> counts((size_t)nchunks);
+  for (int64_t c = 0; c < nchunks; ++c) counts[c] = (int)std::min<int64_t>(e->nn_cap, n - c * e->nn_cap);
+  int* d_counts;
+  AZCHK(tmp.alloc(&d_counts, (size_t)nchunks));
+  HIPCHK(hipMemcpyAsync(d_counts, counts.data(), sizeof(int) * (size_t)nchunks, hipMemcpyHostToDevice, st));
+  for (int64_t c = 0; c < nchunks; ++c) {
+    const int64_t off = c * e->nn_cap;
+    if (d->d_envs) AZCHK(net_launch(e, st, false, e->d_hfeat, d->d_envs + off, e->d_iota, d_counts + c, counts[c], nullptr, nullptr, Ph + (size_t)off * nA, Vh + off, Pinv + off, nA));
+    else AZCHK(net_launch(e, st, true, e->d_hfeat, nullptr, nullptr, nullptr, counts[c], d->d_X + (size_t)off * xs, d->d_A + (size_t)off * nA, Ph + (size_t)off * nA, Vh + off, Pinv + off, nA));
+  }
+  HIPCHK(hipStreamSynchronize(st));                              // `counts` must outlive the copy
+  hipLaunchKernelGGL(k_loss_terms, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d->d_W, d->d_P, d->d_V, Ph, Vh, Pinv, (long long)n, nA, (float)renorm, tkl, thn, tmse, tinv);
+  hipLaunchKernelGGL(k_f32_to_f64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d->d_W, (long long)n, tw);
+  if (batch > n) batch = n;
+  const int64_t nb = (n + batch - 1) / batch;                    // DataLoader(partial = true), learning.jl:171-176
+  double* d_sums;
+  AZCHK(tmp.alloc(&d_sums, (size_t)nb * 5));
+  hipLaunchKernelGGL(k_batch_sums, dim3((unsigned)nb), dim3(256), 0, st, tw, tkl, thn, tmse, tinv, (long long)n, (long long)batch, d_sums);
+  std::vector<double> sums((size_t)nb * 5);
+  HIPCHK(hipMemcpyAsync(sums.data(), d_sums, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const float Lreg = l2 == 0.0 ? 0.f : (float)((double)(float)l2 * reg_sum_trainable(e));
+  double aL = 0., aLp = 0., aLv = 0., aLreg = 0., aLinv = 0., aHn = 0., aw = 0.;
+  for (int64_t b = 0; b < nb; ++b) {
+    const int64_t m = std::min<int64_t>(batch, n - b * batch);
+    const double bw = sums[b * 5], kl = sums[b * 5 + 1], hn = sums[b * 5 + 2], mse = sums[b * 5 + 3], inv = sums[b * 5 + 4];
+    const float Lp = (float)(-kl / bw) - d->Hp;
+    const float Lv = (float)(mse / bw);
+    const float Linv = cinv == 0.0 ? 0.f : (float)cinv * (float)(inv / bw);
+    const float L = ((float)(bw / (double)m) / d->Wmean) * (Lp + Lv + Lreg + Linv);
+    const float Hn = (float)(-hn / bw);
+    aL += (double)L * bw; aLp += (double)Lp * bw; aLv += (double)Lv * bw; aLreg += (double)Lreg * bw;
+    aLinv += (double)Linv * bw; aHn += (double)Hn * bw; aw += bw;
+  }
+  out->L = (float)(aL / aw); out->Lp = (float)(aLp / aw); out->Lv = (float)(aLv / aw); out->Lreg = (float)(aLreg / aw);
+  out->Linv = (float)(aLinv / aw); out->Hp = d->Hp; out->Hpnet = (float)(aHn / aw);
+  HIPCHK(hipGetLastError());
+  return AZ_OK;
 }
 
 extern "C" int az_learning_status(az_engine* e, az_dataset* d, double l2_regularization, double nonvalidity_penalty,

@@ -26,8 +26,7 @@
 #define PLANE_MEMORY(m) if (!(m)) return fail(AZ_ERR_BAD_ARG, "plane memory is NULL"); HIPCHK(hipSetDevice((m)->device))
 
 // ---- push: check the staged samples, then store them into the ring ----------------------------------------------------------------
-enum { PM_NONFINITE = 1, PM_NVIS = 2, PM_A01 = 3, PM_NOLEGAL = 4, PM_PNEG = 5, PM_PILLEGAL = 6 };
-// One wavefront per sample, lanes over the words.  bad = the smallest (sample << 3 | clause) that failed (k_ds_check's encoding).
+// One wavefront per sample, lanes over the words.  What fails raises its SampleFault clause (engine.h); the checker's own clause is n < 1.
 __global__ void __launch_bounds__(64 * PM_WAVES) k_pm_check(const float* __restrict__ X, const float* __restrict__ A, const double* __restrict__ P,
                                                             const double* __restrict__ z, const double* __restrict__ t, const long long* __restrict__ nv,
                                                             long long n, int xs, int nA, unsigned long long* __restrict__ bad) {
@@ -47,9 +46,9 @@ __global__ void __launch_bounds__(64 * PM_WAVES) k_pm_check(const float* __restr
   }
   if (lane == 0) finite = finite && isfinite(z[i]) && isfinite(t[i]);
   const bool nbad = nv && nv[i] < 1;
-  const int code = __ballot(!finite) ? PM_NONFINITE : nbad ? PM_NVIS : __ballot(!a01) ? PM_A01 : !__ballot(legal) ? PM_NOLEGAL
-                   : __ballot(pneg) ? PM_PNEG : __ballot(pill) ? PM_PILLEGAL : 0;
-  if (code && lane == 0) atomicMin(bad, ((unsigned long long)i << 3) | (unsigned long long)code);
+  const int code = __ballot(!finite) ? SF_NONFINITE : nbad ? SF_OWN : __ballot(!a01) ? SF_A01 : !__ballot(legal) ? SF_NOLEGAL
+                   : __ballot(pneg) ? SF_PNEG : __ballot(pill) ? SF_PILLEGAL : 0;
+  if (code && lane == 0) sample_fault_raise(bad, i, code);
 }
 // pushed sample j (j >= skip: the others would be overwritten within this very call) is staged sample (reverse ? n - 1 - j : j)
 // and lands in slot (total + j) % cap
@@ -162,10 +161,6 @@ __global__ void __launch_bounds__(64 * PM_WAVES) k_pm_heads(PmView v, long long 
   const bool differ = __ballot(diff) != 0ULL;
   if (lane == 0) { head[i] = differ ? 1 : 0; if (differ) *collision = 1; }
 }
-static __global__ void k_pm_gather_u64(const unsigned long long* __restrict__ src, const unsigned int* __restrict__ idx, long long n, unsigned long long* __restrict__ dst) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = src[idx[i]];
-}
 // group s (1-based segid of its head, in key order): its first buffer index -- the sort is stable, so that is its head's -- is the
 // key of the sort that orders the output, its number the value; gpos[s] = where it starts in the key order
 __global__ void k_pm_groups(const int* __restrict__ head, const int* __restrict__ seg, const unsigned int* __restrict__ order, long long n,
@@ -228,15 +223,11 @@ extern "C" int az_plane_memory_create(int32_t game, int32_t device, int64_t capa
   if (capacity < 1 || capacity > (1LL << 31) - 1) return fail(AZ_ERR_BAD_ARG, "capacity must be in 1..2^31-1");
   if (gi.A + 2 > 128) return fail(AZ_ERR_BAD_ARG, "game id %d has more than 126 actions", game);   // k_pm_merge: two doubles per lane
   if (gi.C * gi.P + gi.A > 65535) return fail(AZ_ERR_BAD_ARG, "game id %d has rows of more than 65535 words", game);   // d_perm: 16-bit entries
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(AZ_ERR_BAD_ARG, "device %d not available (%d visible)", device, ndev);
-  HIPCHK(hipSetDevice(device));
+  AZCHK(use_device(device));
   az_plane_memory* m = new (std::nothrow) az_plane_memory();
   if (!m) return fail(AZ_ERR_HIP, "out of host memory");
-  m->game = game; m->device = device; m->gi = gi; m->stream = nullptr; m->d_XA = nullptr; m->d_D = nullptr; m->d_n = nullptr;
+  m->game = game; m->device = device; m->gi = gi; m->cap = capacity;
   m->xs = gi.C * gi.P; m->nA = gi.A; m->RW = m->xs + m->nA; m->ND = m->nA + 2;
-  m->cap = capacity; m->total = 0; m->cur_batch = 0; m->hash_bits = 128; m->nsym = 0; m->d_perm = nullptr;
   int st = [&]() -> int {
     HIPCHK(hipStreamCreate(&m->stream));
     AZCHK(mem_alloc(nullptr, &m->d_XA, (size_t)capacity * m->RW));
@@ -316,38 +307,29 @@ static int plane_push(az_plane_memory* m, int64_t n, const float* X, const float
                       const int64_t* nvis, bool reverse) {
   const size_t N = (size_t)n, xs = (size_t)m->xs, nA = (size_t)m->nA;
   hipStream_t st = m->stream;
-  std::vector<void*> tmp;
-  int rc = [&]() -> int {
-    float *sX, *sA; double *sP, *sz, *stt; long long* sn = nullptr; unsigned long long* d_bad;
-    AZCHK(mem_alloc(&tmp, &sX, N * xs)); AZCHK(mem_alloc(&tmp, &sA, N * nA)); AZCHK(mem_alloc(&tmp, &sP, N * nA));
-    AZCHK(mem_alloc(&tmp, &sz, N)); AZCHK(mem_alloc(&tmp, &stt, N)); AZCHK(mem_alloc(&tmp, &d_bad, 1));
-    if (nvis) AZCHK(mem_alloc(&tmp, &sn, N));
-    HIPCHK(hipMemcpyAsync(sX, X, sizeof(float) * N * xs, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sA, A, sizeof(float) * N * nA, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sP, P, sizeof(double) * N * nA, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sz, z, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(stt, t, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    if (nvis) HIPCHK(hipMemcpyAsync(sn, nvis, sizeof(long long) * N, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_bad, 0xff, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_pm_check, dim3(pm_grid(n)), dim3(64 * PM_WAVES), 0, st, sX, sA, sP, sz, stt, sn, (long long)n, m->xs, m->nA, d_bad);
-    unsigned long long bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    if (bad != ~0ull) {
-      static const char* const what[] = {"", "a non-finite value", "n < 1", "an entry of A outside {0, 1}", "no legal action (a row of A without a 1)",
-                                         "P < 0", "P > 0 where A == 0 (the loss takes the logarithm of the masked policy there)"};
-      return fail(AZ_ERR_BAD_ARG, "sample %lld: %s", (long long)(bad >> 3), what[bad & 7]);
-    }
-    const long long skip = std::max<long long>(0, n - m->cap);
-    hipLaunchKernelGGL(k_pm_store, dim3(pm_grid(n - skip)), dim3(64 * PM_WAVES), 0, st, sX, sA, sP, sz, stt, sn, (long long)n, skip, reverse ? 1 : 0,
-                       m->xs, m->nA, (long long)m->total, (long long)m->cap, m->d_XA, m->d_D, m->d_n);
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    return AZ_OK;
-  }();
-  for (void* p : tmp) (void)hipFree(p);
-  AZCHK(rc);
+  Scratch tmp;
+  float *sX, *sA; double *sP, *sz, *stt; long long* sn = nullptr; unsigned long long* d_bad;
+  AZCHK(tmp.alloc(&sX, N * xs)); AZCHK(tmp.alloc(&sA, N * nA)); AZCHK(tmp.alloc(&sP, N * nA));
+  AZCHK(tmp.alloc(&sz, N)); AZCHK(tmp.alloc(&stt, N)); AZCHK(tmp.alloc(&d_bad, 1));
+  if (nvis) AZCHK(tmp.alloc(&sn, N));
+  HIPCHK(hipMemcpyAsync(sX, X, sizeof(float) * N * xs, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(sA, A, sizeof(float) * N * nA, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(sP, P, sizeof(double) * N * nA, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(sz, z, sizeof(double) * N, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(stt, t, sizeof(double) * N, hipMemcpyHostToDevice, st));
+  if (nvis) HIPCHK(hipMemcpyAsync(sn, nvis, sizeof(long long) * N, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(d_bad, 0xff, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_pm_check, dim3(pm_grid(n)), dim3(64 * PM_WAVES), 0, st, sX, sA, sP, sz, stt, sn, (long long)n, m->xs, m->nA, d_bad);
+  unsigned long long bad = 0;
+  HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  AZCHK(sample_fault_status(bad, "n < 1"));
+  const long long skip = std::max<long long>(0, n - m->cap);
+  hipLaunchKernelGGL(k_pm_store, dim3(pm_grid(n - skip)), dim3(64 * PM_WAVES), 0, st, sX, sA, sP, sz, stt, sn, (long long)n, skip, reverse ? 1 : 0,
+                     m->xs, m->nA, (long long)m->total, (long long)m->cap, m->d_XA, m->d_D, m->d_n);
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
   m->total += n;
   return AZ_OK;
 }
@@ -418,61 +400,54 @@ static int plane_dataset_build(az_plane_memory* m, az_dataset* d, int which, int
   const bool sym = nsym > 0;
   const PmView view{m->d_XA, (long long)m->cap, seq0, (long long)n0, m->RW, nsym, m->d_perm};
   const int xs = m->xs, nA = m->nA;
-  std::vector<void*> tmp;
-  int rc = [&]() -> int {
-    HIPCHK(hipStreamSynchronize(m->stream));
-    HIPCHK(hipStreamCreate(&d->stream));
-    hipStream_t st = d->stream;
-    unsigned int *order = nullptr, *gord = nullptr, *gpos = nullptr;
-    int64_t n2 = n1;
-    if (merge) {
-      unsigned long long *k0, *k1, *k1keep, *ks, *ks2, *gkey, *gks; unsigned int *i0, *i1, *i2, *gval; int *head, *seg, *stmp, *coll;
-      const size_t N = (size_t)n1;
-      AZCHK(mem_alloc(&tmp, &k0, N)); AZCHK(mem_alloc(&tmp, &k1, N)); AZCHK(mem_alloc(&tmp, &k1keep, N)); AZCHK(mem_alloc(&tmp, &ks, N)); AZCHK(mem_alloc(&tmp, &ks2, N));
-      AZCHK(mem_alloc(&tmp, &i0, N)); AZCHK(mem_alloc(&tmp, &i1, N)); AZCHK(mem_alloc(&tmp, &i2, N));
-      AZCHK(mem_alloc(&tmp, &head, N)); AZCHK(mem_alloc(&tmp, &seg, N)); AZCHK(mem_alloc(&tmp, &coll, 1));
-      AZCHK(mem_alloc(&tmp, &stmp, std::max(prims::sort_tmp_ints(n1), prims::scan_tmp_ints(n1))));
-      const unsigned gb = (unsigned)((n1 + 255) / 256);
-      HIPCHK(hipMemsetAsync(coll, 0, sizeof(int), st));
-      hipLaunchKernelGGL(sym ? k_pm_hash<true> : k_pm_hash<false>, dim3(pm_grid(n1)), dim3(64 * PM_WAVES), 0, st, view, (long long)n1, m->hash_bits, k0, k1, k1keep, i0);
-      // LSD as dataset_build (memory.hip): stable by k1, then by k0 -> ascending (k0, k1, buffer index)
-      HIPCHK(prims::sort_pairs(k1, ks, i0, i1, n1, stmp, st));
-      hipLaunchKernelGGL(k_pm_gather_u64, dim3(gb), dim3(256), 0, st, k0, i1, (long long)n1, ks2);
-      HIPCHK(prims::sort_pairs(ks2, ks, i1, i2, n1, stmp, st));
-      hipLaunchKernelGGL(sym ? k_pm_heads<true> : k_pm_heads<false>, dim3(pm_grid(n1)), dim3(64 * PM_WAVES), 0, st, view, (long long)n1, k0, k1keep, i2, head, coll);
-      HIPCHK(prims::scan_ints(head, seg, n1, true, stmp, st));
-      int nseg = 0, collision = 0;
-      HIPCHK(hipMemcpyAsync(&nseg, seg + (n1 - 1), sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(&collision, coll, sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      HIPCHK(hipGetLastError());
-      if (collision) return fail(AZ_ERR_STATE, "plane hash collision: two different (X, A) rows share their %d-bit key; no data set was built", m->hash_bits);
-      n2 = nseg;
-      const size_t G = (size_t)n2;
-      AZCHK(mem_alloc(&tmp, &gkey, G)); AZCHK(mem_alloc(&tmp, &gks, G)); AZCHK(mem_alloc(&tmp, &gval, G)); AZCHK(mem_alloc(&tmp, &gord, G)); AZCHK(mem_alloc(&tmp, &gpos, G));
-      hipLaunchKernelGGL(k_pm_groups, dim3(gb), dim3(256), 0, st, head, seg, i2, (long long)n1, gkey, gval, gpos);
-      HIPCHK(prims::sort_pairs(gkey, gks, gval, gord, n2, stmp, st));   // n2 <= n1: stmp is large enough
-      order = i2;
-    }
-    d->n = n2;
-    const size_t G = (size_t)n2;
-    AZCHK(mem_alloc(&d->allocs, &d->d_W, G)); AZCHK(mem_alloc(&d->allocs, &d->d_V, G));
-    AZCHK(mem_alloc(&d->allocs, &d->d_A, G * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_P, G * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_X, G * xs));
-    long long *tn, *tsum;
-    AZCHK(mem_alloc(&tmp, &tn, G)); AZCHK(mem_alloc(&tmp, &tsum, prims::sum_tmp_doubles(n2)));
-    hipLaunchKernelGGL(sym ? k_pm_merge<true> : k_pm_merge<false>, dim3(pm_grid(n2)), dim3(64 * PM_WAVES), 0, st, view, m->d_D, m->d_n, (long long)n1, (long long)n2,
-                       xs, nA, policy, order, gord, gpos, d->d_W, d->d_X, d->d_A, d->d_P, d->d_V, tn);
-    long long* d_sn = nullptr; long long sn = 0;
-    HIPCHK(prims::sum_values<long long>(tn, n2, tsum, &d_sn, st));    // sum(e.n) is an Int: exact
-    HIPCHK(hipMemcpyAsync(&sn, d_sn, sizeof sn, hipMemcpyDeviceToHost, st));
+  Scratch tmp;
+  HIPCHK(hipStreamSynchronize(m->stream));
+  HIPCHK(hipStreamCreate(&d->stream));
+  hipStream_t st = d->stream;
+  unsigned int *order = nullptr, *gord = nullptr, *gpos = nullptr;
+  int64_t n2 = n1;
+  if (merge) {
+    unsigned long long *k0, *k1, *k1keep, *ks, *ks2, *gkey, *gks; unsigned int *i0, *i1, *i2, *gval; int *head, *seg, *stmp, *coll;
+    const size_t N = (size_t)n1;
+    AZCHK(tmp.alloc(&k0, N)); AZCHK(tmp.alloc(&k1, N)); AZCHK(tmp.alloc(&k1keep, N)); AZCHK(tmp.alloc(&ks, N)); AZCHK(tmp.alloc(&ks2, N));
+    AZCHK(tmp.alloc(&i0, N)); AZCHK(tmp.alloc(&i1, N)); AZCHK(tmp.alloc(&i2, N));
+    AZCHK(tmp.alloc(&head, N)); AZCHK(tmp.alloc(&seg, N)); AZCHK(tmp.alloc(&coll, 1));
+    AZCHK(tmp.alloc(&stmp, std::max(prims::sort_tmp_ints(n1), prims::scan_tmp_ints(n1))));
+    const unsigned gb = (unsigned)((n1 + 255) / 256);
+    HIPCHK(hipMemsetAsync(coll, 0, sizeof(int), st));
+    hipLaunchKernelGGL(sym ? k_pm_hash<true> : k_pm_hash<false>, dim3(pm_grid(n1)), dim3(64 * PM_WAVES), 0, st, view, (long long)n1, m->hash_bits, k0, k1, k1keep, i0);
+    HIPCHK(prims::order_by_key(k0, k1, i0, ks, ks2, i1, i2, n1, stmp, st));   // i2: ascending (k0, k1, buffer index), as dataset_build (memory.hip)
+    hipLaunchKernelGGL(sym ? k_pm_heads<true> : k_pm_heads<false>, dim3(pm_grid(n1)), dim3(64 * PM_WAVES), 0, st, view, (long long)n1, k0, k1keep, i2, head, coll);
+    HIPCHK(prims::scan_ints(head, seg, n1, true, stmp, st));
+    int nseg = 0, collision = 0;
+    HIPCHK(hipMemcpyAsync(&nseg, seg + (n1 - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&collision, coll, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
-    d->sum_n = (int64_t)sn;
-    AZCHK(dataset_tensor_stats(d, st));                              // Wtot, Wmean, Hp as az_dataset_create_from_tensors computes them
-    return AZ_OK;
-  }();
-  for (void* p : tmp) (void)hipFree(p);
-  return rc;
+    if (collision) return fail(AZ_ERR_STATE, "plane hash collision: two different (X, A) rows share their %d-bit key; no data set was built", m->hash_bits);
+    n2 = nseg;
+    const size_t G = (size_t)n2;
+    AZCHK(tmp.alloc(&gkey, G)); AZCHK(tmp.alloc(&gks, G)); AZCHK(tmp.alloc(&gval, G)); AZCHK(tmp.alloc(&gord, G)); AZCHK(tmp.alloc(&gpos, G));
+    hipLaunchKernelGGL(k_pm_groups, dim3(gb), dim3(256), 0, st, head, seg, i2, (long long)n1, gkey, gval, gpos);
+    HIPCHK(prims::sort_pairs(gkey, gks, gval, gord, n2, stmp, st));   // n2 <= n1: stmp is large enough
+    order = i2;
+  }
+  d->n = n2;
+  const size_t G = (size_t)n2;
+  AZCHK(mem_alloc(&d->allocs, &d->d_W, G)); AZCHK(mem_alloc(&d->allocs, &d->d_V, G));
+  AZCHK(mem_alloc(&d->allocs, &d->d_A, G * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_P, G * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_X, G * xs));
+  long long *tn, *tsum;
+  AZCHK(tmp.alloc(&tn, G)); AZCHK(tmp.alloc(&tsum, prims::sum_tmp_doubles(n2)));
+  hipLaunchKernelGGL(sym ? k_pm_merge<true> : k_pm_merge<false>, dim3(pm_grid(n2)), dim3(64 * PM_WAVES), 0, st, view, m->d_D, m->d_n, (long long)n1, (long long)n2,
+                     xs, nA, policy, order, gord, gpos, d->d_W, d->d_X, d->d_A, d->d_P, d->d_V, tn);
+  long long* d_sn = nullptr; long long sn = 0;
+  HIPCHK(prims::sum_values<long long>(tn, n2, tsum, &d_sn, st));    // sum(e.n) is an Int: exact
+  HIPCHK(hipMemcpyAsync(&sn, d_sn, sizeof sn, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  d->sum_n = (int64_t)sn;
+  AZCHK(dataset_tensor_stats(d, st));                              // Wtot, Wmean, Hp as az_dataset_create_from_tensors computes them
+  return AZ_OK;
 }
 extern "C" int az_dataset_create_from_plane_memory_sym(az_plane_memory* m, int32_t which, int32_t use_symmetries, int32_t use_position_averaging,
                                                        int32_t weighing_policy, az_dataset** out) {
@@ -482,11 +457,8 @@ extern "C" int az_dataset_create_from_plane_memory_sym(az_plane_memory* m, int32
   if (which != 0 && which != 1) return fail(AZ_ERR_BAD_ARG, "which must be 0 (get_experience) or 1 (last_batch)");
   if (weighing_policy < AZ_WEIGHT_CONSTANT || weighing_policy > AZ_WEIGHT_LINEAR) return fail(AZ_ERR_BAD_ARG, "unknown samples_weighing_policy %d", weighing_policy);
   if (use_symmetries && m->nsym == 0) return fail(AZ_ERR_BAD_ARG, "use_symmetries: no symmetries were declared for this memory (game.jl:332; az_plane_memory_set_symmetries)");
-  az_dataset* d = new (std::nothrow) az_dataset();
-  if (!d) return fail(AZ_ERR_HIP, "out of host memory");
-  d->game = m->game; d->device = m->device; d->gi = m->gi; d->stream = nullptr; d->own_stream = true; d->n = 0; d->sum_n = 0;
-  d->Wtot = 0.0; d->Wmean = 0.f; d->Hp = 0.f; d->d_samples = nullptr; d->d_envs = nullptr;
-  d->d_W = d->d_X = d->d_A = d->d_P = d->d_V = nullptr;
+  az_dataset* d = nullptr;
+  AZCHK(dataset_new(m->game, m->device, m->gi, nullptr, &d));
   const int st = plane_dataset_build(m, d, which, use_symmetries ? m->nsym : 0, use_position_averaging != 0, weighing_policy);
   if (st != AZ_OK) { az_dataset_destroy(d); return st; }
   *out = d;

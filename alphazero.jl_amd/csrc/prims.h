@@ -1,6 +1,7 @@
 // prims.h -- the three device-wide primitives memory.hip needs (merge_by_state, src/memory.jl:89-114, and the data-set sums of
 // src/learning.jl:110-111), hand-written for gfx950: a stable LSD radix sort of (u64 key, u32 value) pairs, an inclusive
-// scan of ints and a deterministic sum of doubles (the same tiles sum 64-bit integers exactly).  Round 2 took them from hipCUB, the last third-party device code in the
+// scan of ints and a deterministic sum of doubles (the same tiles sum 64-bit integers exactly); order_by_key is the two sorts of a
+// by-state grouping, shared with plane_memory.hip.  Round 2 took them from hipCUB, the last third-party device code in the
 // library.  Off the hot path (a data set is built once per learning step), so the design goal is small and obviously
 // stable / deterministic rather than fastest: 8-bit digits, one workgroup per tile of 2048 pairs, and a per-tile local
 // split so that equal digits keep their order.
@@ -166,6 +167,22 @@ inline hipError_t sort_pairs(unsigned long long* keys_in, unsigned long long* ke
   e = hipMemcpyAsync(vals_out, vals_in, sizeof(unsigned int) * (size_t)n, hipMemcpyDeviceToDevice, st);
   if (e != hipSuccess) return e;
   return hipGetLastError();
+}
+
+// ---- grouping by a 128-bit key: the order of merge_by_state, for the state keys of memory.hip and the row hashes of plane_memory.hip ----
+static __global__ void k_gather_u64(const unsigned long long* __restrict__ src, const unsigned int* __restrict__ idx, long long n, unsigned long long* __restrict__ dst) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = src[idx[i]];
+}
+// order[0 .. n) = the indices 0 .. n-1 ascending by (k0, k1, index): LSD over the halves -- a stable sort by k1, then one by k0 of the
+// keys gathered into that order -- so equal keys keep buffer order.  idx holds the identity 0 .. n-1.  k0 is only read; k1 and idx are
+// the first sort's ping-pong partner (destroyed).  ks, ks2 [n] keys and i1 [n] indices are scratch, tmp: sort_tmp_ints(n) ints.
+inline hipError_t order_by_key(const unsigned long long* k0, unsigned long long* k1, unsigned int* idx, unsigned long long* ks, unsigned long long* ks2,
+                               unsigned int* i1, unsigned int* order, long long n, int* tmp, hipStream_t st) {
+  hipError_t e = sort_pairs(k1, ks, idx, i1, n, tmp, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_gather_u64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, k0, i1, n, ks2);
+  return sort_pairs(ks2, ks, i1, order, n, tmp, st);
 }
 
 // ---- deterministic sum of n doubles (or 64-bit integers): fixed tiles of 2048 summed by a fixed tree, tile sums summed by one workgroup in order ----

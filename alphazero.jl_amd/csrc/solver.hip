@@ -62,10 +62,7 @@ extern "C" int az_solver_table_create(int32_t device, int32_t log2_entries, az_s
   if (!out) return fail(AZ_ERR_BAD_ARG, "out is NULL");
   *out = nullptr;
   if (log2_entries < 0 || log2_entries > 30) return fail(AZ_ERR_BAD_ARG, "solver table log2_entries = %d outside 0..30", (int)log2_entries);
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(AZ_ERR_BAD_ARG, "device %d outside 0..%d", (int)device, ndev - 1);
-  HIPCHK(hipSetDevice(device));
+  AZCHK(use_device(device));
   az_solver_table* t = new (std::nothrow) az_solver_table();
   if (!t) return fail(AZ_ERR_HIP, "out of host memory");
   t->device = device; t->log2 = log2_entries;

@@ -394,36 +394,36 @@ struct TrConv {                 // one convolution + batch norm (3x3 of the towe
   float *col, *g, *a;           // im2col input [R][taps*cin] (taps == 1: alias of the input), GEMM output, activation
   float *mean, *invstd;
 };
-struct az_trainer {
-  az_engine* e;
-  az_dataset* d;
-  az_train_cfg cfg;
-  int game, device; GameInfo gi;
-  hipStream_t stream;
+struct az_trainer {               // every member starts here: az_trainer_destroy takes a half-built record apart
+  az_engine* e = nullptr;
+  az_dataset* d = nullptr;
+  az_train_cfg cfg = {};
+  int game = 0, device = 0; GameInfo gi = {};
+  hipStream_t stream = nullptr;
   EnvTrainer env;                                                            // the AZHIP_TRAIN_* overrides, read when az_trainer_create constructs this record (env.h)
-  hipStream_t side;                                                          // the weight gradients of the tower run here, beside the batch-norm backward passes of the next layer
+  hipStream_t side = nullptr;                                                // the weight gradients of the tower run here, beside the batch-norm backward passes of the next layer
   std::vector<hipEvent_t> ev_dg, ev_wg;                                     // per tower layer: output gradient ready / weight gradient done
-  float* gemm_ws; size_t gemm_ws_floats;                                     // split-reduction workspace of gemm_f32
-  int B, nblocks, F, npf, nvf, nA;
-  long long R;
-  size_t nparams;
+  float* gemm_ws = nullptr; size_t gemm_ws_floats = 0;                       // split-reduction workspace of gemm_f32
+  int B = 0, nblocks = 0, F = 0, npf = 0, nvf = 0, nA = 0;
+  long long R = 0;
+  size_t nparams = 0;
   std::vector<TrConv> convs;    // stem, block convs..., then policy-head conv, value-head conv
-  size_t off_pd_b, off_v1_b, off_v2_b;                                     // dense-layer biases in the blob
-  size_t wk_pd, wk_v1, wk_v2, nwork;
-  float *blob, *gblob, *opt_m, *opt_v; unsigned char* trainable;           // [nparams]
-  int* scat; long long nscat;                                                // working entries that carry a gradient (the primary ranges)
-  float *work, *gwork; int* map;                                             // working parameters and their blob map
+  size_t off_pd_b = 0, off_v1_b = 0, off_v2_b = 0;                         // dense-layer biases in the blob
+  size_t wk_pd = 0, wk_v1 = 0, wk_v2 = 0, nwork = 0;
+  float *blob = nullptr, *gblob = nullptr, *opt_m = nullptr, *opt_v = nullptr; unsigned char* trainable = nullptr;   // [nparams]
+  int* scat = nullptr; long long nscat = 0;                                  // working entries that carry a gradient (the primary ranges)
+  float *work = nullptr, *gwork = nullptr; int* map = nullptr;               // working parameters and their blob map
   // batch + head buffers
-  int* d_idx; float *bW, *bX, *bA, *bP, *bV;
-  float *logits, *v1, *tpre, *dlogits, *dt, *dv1;
-  float *dact, *dact2, *dact3, *dcol;                                        // [R][F] gradients (dcol / dact / dact3 take turns as the running gradient, dact2 = the skip share)
-  float* wg_part; int wg_splits, wg_bpw;                       // k_wgrad16: partial dW per row split, boards per workgroup
-  double *part, *sums, *terms, *bsums;
-  float* bn_mf;                                                              // [2][C] the batch-norm backward means of the layer in flight
-  int* fin_counter;                                                          // tr_finish: counter of the workgroups that have left their partial sums
+  int* d_idx = nullptr; float *bW = nullptr, *bX = nullptr, *bA = nullptr, *bP = nullptr, *bV = nullptr;
+  float *logits = nullptr, *v1 = nullptr, *tpre = nullptr, *dlogits = nullptr, *dt = nullptr, *dv1 = nullptr;
+  float *dact = nullptr, *dact2 = nullptr, *dact3 = nullptr, *dcol = nullptr;   // [R][F] gradients (dcol / dact / dact3 take turns as the running gradient, dact2 = the skip share)
+  float* wg_part = nullptr; int wg_splits = 0, wg_bpw = 0;       // k_wgrad16: partial dW per row split, boards per workgroup
+  double *part = nullptr, *sums = nullptr, *terms = nullptr, *bsums = nullptr;
+  float* bn_mf = nullptr;                                                    // [2][C] the batch-norm backward means of the layer in flight
+  int* fin_counter = nullptr;                                                // tr_finish: counter of the workgroups that have left their partial sums
   std::vector<void*> allocs;
-  std::vector<int> perm; int64_t perm_pos, epoch; int64_t step;
-  float b1t, b2t;
+  std::vector<int> perm; int64_t perm_pos = 0, epoch = 0; int64_t step = 0;
+  float b1t = 1.0f, b2t = 1.0f;
 };
 
 template <class T> static int tr_alloc(az_trainer* t, T** p, size_t n, bool zero = false) {
@@ -793,10 +793,9 @@ extern "C" int az_trainer_create(az_engine* e, az_dataset* d, const az_train_cfg
   if (!(cfg->rewards_renormalization > 0.0)) return fail(AZ_ERR_BAD_ARG, "rewards_renormalization must be > 0");
   az_trainer* t = new (std::nothrow) az_trainer();
   if (!t) return fail(AZ_ERR_HIP, "out of host memory");
-  t->e = e; t->d = d; t->cfg = *cfg; t->game = e->cfg.game; t->device = e->device; t->gi = e->gi; t->stream = nullptr; t->side = nullptr; t->gemm_ws = nullptr; t->gemm_ws_floats = 0;
+  t->e = e; t->d = d; t->cfg = *cfg; t->game = e->cfg.game; t->device = e->device; t->gi = e->gi;
   t->B = (int)B; t->nblocks = e->cfg.num_blocks; t->F = e->cfg.num_filters; t->npf = e->cfg.num_policy_head_filters; t->nvf = e->cfg.num_value_head_filters;
   t->nA = e->gi.A; t->R = (long long)B * e->gi.P; t->nparams = e->blob.size();
-  t->perm_pos = 0; t->epoch = 0; t->step = 0; t->b1t = 1.0f; t->b2t = 1.0f;
   int st = [&]() -> int {
     // the chain of the step on a high-priority stream, the weight gradients beside it on a low-priority one
     int pr_least = 0, pr_greatest = 0;
@@ -858,15 +857,11 @@ extern "C" int az_debug_trainer_activation(az_trainer* t, int32_t which, float* 
 // the trainer's own launch helpers on t->stream -- so the geometry table, wg_splits, the partial buffers, the fragment maps and the
 // GEMM workspace with its split rule are the ones a step uses.  tests/test_train_kernels_gpu.py feeds them small integers, whose
 // fp32 sums are exact in any order, and compares bit for bit at the batches where the kernels' inner loops iterate.
-struct TrTemp {                                                      // device memory of one call
-  std::vector<void*> allocs;
-  ~TrTemp() { for (void* p : allocs) (void)hipFree(p); }
-  int up(float** p, const float* host, size_t n) {
-    AZCHK(mem_alloc(&allocs, p, n));
-    if (host) HIPCHK(hipMemcpy(*p, host, sizeof(float) * n, hipMemcpyHostToDevice));
-    return AZ_OK;
-  }
-};
+static int tr_up(Scratch& tmp, float** p, const float* host, size_t n) {   // a host array as scratch of the call
+  AZCHK(tmp.alloc(p, n));
+  if (host) HIPCHK(hipMemcpy(*p, host, sizeof(float) * n, hipMemcpyHostToDevice));
+  return AZ_OK;
+}
 #define TR_TOWER(t) if ((t)->nblocks < 1) return fail(AZ_ERR_BAD_ARG, "the trainer's tower has no F -> F convolution (num_blocks = 0)")
 // weight gradient of a 3x3 F -> F convolution (tr_wgrad16 = k_wgrad16 + k_wgrad_reduce): a, dg = [B P][F] with row = board P + y W + x;
 // out[9][F][F] = [tap][ci][co], tap = 3 (dy + 1) + (dx + 1): sum over the rows whose neighbour (y + dy, x + dx) is on the board of a[neighbour][ci] dg[row][co]
@@ -911,12 +906,12 @@ extern "C" int az_debug_trainer_conv(az_trainer* t, int32_t layer, int32_t dgrad
   const float* second = dgrad ? addend : res;
   if (second) HIPCHK(hipMemcpy(t->dact2, second, bytes, hipMemcpyHostToDevice));
   int np = 0;
-  TrTemp tmp;                                                       // lives until the stream has been waited for
+  Scratch tmp;                                                      // lives until the stream has been waited for
   if (dgrad) {
     AZCHK(tr_conv16(t, t->dact, t->work + c.wk_fdg, t->dact3, false, &np, second ? t->dact2 : nullptr));
   } else {
     float* dbn = nullptr;
-    AZCHK(tmp.up(&dbn, bn, 4 * (size_t)F));
+    AZCHK(tr_up(tmp, &dbn, bn, 4 * (size_t)F));
     TrFinal fin{};                                                  // mode 0: the sums only; no counter: the second stage is the separate launch
     AZCHK(tr_conv16(t, nullptr, t->work + c.wk_ffwd, t->dact3, true, &np, nullptr, BnIn{t->dact, dbn, dbn + F, dbn + 2 * F, dbn + 3 * F, second ? t->dact2 : nullptr, t->dcol}, fin));
     hipLaunchKernelGGL(k_tr_colsum_final, dim3(F), dim3(64), 0, t->stream, t->part, np, F, t->sums, fin);
@@ -941,9 +936,9 @@ extern "C" int az_debug_trainer_gemm(az_trainer* t, int32_t ta, int32_t tb, int3
   if (!A || lda < ca || na != (int64_t)ra * lda) return fail(AZ_ERR_BAD_ARG, "A must hold %d rows of lda >= %d floats", ra, ca);
   if (!B || ldb < cb || nb != (int64_t)rb * ldb) return fail(AZ_ERR_BAD_ARG, "B must hold %d rows of ldb >= %d floats", rb, cb);
   if (!Cm || ldc < N || nc != (int64_t)M * ldc) return fail(AZ_ERR_BAD_ARG, "C must hold %d rows of ldc >= %d floats", M, N);
-  TrTemp tmp;
+  Scratch tmp;
   float *dA = nullptr, *dB = nullptr, *dC = nullptr;
-  AZCHK(tmp.up(&dA, A, (size_t)na)); AZCHK(tmp.up(&dB, B, (size_t)nb)); AZCHK(tmp.up(&dC, Cm, (size_t)nc));
+  AZCHK(tr_up(tmp, &dA, A, (size_t)na)); AZCHK(tr_up(tmp, &dB, B, (size_t)nb)); AZCHK(tr_up(tmp, &dC, Cm, (size_t)nc));
   HIPCHK(hipStreamSynchronize(t->stream));
   AZCHK(tr_gemm(t, ta != 0, tb != 0, M, N, K, alpha, dA, lda, dB, ldb, beta, dC, ldc));
   HIPCHK(hipStreamSynchronize(t->stream));

@@ -295,6 +295,41 @@ def test_map_structure(dumped):
     assert np.array_equal(np.flatnonzero(maps["trainable"] == 0), frozen) and set(np.unique(maps["trainable"])) == {0, 1}
 
 
+def old_regularisation_walk(C, P, A, nb, F, npf, nvf):
+    """The blob indices az_learning_status's regularisation sum visited while csrc/memory.hip still walked the blob by hand, restated from
+    that walk: `take` n values, `skip` n values -- per convolution its weight, bias, gamma and beta taken, running mean and variance
+    skipped; the dense layers taken whole.  Returns (the indices in the order visited, where the walk ended)."""
+    at, seen = 0, []
+
+    def take(n):
+        nonlocal at
+        seen.append(np.arange(at, at + n))
+        at += n
+
+    def skip(n):
+        nonlocal at
+        at += n
+
+    take(9 * C * F); take(F); take(2 * F); skip(2 * F)
+    for _ in range(2 * nb):
+        take(9 * F * F); take(F); take(2 * F); skip(2 * F)
+    take(F * npf); take(npf); take(2 * npf); skip(2 * npf); take(A * P * npf); take(A)
+    take(F * nvf); take(nvf); take(2 * nvf); skip(2 * nvf); take(F * P * nvf); take(F); take(F); take(1)
+    return np.concatenate(seen), at
+
+
+@pytest.mark.parametrize("game,nb,F", [(L.GAME_TICTACTOE, 1, 64), (L.GAME_CONNECT_FOUR, 5, 64), (L.GAME_MANCALA, 5, 128), (L.GAME_GO9_PLANES, 10, 128)],
+                         ids=["ttt-1x64", "c4-5x64", "mancala-5x128", "go9-10x128"])
+def test_trainable_mask_marks_what_the_regularisation_walk_visited(driver, game, nb, F):
+    """reg_sum_trainable sums blob[i]^2 over trainable_mask in ascending i; the hand walk it replaced visited exactly those i, ascending"""
+    C_, P, A, _ = GEOM[game]
+    table, maps, _, _ = driver((game, nb, F, (32, 32)))
+    visited, end = old_regularisation_walk(C_, P, A, nb, F, 32, 32)
+    assert end == dict(table)["total"] == maps["trainable"].size
+    assert np.all(np.diff(visited) > 0)                                 # one accumulator in ascending blob order, then as now
+    assert np.array_equal(np.flatnonzero(maps["trainable"]), visited)
+
+
 @pytest.mark.parametrize("mut,arrays", [("swap_wi_wj", ("conv_w", "c16_w", "c16b_w", "stem_w", "s16_w", "train_map")),
                                         ("no_tap_mirror", ("train_map",)),
                                         ("npf_for_nvf", ("head_b", "head_bn", "val_w", "val_b", "val2_w", "train_map", "trainable"))])
