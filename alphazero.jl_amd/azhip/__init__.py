@@ -6,12 +6,12 @@ include/azhip.h (libazhip.so, hand-written HIP for gfx950).  There is no CPU fal
 """
 from . import _lib
 from ._lib import (AzError, GAME_CONNECT_FOUR, GAME_GO9_PLANES, GAME_MANCALA, GAME_TICTACTOE, ORACLE_HASH, ORACLE_RESNET,
-                   ORACLE_ROLLOUT, ORACLE_UNIFORM)
+                   ORACLE_ROLLOUT, ORACLE_SIMPLENET, ORACLE_UNIFORM)
 from .engine import Engine, cached_engine, clear_engine_cache, default_cfg
 from .comm import Comm
 from .params import ArenaParams, ConstSchedule, MctsParams, PLSchedule, SimParams
 from .game import ConnectFourSpec, GameEnv, GameSpec, Go9PlanesSpec, MancalaSpec, TicTacToeSpec, plane_symmetries
-from .network import ResNet, ResNetHP
+from .network import ResNet, ResNetHP, SimpleNet, SimpleNetHP
 from . import mcts as MCTS
 from . import minmax as MinMax
 from . import solver as Solver

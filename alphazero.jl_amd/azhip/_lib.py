@@ -15,7 +15,8 @@ REPLACEMENT_GAME_BIT = 0x40000000
 AZ_OK, AZ_ERR_BAD_ARG, AZ_ERR_CAPACITY, AZ_ERR_HIP, AZ_ERR_STATE = 0, -1, -2, -3, -4
 GAME_CONNECT_FOUR, GAME_TICTACTOE, GAME_MANCALA = 0, 1, 2
 GAME_GO9_PLANES = 3          # network-only geometry (9, 9, 4), 82 actions: az_net_forward and the trainer (on tensors) for host-stepped 9x9 Go
-ORACLE_UNIFORM, ORACLE_HASH, ORACLE_RESNET, ORACLE_ROLLOUT = 0, 1, 2, 3
+ORACLE_UNIFORM, ORACLE_HASH, ORACLE_RESNET, ORACLE_ROLLOUT, ORACLE_SIMPLENET = 0, 1, 2, 3, 4
+NET_ORACLES = (ORACLE_RESNET, ORACLE_SIMPLENET)   # the engine's oracle is its network (csrc/engine.h oracle_is_net)
 MAX_ACTIONS = 9
 SCHED_MAX = 8
 PROF_NUM = 8
@@ -139,6 +140,12 @@ class HostTreeStats(C.Structure):
                                          "max_nodes", "max_edge_slots", "max_path", "steps")]
 
 
+class SimpleNetHPRec(C.Structure):
+    """az_simplenet_hp = SimpleNetHP (simplenet.jl:15-22) without the batch-norm momentum, which is az_train_cfg's"""
+    _fields_ = [("struct_size", C.c_int32), ("width", C.c_int32), ("depth_common", C.c_int32), ("depth_phead", C.c_int32),
+                ("depth_vhead", C.c_int32), ("use_batch_norm", C.c_int32)]
+
+
 PROGRESS_CB = C.CFUNCTYPE(None, C.c_void_p)
 
 # every symbol include/azhip.h declares: name -> argtypes (restype is int unless noted)
@@ -158,6 +165,8 @@ SYMBOLS = {
     "az_abi_struct_size": [_I32],
     "az_engine_cfg_init": [C.POINTER(EngineCfg)],
     "az_engine_create": [C.POINTER(EngineCfg), C.POINTER(_VP)],
+    "az_simplenet_hp_init": [C.POINTER(SimpleNetHPRec)],
+    "az_engine_create_simplenet": [C.POINTER(EngineCfg), C.POINTER(SimpleNetHPRec), C.POINTER(_VP)],
     "az_engine_destroy": [_VP],
     "az_game_num_actions": [C.c_int, C.POINTER(_I32)],
     "az_game_state_dim": [C.c_int, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)],
@@ -257,7 +266,8 @@ SYMBOLS = {
 STRUCTS = [("az_engine_cfg", EngineCfg), ("az_move_rec", MoveRec), ("az_game_rec", GameRec), ("az_trace_buf", TraceBuf),
            ("az_selfplay_stats", SelfplayStats), ("az_sample", Sample), ("az_dataset_info", DatasetInfo),
            ("az_learning_status_t", LearningStatusRec), ("az_train_cfg", TrainCfg), ("az_gather_stats", GatherStats), ("az_prof", Prof),
-           ("az_minmax_cfg", MinMaxCfg), ("az_solver_cfg", SolverCfg), ("az_host_tree_cfg", HostTreeCfg), ("az_host_tree_stats", HostTreeStats)]
+           ("az_minmax_cfg", MinMaxCfg), ("az_solver_cfg", SolverCfg), ("az_host_tree_cfg", HostTreeCfg), ("az_host_tree_stats", HostTreeStats),
+           ("az_simplenet_hp", SimpleNetHPRec)]
 _lib = None
 
 

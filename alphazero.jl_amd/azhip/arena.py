@@ -57,11 +57,11 @@ def _engine(gspec, player, sim, device, seed, role):
         raise TypeError("the device arena pits MctsPlayers, NetworkPlayers and MinMax players (Human players stay on the host)")
     kind = oracle_kind(oracle)
     kw = engine_options(params, sim, seed=seed, arena=True)
-    if kind == L.ORACLE_RESNET:
+    if kind in L.NET_ORACLES:
         kw.update(oracle.engine_options())
     e = cached_engine(role, game=gspec.game_id, oracle=kind, device=device, **kw)   # kept across checkpoints (engine.py)
     e.set_minmax(None)
-    if kind == L.ORACLE_RESNET:
+    if kind in L.NET_ORACLES:
         e.net_set_params(oracle.params())
     return e
 

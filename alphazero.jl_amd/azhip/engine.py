@@ -32,11 +32,28 @@ def default_cfg(**kw):
     return cfg
 
 
+def simplenet_rec(hp):
+    """az_simplenet_hp of a network.SimpleNetHP (or anything with its fields)"""
+    rec = L.SimpleNetHPRec()
+    check(lib().az_simplenet_hp_init(C.byref(rec)))
+    rec.width, rec.depth_common, rec.depth_phead, rec.depth_vhead = int(hp.width), int(hp.depth_common), int(hp.depth_phead), int(hp.depth_vhead)
+    rec.use_batch_norm = 1 if hp.use_batch_norm else 0
+    return rec
+
+
 class Engine:
-    def __init__(self, cfg=None, **kw):
+    def __init__(self, cfg=None, simplenet=None, **kw):
+        """simplenet: a network.SimpleNetHP -- the engine's oracle is that dense network (az_engine_create_simplenet)"""
         self.cfg = cfg if cfg is not None else default_cfg(**kw)
         h = C.c_void_p()
-        check(lib().az_engine_create(C.byref(self.cfg), C.byref(h)))
+        if simplenet is not None:
+            self.cfg = EngineCfg.from_buffer_copy(self.cfg)           # the caller's record stays as it was: the oracle kind is set below
+            self.simplenet = simplenet
+            rec = simplenet if isinstance(simplenet, L.SimpleNetHPRec) else simplenet_rec(simplenet)
+            check(lib().az_engine_create_simplenet(C.byref(self.cfg), C.byref(rec), C.byref(h)))
+            self.cfg.oracle = L.ORACLE_SIMPLENET
+        else:
+            check(lib().az_engine_create(C.byref(self.cfg), C.byref(h)))
         self._h = h
         n = C.c_int32()
         check(lib().az_game_num_actions(self.cfg.game, C.byref(n)))
@@ -341,15 +358,22 @@ def _evict():
     _cache.pop(k).close()
 
 
-def cached_engine(role="", **kw):
+def cached_engine(role="", simplenet=None, **kw):
     import ctypes
     cfg = default_cfg(**kw)
-    key = (role, bytes(ctypes.string_at(ctypes.addressof(cfg), ctypes.sizeof(cfg))), tuple(os.environ.get(k, "") for k in CREATE_ENV))
+    rec = simplenet_rec(simplenet) if simplenet is not None else None
+    if rec is not None:                                             # what az_engine_create_simplenet ignores or sets is no part of the key
+        blank = default_cfg()
+        cfg.oracle = L.ORACLE_SIMPLENET
+        for f in ("num_blocks", "num_filters", "num_policy_head_filters", "num_value_head_filters"):
+            setattr(cfg, f, getattr(blank, f))
+    key = (role, bytes(ctypes.string_at(ctypes.addressof(cfg), ctypes.sizeof(cfg))), tuple(os.environ.get(k, "") for k in CREATE_ENV),
+           bytes(ctypes.string_at(ctypes.addressof(rec), ctypes.sizeof(rec))) if rec is not None else b"")
     e = _cache.pop(key, None)
     if e is None or e._h is None:
         while len(_cache) >= CACHE_MAX:
             _evict()
-        e = Engine(cfg=cfg)
+        e = Engine(cfg=cfg, simplenet=rec)
         need = e.device_bytes()
         while _cache and _cache_bytes() + need > CACHE_MAX_BYTES:
             _evict()

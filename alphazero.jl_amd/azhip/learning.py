@@ -104,7 +104,7 @@ class Trainer:
         self.Wmean, self.Hp = self.data.Wmean, self.data.Hp
         self._hyper = network.hyper
         kw = network.engine_options()
-        self._eng = Engine(game=gspec.game_id, oracle=L.ORACLE_RESNET, device=device, num_workers=8, batch_size=8,
+        self._eng = Engine(game=gspec.game_id, oracle=network.ORACLE, device=device, num_workers=8, batch_size=8,
                            num_iters_per_turn=2, **kw)
         self._eng.net_set_params(network.params())
 

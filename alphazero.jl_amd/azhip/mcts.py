@@ -37,7 +37,9 @@ class HashOracle:
 
 
 def oracle_kind(oracle):
-    from .network import ResNet
+    from .network import ResNet, SimpleNet
+    if isinstance(oracle, SimpleNet):
+        return L.ORACLE_SIMPLENET
     if isinstance(oracle, ResNet):
         return L.ORACLE_RESNET
     if isinstance(oracle, (RandomOracle, HashOracle, RolloutOracle)):
@@ -55,13 +57,13 @@ class Env:
         self.gamma, self.cpuct, self.noise_ϵ, self.noise_α, self.prior_temperature = gamma, cpuct, noise_ϵ, noise_α, prior_temperature
         kw = {}
         kind = oracle_kind(oracle)
-        if kind == L.ORACLE_RESNET:
+        if kind in L.NET_ORACLES:
             kw = oracle.engine_options()
         self._e = Engine(game=gspec.game_id, oracle=kind, device=device, num_workers=1, batch_size=1,
                          num_iters_per_turn=2, gamma=gamma, cpuct=cpuct, dirichlet_noise_eps=noise_ϵ,
                          dirichlet_noise_alpha=noise_α, prior_temperature=prior_temperature, seed=seed,
                          max_nodes_per_slot=max_nodes, reset_every=0, **kw)
-        if kind == L.ORACLE_RESNET:
+        if kind in L.NET_ORACLES:
             self._e.net_set_params(oracle.params())
         self._calls = 0
 

@@ -1,4 +1,4 @@
-"""Network plugin mirror (src/networks/network.jl:30-328, src/networks/flux.jl, architectures/resnet.jl).
+"""Network plugin mirror (src/networks/network.jl:30-328, src/networks/flux.jl, architectures/resnet.jl, architectures/simplenet.jl).
 
 `ResNet` keeps its parameters as ONE fp32 blob in Flux array order (the layout az_net_set_params takes)
 and evaluates through the HIP tower/heads kernels.  Training (`train!`, optimisers) is outside the
@@ -83,10 +83,67 @@ def split_params(game, hp, blob):
     return out
 
 
+@dataclass(frozen=True)
+class SimpleNetHP:
+    """simplenet.jl:15-22"""
+    width: int
+    depth_common: int
+    depth_phead: int = 1
+    depth_vhead: int = 1
+    use_batch_norm: bool = False
+    batch_norm_momentum: float = 0.6
+
+
+def simple_param_layout(game, hp):
+    """[(name, Flux shape)] of a SimpleNet in blob order (csrc/net_layout.h SimpleLayout): common, policy head, value head; per
+    D(i -> o) the Dense's W (o, i) and b, then -- with batch norm only -- gamma, beta, mean, var."""
+    W, H, C, A = _DIMS[game]
+    h = hp.width
+
+    def D(prefix, i, o):
+        out = [(prefix + ".dense.W", (o, i)), (prefix + ".dense.b", (o,))]
+        if hp.use_batch_norm:
+            out += [(prefix + ".bn.gamma", (o,)), (prefix + ".bn.beta", (o,)), (prefix + ".bn.mean", (o,)), (prefix + ".bn.var", (o,))]
+        return out
+
+    out = D("common0", W * H * C, h)
+    for l in range(hp.depth_common):
+        out += D("common%d" % (l + 1), h, h)
+    for l in range(hp.depth_phead):
+        out += D("phead%d" % l, h, h)
+    out += [("phead.out.W", (A, h)), ("phead.out.b", (A,))]
+    for l in range(hp.depth_vhead):
+        out += D("vhead%d" % l, h, h)
+    out += [("vhead.out.W", (1, h)), ("vhead.out.b", (1,))]
+    return out
+
+
+def simple_random_params(game, hp, seed=2026):
+    """Flux's initial SimpleNet with the batch norms moved off the identity: Glorot-uniform dense weights, zero biases, and the batch-norm
+    vectors perturbed by U(-0.1, 0.1) around (gamma, beta, mean, var) = (1, 0, 0, 1) as random_params does; numpy's Philox(seed)."""
+    rng = np.random.Generator(np.random.Philox(seed))
+    parts = []
+    for name, shape in simple_param_layout(game, hp):
+        n = int(np.prod(shape))
+        if name.endswith(".W"):
+            s = np.sqrt(6.0 / (shape[0] + shape[1]))
+            parts.append(rng.uniform(-s, s, n))
+        elif name.endswith(".b"):
+            parts.append(np.zeros(n))
+        elif name.endswith(".gamma") or name.endswith(".var"):
+            parts.append(1.0 + rng.uniform(-0.1, 0.1, n))
+        else:
+            parts.append(rng.uniform(-0.1, 0.1, n))
+    return np.concatenate(parts).astype(np.float32)
+
+
 class ResNet:
     """ResNet <: TwoHeadNetwork (resnet.jl:45-92): ResNet(gspec, hyper)."""
 
     HyperParams = ResNetHP
+    ORACLE = L.ORACLE_RESNET
+    _layout = staticmethod(param_layout)
+    _random = staticmethod(random_params)
 
     def __init__(self, gspec, hyper, params=None, seed=2026, device=0, bf16=False):
         """bf16: evaluate the residual tower in bfloat16 (az_engine_cfg.net_bf16, csrc/resnet16b.h); the parameters stay fp32"""
@@ -94,8 +151,8 @@ class ResNet:
         self.hyper = hyper
         self.device = device
         self.bf16 = bool(bf16)
-        self._params = random_params(gspec.game_id, hyper, seed) if params is None else np.asarray(params, dtype=np.float32).copy()
-        if self._params.size != num_parameters(gspec.game_id, hyper):
+        self._params = self._random(gspec.game_id, hyper, seed) if params is None else np.asarray(params, dtype=np.float32).copy()
+        if self._params.size != int(sum(int(np.prod(s)) for _, s in self._layout(gspec.game_id, hyper))):
             raise ValueError("parameter blob has the wrong size")
         self._on_gpu = False
         self._test_mode = False
@@ -113,11 +170,23 @@ class ResNet:
 
     def num_parameters(self):
         # trainable parameters only (BatchNorm mean/var are state): network.jl:218-220
-        lay = param_layout(self.gspec.game_id, self.hyper)
+        lay = self._layout(self.gspec.game_id, self.hyper)
         return int(sum(int(np.prod(s)) for n, s in lay if not (n.endswith(".mean") or n.endswith(".var"))))
 
+    def param_layout(self):
+        return self._layout(self.gspec.game_id, self.hyper)
+
+    def split_params(self):
+        """{name: ndarray with the Julia shape (Fortran order view)} of this network's blob"""
+        out, off = {}, 0
+        for name, shape in self.param_layout():
+            n = int(np.prod(shape))
+            out[name] = self._params[off:off + n].reshape(shape, order="F")
+            off += n
+        return out
+
     def regularized_params(self):
-        p = split_params(self.gspec.game_id, self.hyper, self._params)
+        p = self.split_params()
         return [v for k, v in p.items() if k.endswith(".W")]
 
     def on_gpu(self):
@@ -137,7 +206,7 @@ class ResNet:
         self._test_mode = bool(mode)
 
     def copy_(self):
-        nn = ResNet(self.gspec, self.hyper, params=self._params, device=self.device, bf16=self.bf16)
+        nn = type(self)(self.gspec, self.hyper, params=self._params, device=self.device, bf16=self.bf16)
         nn._on_gpu, nn._test_mode = self._on_gpu, self._test_mode
         return nn
 
@@ -160,7 +229,7 @@ class ResNet:
 
     def _eng(self):
         if self._engine is None:
-            self._engine = Engine(game=self.gspec.game_id, oracle=L.ORACLE_RESNET, device=self.device,
+            self._engine = Engine(game=self.gspec.game_id, oracle=self.ORACLE, device=self.device,
                                   num_workers=1, batch_size=1, num_iters_per_turn=2, **self.engine_options())
             self._engine.net_set_params(self._params)
         return self._engine
@@ -183,6 +252,23 @@ class ResNet:
     __call__ = evaluate
 
 
+class SimpleNet(ResNet):
+    """SimpleNet <: TwoHeadNetwork (simplenet.jl:29-64): SimpleNet(gspec, hyper).  The interface of ResNet over the dense network."""
+
+    HyperParams = SimpleNetHP
+    ORACLE = L.ORACLE_SIMPLENET
+    _layout = staticmethod(simple_param_layout)
+    _random = staticmethod(simple_random_params)
+
+    def __init__(self, gspec, hyper, params=None, seed=2026, device=0, bf16=False):
+        if bf16:
+            raise ValueError("the SimpleNet runs in fp32")
+        super().__init__(gspec, hyper, params=params, seed=seed, device=device)
+
+    def engine_options(self):
+        return dict(simplenet=self.hyper)
+
+
 def copy(nn, on_gpu, test_mode):
     """Network.copy(nn; on_gpu, test_mode), network.jl:323-328"""
     nn = nn.copy_()
@@ -198,11 +284,21 @@ def with_filters(hp, **kw):
 MAGIC = b"AZHIPNET"
 
 
+SIMPLE_MAGIC = b"AZHIPSNT"
+
+
 def save_params(path, nn):
-    """Raw checkpoint of a network: magic, game id, ResNetHP fields (int32), parameter count (int64), Float32 little-endian
+    """Raw checkpoint of a network.  SimpleNet: magic AZHIPSNT, game id, width, the three depths, use_batch_norm (int32), parameter count
+    (int64), Float32 little-endian blob.  ResNet: magic, game id, ResNetHP fields (int32), parameter count (int64), Float32 little-endian
     blob in Flux parameter order -- the file julia/AlphaZeroHIP.jl's save_params writes (checkpoint interop)."""
     import struct
     h = nn.hyper
+    if isinstance(nn, SimpleNet):
+        with open(path, "wb") as f:
+            f.write(SIMPLE_MAGIC)
+            f.write(struct.pack("<6iq", nn.gspec.game_id, h.width, h.depth_common, h.depth_phead, h.depth_vhead, int(h.use_batch_norm), nn.params().size))
+            f.write(np.ascontiguousarray(nn.params(), dtype="<f4").tobytes())
+        return
     with open(path, "wb") as f:
         f.write(MAGIC)
         f.write(struct.pack("<5iq", nn.gspec.game_id, h.num_blocks, h.num_filters, h.num_policy_head_filters, h.num_value_head_filters,
@@ -213,7 +309,14 @@ def save_params(path, nn):
 def load_params(path, gspec):
     import struct
     with open(path, "rb") as f:
-        if f.read(8) != MAGIC:
+        magic = f.read(8)
+        if magic == SIMPLE_MAGIC:
+            game, w, dc, dp, dv, bn, n = struct.unpack("<6iq", f.read(32))
+            if game != gspec.game_id:
+                raise ValueError("parameter file is for game %d" % game)
+            blob = np.frombuffer(f.read(4 * n), dtype="<f4").astype(np.float32)
+            return SimpleNet(gspec, SimpleNetHP(width=w, depth_common=dc, depth_phead=dp, depth_vhead=dv, use_batch_norm=bool(bn)), params=blob)
+        if magic != MAGIC:
             raise ValueError("not an AZHIPNET parameter file")
         game, nb, nf, npf, nvf, n = struct.unpack("<5iq", f.read(28))
         if game != gspec.game_id:

@@ -115,12 +115,12 @@ class _Thinker:
         self.core = p
         if isinstance(p, MctsPlayer):
             mp, kind = p.params, oracle_kind(p.oracle)
-            kw = p.oracle.engine_options() if kind == L.ORACLE_RESNET else {}
+            kw = p.oracle.engine_options() if kind in L.NET_ORACLES else {}
             self.engine = Engine(game=gspec.game_id, oracle=kind, num_workers=num_workers, batch_size=num_workers,
                                  num_iters_per_turn=mp.num_iters_per_turn, gamma=mp.gamma, cpuct=mp.cpuct,
                                  dirichlet_noise_eps=mp.dirichlet_noise_ϵ, dirichlet_noise_alpha=mp.dirichlet_noise_α,
                                  prior_temperature=mp.prior_temperature, seed=p.seed, reset_every=0, lock_step=1, **kw)
-            if kind == L.ORACLE_RESNET:
+            if kind in L.NET_ORACLES:
                 self.engine.net_set_params(p.oracle.params())
 
     def close(self):

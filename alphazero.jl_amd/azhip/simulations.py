@@ -54,10 +54,10 @@ def _engine_for(gspec, player, p, device, seed):
         raise TypeError("the device path simulates MctsPlayer self-play only")
     kind = oracle_kind(player.oracle)
     kw = engine_options(player.params, p, seed=seed)
-    if kind == L.ORACLE_RESNET:
+    if kind in L.NET_ORACLES:
         kw.update(player.oracle.engine_options())
     e = cached_engine("selfplay", game=gspec.game_id, oracle=kind, device=device, **kw)   # kept across phases (engine.py)
-    if kind == L.ORACLE_RESNET:
+    if kind in L.NET_ORACLES:
         e.net_set_params(player.oracle.params())
     return e
 

@@ -210,7 +210,6 @@ def learning_step(gspec, curnn, bestnn, memory, learning_params, arena_params=No
     replacement rule avgr >= best so far (initially update_threshold).  Returns (curnn, bestnn, LearningReport)."""
     from .arena import compare_networks
     from .learning import Trainer
-    from .network import ResNet
     lp, ap = learning_params, arena_params
 
     def call(name, *a):                                           # Handlers.<name>(handler, ...), training.jl:40-75 (all optional)
@@ -240,7 +239,7 @@ def learning_step(gspec, curnn, bestnn, memory, learning_params, arena_params=No
             call("updates_finished", status)
             ttrain += t2 - t1
             tloss += t3 - t2
-            curnn = ResNet(gspec, curnn.hyper, params=tr.trained_params())      # get_trained_network
+            curnn = type(curnn)(gspec, curnn.hyper, params=tr.trained_params())      # get_trained_network
             if ap is None:
                 bestnn, replaced = curnn.copy_(), True
             else:

@@ -42,6 +42,7 @@ extern "C" int az_abi_struct_size(int32_t which) {
     case AZ_STRUCT_SOLVER_CFG: return (int)sizeof(az_solver_cfg);
     case AZ_STRUCT_HOST_TREE_CFG: return (int)sizeof(az_host_tree_cfg);
     case AZ_STRUCT_HOST_TREE_STATS: return (int)sizeof(az_host_tree_stats);
+    case AZ_STRUCT_SIMPLENET_HP: return (int)sizeof(az_simplenet_hp);
   }
   return -1;
 }
@@ -101,6 +102,15 @@ extern "C" int az_engine_cfg_init(az_engine_cfg* c) {
   c->num_workers = 128; c->batch_size = 64; c->reset_every = 2; c->fill_batches = 1;
   c->flip_probability = 0.0; c->seed = 1;
   c->num_blocks = 5; c->num_filters = 64; c->num_policy_head_filters = 32; c->num_value_head_filters = 32;
+  return AZ_OK;
+}
+
+// games/tictactoe/params.jl: SimpleNetHP(width = 200, depth_common = 6, use_batch_norm = true), head depths 1 (simplenet.jl:18-19)
+extern "C" int az_simplenet_hp_init(az_simplenet_hp* h) {
+  if (!h) return fail(AZ_ERR_BAD_ARG, "hp is NULL");
+  memset(h, 0, sizeof *h);
+  h->struct_size = (int32_t)sizeof *h;
+  h->width = 200; h->depth_common = 6; h->depth_phead = 1; h->depth_vhead = 1; h->use_batch_norm = 1;
   return AZ_OK;
 }
 
@@ -254,16 +264,18 @@ extern "C" int az_debug_slot_caps(az_engine* e, int* node_count, int* slot_cap) 
 // ---- az_engine_create, step by step.  Every step takes the engine as far as its title says and returns a status; after a failure
 // az_engine_destroy takes apart whatever the steps before it left.  The ORDER of the steps is the order of the device allocations and
 // of the work on the engine's stream.
-static int check_cfg(const az_engine_cfg* c, GameInfo* gi) {          // everything that can be refused before the device is touched
+// (hp: the SimpleNet hyperparameters az_engine_create_simplenet was given, else NULL)
+static int check_cfg(const az_engine_cfg* c, const az_simplenet_hp* hp, GameInfo* gi) {          // everything that can be refused before the device is touched
   if (c->struct_size != (int32_t)sizeof(az_engine_cfg)) return fail(AZ_ERR_BAD_ARG, "az_engine_cfg size mismatch (%d vs %zu): call az_engine_cfg_init", c->struct_size, sizeof(az_engine_cfg));
   if (!game_info(c->game, gi)) return fail(AZ_ERR_BAD_ARG, "unknown game id %d", c->game);
-  if (c->oracle < AZ_ORACLE_UNIFORM || c->oracle > AZ_ORACLE_ROLLOUT) return fail(AZ_ERR_BAD_ARG, "unknown oracle kind %d", c->oracle);
+  if (c->oracle == AZ_ORACLE_SIMPLENET && !hp) return fail(AZ_ERR_BAD_ARG, "a SimpleNet engine needs its hyperparameters: call az_engine_create_simplenet");
+  if (c->oracle < AZ_ORACLE_UNIFORM || c->oracle > AZ_ORACLE_SIMPLENET) return fail(AZ_ERR_BAD_ARG, "unknown oracle kind %d", c->oracle);
   if (c->game == AZ_GAME_GO9_PLANES && c->oracle != AZ_ORACLE_RESNET) return fail(AZ_ERR_BAD_ARG, "the 9x9x4 plane geometry has no device twin: it serves az_net_forward only (ResNet oracle)");
   if (c->num_workers < 1) return fail(AZ_ERR_BAD_ARG, "num_workers must be >= 1");
   if (c->batch_size > c->num_workers) return fail(AZ_ERR_BAD_ARG, "batch_size (%d) must be <= num_workers (%d) (src/params.jl:361-384)", c->batch_size, c->num_workers);
   // 0 = no search: the engine is a NetworkPlayer (play.jl:226-235) for az_arena_run
-  if (!(c->num_iters_per_turn >= 2 || (c->num_iters_per_turn == 0 && c->oracle == AZ_ORACLE_RESNET)))
-    return fail(AZ_ERR_BAD_ARG, "num_iters_per_turn must be >= 2 (with 1 the policy is 0/0, src/mcts.jl:267), or 0 with the ResNet oracle (NetworkPlayer, arena only)");
+  if (!(c->num_iters_per_turn >= 2 || (c->num_iters_per_turn == 0 && oracle_is_net(*c))))
+    return fail(AZ_ERR_BAD_ARG, "num_iters_per_turn must be >= 2 (with 1 the policy is 0/0, src/mcts.jl:267), or 0 with a network oracle (NetworkPlayer, arena only)");
   if (!(c->flip_probability >= 0.0 && c->flip_probability <= 1.0)) return fail(AZ_ERR_BAD_ARG, "flip_probability must be in [0, 1]");
   if (c->temperature_len < 1 || c->temperature_len > AZ_SCHED_MAX) return fail(AZ_ERR_BAD_ARG, "temperature schedule needs 1..%d breakpoints", AZ_SCHED_MAX);
   if (c->reset_every < 0) return fail(AZ_ERR_BAD_ARG, "reset_every must be >= 0");
@@ -275,6 +287,14 @@ static int check_cfg(const az_engine_cfg* c, GameInfo* gi) {          // everyth
     if (c->num_policy_head_filters < 1 || c->num_value_head_filters < 1 || hf > c->num_filters) return fail(AZ_ERR_BAD_ARG, "head filters %d/%d unsupported (policy + value must be <= num_filters)", c->num_policy_head_filters, c->num_value_head_filters);
     if (c->num_blocks < 0 || c->num_blocks > 64) return fail(AZ_ERR_BAD_ARG, "num_blocks out of range");
     if (c->net_bf16 != 0 && c->net_bf16 != 1) return fail(AZ_ERR_BAD_ARG, "net_bf16 must be 0 or 1");
+  }
+  if (c->oracle == AZ_ORACLE_SIMPLENET) {
+    if (hp->struct_size != (int32_t)sizeof(az_simplenet_hp)) return fail(AZ_ERR_BAD_ARG, "az_simplenet_hp size mismatch (%d vs %zu): call az_simplenet_hp_init", hp->struct_size, sizeof(az_simplenet_hp));
+    if (hp->width < 1 || hp->width > 16 * SN_WAVES * SN_TPW) return fail(AZ_ERR_BAD_ARG, "width = %d: a SimpleNet is 1 .. %d wide", hp->width, 16 * SN_WAVES * SN_TPW);
+    if (hp->depth_common < 0 || hp->depth_common > SN_MAX_DEPTH || hp->depth_phead < 0 || hp->depth_phead > SN_MAX_DEPTH || hp->depth_vhead < 0 || hp->depth_vhead > SN_MAX_DEPTH)
+      return fail(AZ_ERR_BAD_ARG, "depths %d / %d / %d: each of depth_common, depth_phead, depth_vhead is 0 .. %d", hp->depth_common, hp->depth_phead, hp->depth_vhead, SN_MAX_DEPTH);
+    if (hp->use_batch_norm != 0 && hp->use_batch_norm != 1) return fail(AZ_ERR_BAD_ARG, "use_batch_norm must be 0 or 1");
+    if (c->net_bf16 != 0) return fail(AZ_ERR_BAD_ARG, "net_bf16 must be 0: the SimpleNet runs in fp32");
   }
   return AZ_OK;
 }
@@ -396,7 +416,7 @@ static int create_side_records(az_engine* e) {
 static int create_eval_cache(az_engine* e) {
   const az_engine_cfg* c = &e->cfg; const GameInfo& gi = e->gi; DView& v = e->v; const int G = v.G;
   AZCHK(dalloc(e, &v.Pout, (size_t)std::max(G, 1) * gi.APAD)); AZCHK(dalloc(e, &v.Vout, G));
-  const bool on = e->env.eval_cache >= 0 ? e->env.eval_cache != 0 && c->oracle != AZ_ORACLE_ROLLOUT : c->oracle == AZ_ORACLE_RESNET;
+  const bool on = e->env.eval_cache >= 0 ? e->env.eval_cache != 0 && c->oracle != AZ_ORACLE_ROLLOUT : oracle_is_net(*c);
   if (!on || e->env.use_graphs) return AZ_OK;
   // sized from the workload: 8 x slots x simulations per move entries of 64 bytes, 2^16 (4 MB) ... 2^24 (1 GB: BASELINE
   // configs[1]; a phase there evaluates 2-6 x 10^7 states) -- an 8-slot test engine and the 128-worker arena players no longer hold
@@ -451,7 +471,7 @@ static int create_staging(az_engine* e) {
 static int create_net_buffers(az_engine* e) {
   const az_engine_cfg* c = &e->cfg; const GameInfo& gi = e->gi;
   e->nn_cap = e->io_cap;
-  AZCHK(dalloc(e, &e->d_hfeat, (size_t)e->nn_cap * gi.P * std::max(64, c->num_filters), false));
+  if (c->oracle != AZ_ORACLE_SIMPLENET) AZCHK(dalloc(e, &e->d_hfeat, (size_t)e->nn_cap * gi.P * std::max(64, c->num_filters), false));   // (a SimpleNet's features stay in LDS)
   AZCHK(dalloc(e, &e->d_X, (size_t)e->nn_cap * gi.C * gi.P)); AZCHK(dalloc(e, &e->d_A, (size_t)e->nn_cap * gi.A));
   AZCHK(dalloc(e, &e->d_P, (size_t)e->nn_cap * std::max(16, gi.APAD))); AZCHK(dalloc(e, &e->d_V, e->nn_cap)); AZCHK(dalloc(e, &e->d_Pinv, e->nn_cap));
   AZCHK(dalloc(e, &e->d_tmp_env, e->nn_cap)); AZCHK(dalloc(e, &e->d_iota, e->nn_cap)); AZCHK(dalloc(e, &e->d_ntmp, 1));
@@ -510,7 +530,7 @@ static int create_groups(az_engine* e) {
       HIPCHK(hipEventCreateWithFlags(&e->ev_tree[g], hipEventDisableTiming));
       HIPCHK(hipEventCreateWithFlags(&e->ev_net[g], hipEventDisableTiming));
     }
-    AZCHK(dalloc(e, &e->g_hfeat[g], (size_t)Gh * gi.P * std::max(64, c->num_filters), false));
+    if (c->oracle != AZ_ORACLE_SIMPLENET) AZCHK(dalloc(e, &e->g_hfeat[g], (size_t)Gh * gi.P * std::max(64, c->num_filters), false));
     e->ngroups = g + 1;
   }
   return AZ_OK;
@@ -550,20 +570,35 @@ static int create_finish(az_engine* e) {
 static int (*const CREATE_STEPS[])(az_engine*) = {create_stream, create_tree, create_side_records, create_eval_cache, create_words, create_staging,
                                                    create_net_buffers, create_groups, set_search_params, create_finish};
 
-extern "C" int az_engine_create(const az_engine_cfg* c, az_engine** out) {
-  if (!c || !out) return fail(AZ_ERR_BAD_ARG, "NULL argument");
-  *out = nullptr;
+static int engine_create(const az_engine_cfg* c, const az_simplenet_hp* hp, az_engine** out) {
   GameInfo gi;
-  AZCHK(check_cfg(c, &gi));
+  AZCHK(check_cfg(c, hp, &gi));
   AZCHK(use_device(c->device));
   az_engine* e = new (std::nothrow) az_engine();                      // (e->env: reads the creation-time overrides)
   if (!e) return fail(AZ_ERR_HIP, "out of host memory");
   e->cfg = *c; e->gi = gi; e->device = c->device;
+  if (hp) e->shp = *hp;
   int st = AZ_OK;
+  // a captured wave pair is keyed by what decides the TOWER kernel and its grid: not built for the one-launch network
+  if (hp && e->env.use_graphs) st = fail(AZ_ERR_BAD_ARG, "hipGraph replay (AZHIP_GRAPH) is not available for a SimpleNet engine");
   for (auto step : CREATE_STEPS) if (st == AZ_OK) st = step(e);
   if (st != AZ_OK) { std::string keep = g_err; az_engine_destroy(e); g_err = keep; return st; }
   *out = e;
   return AZ_OK;
+}
+extern "C" int az_engine_create(const az_engine_cfg* c, az_engine** out) {
+  if (!c || !out) return fail(AZ_ERR_BAD_ARG, "NULL argument");
+  *out = nullptr;
+  return engine_create(c, nullptr, out);
+}
+extern "C" int az_engine_create_simplenet(const az_engine_cfg* c, const az_simplenet_hp* hp, az_engine** out) {
+  if (!c || !hp || !out) return fail(AZ_ERR_BAD_ARG, "NULL argument");
+  *out = nullptr;
+  if (c->struct_size != (int32_t)sizeof(az_engine_cfg)) return fail(AZ_ERR_BAD_ARG, "az_engine_cfg size mismatch (%d vs %zu): call az_engine_cfg_init", c->struct_size, sizeof(az_engine_cfg));
+  if (c->game == AZ_GAME_GO9_PLANES) return fail(AZ_ERR_BAD_ARG, "the 9x9x4 plane geometry is served by ResNet engines only");
+  az_engine_cfg cs = *c;
+  cs.oracle = AZ_ORACLE_SIMPLENET;
+  return engine_create(&cs, hp, out);
 }
 
 
@@ -646,7 +681,7 @@ extern "C" int az_game_play(az_engine* e, const uint64_t* keys, const int32_t* a
 // ------------------------------------------------------------------------------- network
 extern "C" int az_net_num_params(const az_engine* e, int64_t* n) {
   if (!e || !n) return fail(AZ_ERR_BAD_ARG, "NULL");
-  *n = (int64_t)net_layout(e->gi, e->cfg).total;
+  *n = e->cfg.oracle == AZ_ORACLE_SIMPLENET ? (int64_t)simple_layout(e->gi, e->shp).total : (int64_t)net_layout(e->gi, e->cfg).total;
   return AZ_OK;
 }
 
@@ -712,10 +747,61 @@ static NetHost net_host(const NetLayout& lay, const NetMaps& M, const float* blo
 }
 
 static int ec_empty(az_engine* e, bool wipe = false);
+// az_net_set_params of a SimpleNet engine: per layer its fragments (net_layout.h order_simple16) and its folded [scale | shift], all
+// layers in two device arrays; the layer table (which activation buffer each layer reads and writes) goes to the kernel by value
+static int simple_set_params(az_engine* e, const float* blob, int64_t n) {
+  const SimpleLayout lay = simple_layout(e->gi, e->shp);
+  if (!blob || n != (int64_t)lay.total) return fail(AZ_ERR_BAD_ARG, "parameter blob has %lld values, expected %zu", (long long)n, lay.total);
+  e->blob.assign(blob, blob + n);
+  if (!e->simple_maps) { e->simple_maps.reset(new SimpleMaps(lay)); e->trainable = trainable_mask(lay); }
+  const SimpleMaps& M = *e->simple_maps;
+  SimpleDev sd;
+  memset(&sd, 0, sizeof sd);
+  std::vector<float> w, ss;
+  const int nl = (int)lay.dense.size();
+  const int HP = pad_to(lay.s.width, 16);
+  sd.nlayers = nl; sd.indim = lay.s.indim; sd.kp0 = pad_to(lay.s.indim, 16); sd.rs = sn_row_words(std::max(sd.kp0, HP));
+  // buffers: the trunk alternates 0 <-> 1 and leaves its result in `c`; each head alternates between the two others
+  const int c = lay.ncommon() & 1, ab[2] = {c == 0 ? 1 : 0, 2};
+  int src = 0, hp = 0;
+  for (int l = 0; l < nl; ++l) {
+    const DenseAt& d = lay.dense[l];
+    if (l == lay.pfirst() || l == lay.vfirst()) { src = c; hp = 0; }
+    SnLayer& L = sd.layer[l];
+    const int OP = pad_to(d.out, 16);
+    L.w_off = (uint32_t)w.size(); L.ss_off = (uint32_t)ss.size();
+    L.kb = (uint16_t)(pad_to(d.in, 16) / 16); L.ct = (uint16_t)(OP / 16);
+    L.src = (uint8_t)src;
+    L.mode = !d.last ? SN_HIDDEN : l == nl - 1 ? SN_VALUE : SN_POLICY;
+    if (l < lay.ncommon()) L.dst = (uint8_t)(src ^ 1); else L.dst = (uint8_t)ab[hp++ & 1];
+    src = L.dst;
+    const std::vector<float> wl = gather(M.layer[l].w, blob), b = gather(M.layer[l].b, blob);
+    w.insert(w.end(), wl.begin(), wl.end());
+    std::vector<float> f(2 * (size_t)OP, 0.0f);
+    if (d.bn) {
+      std::vector<float> bn;
+      for (int k = 0; k < 4; ++k) { const std::vector<float> v = gather(M.layer[l].bn[k], blob); bn.insert(bn.end(), v.begin(), v.end()); }
+      bn_fold(b.data(), bn.data(), OP, f.data(), f.data() + OP);    // (padded columns: gamma 0 -- scale and shift exactly 0)
+    } else {
+      for (int o = 0; o < OP; ++o) { f[o] = 1.0f; f[OP + o] = b[o]; }
+    }
+    ss.insert(ss.end(), f.begin(), f.end());
+  }
+  AZCHK(sync_all(e));
+  for (void* q : e->net_allocs) (void)hipFree(q);
+  e->net_allocs.clear();
+  e->net_loaded = false;
+  AZCHK(net_upload(e, w, &sd.w)); AZCHK(net_upload(e, ss, &sd.ss));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  e->snet = sd;
+  e->net_loaded = true;
+  return ec_empty(e);                                                // the answers of the old network are gone with it
+}
 extern "C" int az_net_set_params(az_engine* e, const float* blob, int64_t n) {
   ENGINE(e);
-  if (e->cfg.oracle != AZ_ORACLE_RESNET) return fail(AZ_ERR_STATE, "engine was created without the ResNet oracle");
+  if (!oracle_is_net(e->cfg)) return fail(AZ_ERR_STATE, "engine was created without a network oracle");
   if (e->running) return fail(AZ_ERR_STATE, "self-play in progress");
+  if (e->cfg.oracle == AZ_ORACLE_SIMPLENET) return simple_set_params(e, blob, n);
   const az_engine_cfg& c = e->cfg;
   const NetLayout lay = net_layout(e->gi, c);
   if (!blob || n != (int64_t)lay.total) return fail(AZ_ERR_BAD_ARG, "parameter blob has %lld values, expected %zu", (long long)n, lay.total);
@@ -912,11 +998,11 @@ template <class Gm> static int wave_group(az_engine* e, int g, uint32_t sim_idx)
   // streams, behind an event recorded here, and the next wave's launch waits for ONE event that stands for both (below).
   hipStream_t s2 = st;
   e->bg_signal = false;
-  const bool side = e->fr_on && !split && e->cfg.oracle == AZ_ORACLE_RESNET && e->fr_s[1] && st == e->fr_s[0];
+  const bool side = e->fr_on && !split && oracle_is_net(e->cfg) && e->fr_s[1] && st == e->fr_s[0];
   // (the stop word of the background search: without it a background launch of fr_kbg simulations outlasts a SHORT tower and the next wave
   // waits for it -- Mancala, 8192 slots: 19.8 instead of 39.7 M sims/s; AZHIP_BG_STOP=0 switches it off)
   if (side) { s2 = e->fr_s[1]; HIPCHK(hipEventRecord(e->fr_ev[0], st)); ++e->bg_seq; e->bg_signal = env_process().bg_stop && e->fr_kbg > 0; }
-  if (e->cfg.oracle == AZ_ORACLE_RESNET) {
+  if (oracle_is_net(e->cfg)) {
     AZCHK(net_wave(e, g, split, e->group_active[g]));
   } else {
     LAUNCH_ON(e, st, AZ_K_SYNTH, G, (k_synth_oracle<Gm>), (G + 255) / 256, 256, 0, v, e->p, sim_idx, par);
@@ -947,7 +1033,7 @@ template <class Gm> static int wave_group(az_engine* e, int g, uint32_t sim_idx)
       HIPCHK(hipEventRecord(e->fr_ev[2], s3)); HIPCHK(hipStreamWaitEvent(s2, e->fr_ev[2], 0));
       HIPCHK(hipEventRecord(e->fr_ev[1], s2)); HIPCHK(hipStreamWaitEvent(st, e->fr_ev[1], 0));
     }   // the next wave's launch finds the slots' state settled
-    else if (split && e->cfg.oracle == AZ_ORACLE_RESNET) HIPCHK(hipStreamWaitEvent(st, e->ev_net[g], 0));   // the next wave's launch needs this wave's answers
+    else if (split && oracle_is_net(e->cfg)) HIPCHK(hipStreamWaitEvent(st, e->ev_net[g], 0));   // the next wave's launch needs this wave's answers
   }
   return AZ_OK;
 }
@@ -975,7 +1061,7 @@ template <class Gm> static int recover_split(az_engine* e) {
     e->wave_par[g] ^= (skipped[2 * g] & 1);                          // back to the leaf counter of the last wave that really ran
     if (skipped[2 * g + 1]) e->pending[g] = true;                    // its expand + backup did not happen
   }
-  if (e->cfg.oracle == AZ_ORACLE_RESNET)
+  if (oracle_is_net(e->cfg))
     for (int g = 0; g < e->ngroups; ++g)
       if (e->pending[g] && e->group_active[g] > 0) {
         AZCHK(net_wave(e, g, e->gs[g] != e->gt[g], e->group_active[g]));
@@ -1176,7 +1262,7 @@ extern "C" int az_mcts_explore(az_engine* e, const uint64_t* root_keys, int32_t 
   if (e->mm_on) return fail(AZ_ERR_STATE, "the engine is a MinMax player (az_engine_set_minmax): it has no search to explore");
   if (!root_keys || nslots < 1 || nslots > e->v.G) return fail(AZ_ERR_BAD_ARG, "nslots must be in 1..num_workers");
   if (nsims < 1) return fail(AZ_ERR_BAD_ARG, "nsims must be >= 1");
-  if (e->cfg.oracle == AZ_ORACLE_RESNET && !e->net_loaded) return fail(AZ_ERR_STATE, "az_net_set_params has not been called");
+  if (oracle_is_net(e->cfg) && !e->net_loaded) return fail(AZ_ERR_STATE, "az_net_set_params has not been called");
   std::vector<int> slots(nslots);
   std::vector<uint32_t> gids(nslots), mv(nslots);
   std::vector<GEnv> roots(nslots);
@@ -1270,7 +1356,7 @@ extern "C" int az_selfplay_begin(az_engine* e, int32_t num_games, int32_t first_
     DISPATCH_GAME(e->cfg.game, nosym = Gm::NSYM == 0);
     if (nosym) return fail(AZ_ERR_BAD_ARG, "flip_probability != 0 but no symmetries were declared for this game (game.jl:332)");
   }
-  if (e->cfg.oracle == AZ_ORACLE_RESNET && !e->net_loaded) return fail(AZ_ERR_STATE, "az_net_set_params has not been called");
+  if (oracle_is_net(e->cfg) && !e->net_loaded) return fail(AZ_ERR_STATE, "az_net_set_params has not been called");
   const int G = e->v.G;
   // a fresh player per worker (simulations.jl:217-218): empty trees, zero counters
   AZCHK(reset_wave_state(e));
@@ -1337,7 +1423,7 @@ extern "C" int az_selfplay_begin(az_engine* e, int32_t num_games, int32_t first_
       e->fr_prev_done = 0; e->fr_prev_recs = 0; e->fr_since_round = 0; e->fr_given_up = 0;
     }
     for (int g = 0; g < e->ngroups; ++g) { e->gv[g].run_k = on ? e->fr_k : 0; e->gv[g].fr = on ? 1 : 0; e->gv[g].fr_active = on ? &e->d_fr->active[g] : nullptr; }
-    if (on && e->ngroups == 1 && e->cfg.oracle == AZ_ORACLE_RESNET) {   // tree kernels under the group's own network launch: two streams (ev_* with them)
+    if (on && e->ngroups == 1 && oracle_is_net(e->cfg)) {   // tree kernels under the group's own network launch: two streams (ev_* with them)
       HIPCHK(hipStreamSynchronize(e->stream));
       e->gs[0] = e->gt[0] = e->fr_s[0];                                // (the second stream, fr_s[1], carries the move step and the background search: wave_group)
     }
@@ -1934,7 +2020,7 @@ extern "C" int az_arena_run(az_engine* contender, az_engine* baseline, int32_t n
   if (num_games < 1) return fail(AZ_ERR_BAD_ARG, "num_games must be >= 1");
   if (baseline->v.G < std::min(contender->v.G, (int)num_games)) return fail(AZ_ERR_BAD_ARG, "baseline engine has fewer workers (%d) than the arena needs (%d)", baseline->v.G, std::min(contender->v.G, (int)num_games));
   for (az_engine* e : {contender, baseline})
-    if (e->cfg.oracle == AZ_ORACLE_RESNET && !e->net_loaded) return fail(AZ_ERR_STATE, "az_net_set_params has not been called");
+    if (oracle_is_net(e->cfg) && !e->net_loaded) return fail(AZ_ERR_STATE, "az_net_set_params has not been called");
   if (out && (!out->games || !out->moves)) return fail(AZ_ERR_BAD_ARG, "NULL trace buffers");
   const bool trace = EnvArena().trace;     // which tower forms served the evaluation, and who else counted as a split-tower user
   long long h0[2][4];

@@ -359,7 +359,7 @@ extern "C" int az_comm_broadcast_params(az_comm* c, az_engine* e, int32_t root) 
   int64_t n = 0;
   if (!e) local = fail(AZ_ERR_BAD_ARG, "NULL engine");
   else if (e->device != c->device) local = fail(AZ_ERR_BAD_ARG, "engine and communicator are on different devices");
-  else if (e->cfg.oracle != AZ_ORACLE_RESNET) local = fail(AZ_ERR_STATE, "engine was created without the ResNet oracle");
+  else if (!oracle_is_net(e->cfg)) local = fail(AZ_ERR_STATE, "engine was created without a network oracle");
   else if (c->rank == root && !e->net_loaded) local = fail(AZ_ERR_STATE, "the root has no parameters loaded");
   else local = az_net_num_params(e, &n);
   std::vector<float> h;

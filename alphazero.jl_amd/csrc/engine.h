@@ -28,6 +28,7 @@
 #include "resnet.h"
 #include "resnet16.h"
 #include "resnet16b.h"
+#include "simplenet.h"
 #include "tree.h"
 
 // ------------------------------------------------------------------------------- errors
@@ -80,6 +81,14 @@ inline NetLayout net_layout(const GameInfo& gi, const az_engine_cfg& c) {
   return NetLayout(NetShape{gi.C, gi.P, gi.A, gi.APAD, c.num_blocks, c.num_filters, c.num_policy_head_filters, c.num_value_head_filters});
 }
 
+// where each piece of a SimpleNet engine's parameter blob lies (net_layout.h)
+inline SimpleLayout simple_layout(const GameInfo& gi, const az_simplenet_hp& h) {
+  return SimpleLayout(SimpleShape{gi.C * gi.P, gi.A, h.width, h.depth_common, h.depth_phead, h.depth_vhead, h.use_batch_norm});
+}
+// "the engine's oracle is its network": what the search, the arena, the replay memory, the learning status, the trainer, the broadcast
+// and the host-stepped trees ask before they use az_net_* machinery
+inline bool oracle_is_net(const az_engine_cfg& c) { return c.oracle == AZ_ORACLE_RESNET || c.oracle == AZ_ORACLE_SIMPLENET; }
+
 // ------------------------------------------------------------------------------- engine
 // The tower forms.  The values are the AZHIP_TOWER numbers (az_engine::env.tower_pick); net_impl.h holds one descriptor per form
 // (kernel, layout, geometry table, availability, name, tower_hist bucket) and pick_tower, which chooses among them.
@@ -102,6 +111,7 @@ struct ProfRec { hipEvent_t a = nullptr, b = nullptr; int cls = 0; };
 // any point in between.  DView / DParams go to the kernels by value and stay trivially copyable (memset by the step that fills them).
 struct az_engine {
   az_engine_cfg cfg = {};
+  az_simplenet_hp shp = {};         // cfg.oracle == AZ_ORACLE_SIMPLENET: the network's hyperparameters (the ResNet fields of cfg are unused)
   GameInfo gi = {};
   EnvCreate env;                 // the AZHIP_* overrides, read when az_engine_create constructs this record (env.h): forced kernels, experiments, test knobs
   int device = 0;
@@ -152,6 +162,8 @@ struct az_engine {
   std::unique_ptr<const NetMaps> net_maps;   // net_layout.h: the index maps of the arrays below; they depend on cfg only, so the first az_net_set_params builds them for all
   std::vector<unsigned char> trainable;      // net_layout.h trainable_mask: built with net_maps; the regularisation sum of az_learning_status walks it
   NetDev net = {};
+  std::unique_ptr<const SimpleMaps> simple_maps;   // SimpleNet engines: net_layout.h, built by the first az_net_set_params
+  SimpleDev snet = {};           // k_simplenet's fragments, folded batch norms and layer table (SimpleNet engines)
   Net16bDev net16b = {};         // bf16 fragments (cfg.net_bf16)
   Net16Dev net16 = {};           // k_tower16 fragments (64 filters)
   uint16_t* d_geo[GEO_COUNT] = {};   // Geo16 tables by GeoSlot (resnet16.h); GEO_NTM is NULL where the game has no exact-fit variant

@@ -425,7 +425,7 @@ extern "C" int az_host_tree_create(az_engine* e, int32_t device, int32_t num_act
   if (edge_slots_per_worker < num_actions) return fail(AZ_ERR_BAD_ARG, "edge_slots_per_worker = %d below num_actions = %d", edge_slots_per_worker, num_actions);
   if (max_depth < 1) return fail(AZ_ERR_BAD_ARG, "max_depth = %d below 1", max_depth);
   if (e) {
-    if (e->cfg.oracle != AZ_ORACLE_RESNET) return fail(AZ_ERR_BAD_ARG, "engine mode needs an engine with the ResNet oracle");
+    if (!oracle_is_net(e->cfg)) return fail(AZ_ERR_BAD_ARG, "engine mode needs an engine with a network oracle");
     if (!e->net_loaded) return fail(AZ_ERR_STATE, "az_net_set_params has not been called");
     if (num_actions != e->gi.A) return fail(AZ_ERR_BAD_ARG, "num_actions = %d, the engine's game has %d", num_actions, e->gi.A);
     if (num_workers > e->nn_cap) return fail(AZ_ERR_BAD_ARG, "num_workers = %d above the %d rows one network launch of the engine takes", num_workers, e->nn_cap);

@@ -641,7 +641,7 @@ extern "C" int az_learning_status(az_engine* e, az_dataset* d, double l2_regular
   ENGINE(e);
   if (!d || !out) return fail(AZ_ERR_BAD_ARG, "NULL argument");
   if (e->running) return fail(AZ_ERR_STATE, "self-play in progress");
-  if (e->cfg.oracle != AZ_ORACLE_RESNET || !e->net_loaded) return fail(AZ_ERR_STATE, "az_net_set_params has not been called");
+  if (!oracle_is_net(e->cfg) || !e->net_loaded) return fail(AZ_ERR_STATE, "az_net_set_params has not been called");
   if (d->game != e->cfg.game || d->device != e->device) return fail(AZ_ERR_BAD_ARG, "data set and engine differ in game or device");
   if (d->n < 1) return fail(AZ_ERR_BAD_ARG, "empty data set");
   if (loss_computation_batch_size < 1) return fail(AZ_ERR_BAD_ARG, "loss_computation_batch_size must be >= 1");

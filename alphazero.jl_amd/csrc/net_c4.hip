@@ -95,7 +95,7 @@ template <int F> static int heads_timeline(az_engine* e, int32_t n, unsigned lon
 // the bounded poll must give up (DERR_EXCHANGE -> AZ_ERR_HIP from this call) instead of hanging the GPU
 extern "C" int az_debug_exchange_timeout(az_engine* e) {
   ENGINE(e);
-  if (!e->net_loaded || e->cfg.game != AZ_GAME_CONNECT_FOUR || e->cfg.num_filters != 128 || e->cfg.net_bf16) return fail(AZ_ERR_BAD_ARG, "connect-four, 128 filters, fp32");
+  if (e->cfg.oracle != AZ_ORACLE_RESNET || !e->net_loaded || e->cfg.game != AZ_GAME_CONNECT_FOUR || e->cfg.num_filters != 128 || e->cfg.net_bf16) return fail(AZ_ERR_BAD_ARG, "connect-four, ResNet oracle, 128 filters, fp32");
   using T = T16S<ConnectFour, 128>;
   const int n = 2;
   std::vector<GEnv> envs(n, ConnectFour::init());
@@ -125,11 +125,12 @@ extern "C" int az_debug_tree_stamps(az_engine* e, unsigned long long* out) {
 }
 extern "C" int az_debug_heads_timeline(az_engine* e, int32_t n, unsigned long long* out, int64_t cap) {
   ENGINE(e);
-  if (!e->net_loaded || n < 1 || n > e->nn_cap || e->cfg.game != AZ_GAME_CONNECT_FOUR || !e->net.hd16_ok) return fail(AZ_ERR_BAD_ARG, "connect-four with 32 head filters");
+  if (e->cfg.oracle != AZ_ORACLE_RESNET || !e->net_loaded || n < 1 || n > e->nn_cap || e->cfg.game != AZ_GAME_CONNECT_FOUR || !e->net.hd16_ok) return fail(AZ_ERR_BAD_ARG, "connect-four, ResNet oracle with 32 head filters");
   return e->cfg.num_filters == 128 ? heads_timeline<128>(e, n, out, cap) : heads_timeline<64>(e, n, out, cap);
 }
 extern "C" int az_debug_tower_timeline(az_engine* e, int32_t n, int32_t nt, unsigned long long* out, int64_t cap) {
   ENGINE(e);
+  if (e->cfg.oracle != AZ_ORACLE_RESNET) return fail(AZ_ERR_BAD_ARG, "the tower timeline needs an engine with the ResNet oracle");
   if (!e->net_loaded || n < 1 || n > e->nn_cap) return fail(AZ_ERR_BAD_ARG, "bad n / no net");
   if (e->cfg.game == AZ_GAME_CONNECT_FOUR && e->cfg.net_bf16 && nt == 11) return e->cfg.num_filters == 128 ? tower_timeline_bf16<128>(e, n, out, cap) : tower_timeline_bf16<64>(e, n, out, cap);
   if (e->cfg.game != AZ_GAME_CONNECT_FOUR || e->cfg.net_bf16 || (nt != 11 && nt != 3 && nt != 2)) return fail(AZ_ERR_BAD_ARG, "connect-four; fp32: nt = 11, 3 or 2 (= split tower), bf16: nt = 11");

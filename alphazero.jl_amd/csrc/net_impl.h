@@ -116,7 +116,60 @@ template <class G> static int geometry_out(uint16_t* out, int64_t cap, int* rows
   *rows = G::RPAD; *products = G::tab.cost;
   return AZ_OK;
 }
+static const char* game_name(const az_engine* e);
+// The background search's stop word behind a network launch that does not raise it itself (every form but the paired towers, and
+// k_simplenet): set from a stream of its own behind an event on the launch's stream `sn` (a one-thread launch IN the wave's stream sat
+// 7.6 us between tower and heads)
+static int raise_stop_word(az_engine* e, hipStream_t sn) {
+  HIPCHK(hipEventRecord(e->fr_ev[3], sn));
+  HIPCHK(hipStreamWaitEvent(e->fr_s[3], e->fr_ev[3], 0));
+  hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, e->fr_s[3], e->d_bg_stop, e->bg_seq);
+  return AZ_OK;
+}
+// ---- SimpleNet engines (simplenet.h): one kernel, one launch per batch ------------------------------------------------------------
+template <class Gm> static constexpr bool SIMPLE_OK = Gm::A <= 16;   // one policy tile: the three device twins (the plane geometry is refused at create)
+template <class Gm> static int simple_set_kernel_attrs() {
+  if constexpr (SIMPLE_OK<Gm>) {
+    const int most = (int)sn_lds_bytes(sn_row_words(16 * SN_WAVES * SN_TPW));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_simplenet<Gm, false>), hipFuncAttributeMaxDynamicSharedMemorySize, most));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_simplenet<Gm, true>), hipFuncAttributeMaxDynamicSharedMemorySize, most));
+  }
+  return AZ_OK;
+}
+// the whole network on up to n_max boards (device count in n_ptr when given); the arguments of launch_heads
+template <class Gm, bool FROM_PLANES>
+static int launch_simple(az_engine* e, hipStream_t st, const GEnv* envs, const int* eslots, const int* n_ptr, int n_max, const float* X,
+                         const float* Amask, float* Pout, float* Vout, float* Pinv, int pstride) {
+  if constexpr (!SIMPLE_OK<Gm>) return fail(AZ_ERR_STATE, "no SimpleNet kernel for this geometry");
+  else {
+    if (n_max <= 0) return AZ_OK;
+    snprintf(e->last_tower, sizeof e->last_tower, "k_simplenet<%s>", game_name(e));
+    e->tower_hist[3]++;
+    LAUNCH_ON(e, st, AZ_K_TOWER, n_max, (k_simplenet<Gm, FROM_PLANES>), (n_max + SN_ROWS - 1) / SN_ROWS, SN_THREADS, sn_lds_bytes(e->snet.rs), e->snet,
+              envs, eslots, n_ptr, n_max, X, Amask, Pout, Vout, Pinv, pstride);
+    return AZ_OK;
+  }
+}
+// The network part of a wave: the one launch takes the place of tower + heads on the group's network stream; the streams meet as in
+// wave_net_f, and the background search's stop word is raised behind the launch (k_simplenet does not raise it itself).
+template <class Gm> static int wave_simple(az_engine* e, int g, bool split, int nmax) {
+  const DView& v = e->gv[g];
+  hipStream_t st = e->gs[g], sn = e->gt[g];
+  if (split) { HIPCHK(hipEventRecord(e->ev_tree[g], st)); HIPCHK(hipStreamWaitEvent(sn, e->ev_tree[g], 0)); }
+  const int N = std::max(1, std::min(v.G, nmax));
+  const int* nev = v.n_eval + e->wave_par[g];
+  const int* const eslots = v.eval_slots + (size_t)e->wave_par[g] * v.eval_stride;
+  AZCHK((launch_simple<Gm, false>(e, sn, v.leaf_env, eslots, nev, N, nullptr, nullptr, v.Pout, v.Vout, nullptr, Gm::APAD)));
+  if (e->bg_signal) AZCHK(raise_stop_word(e, sn));
+  if (split) {
+    HIPCHK(hipEventRecord(e->ev_net[g], sn));
+    if (!e->fr_on) HIPCHK(hipStreamWaitEvent(st, e->ev_net[g], 0));   // (a free-running wave_group waits for ev_net at its end)
+  }
+  return AZ_OK;
+}
+
 template <class Gm> static int set_kernel_attrs(az_engine* e) {
+  if (e->cfg.oracle == AZ_ORACLE_SIMPLENET) return simple_set_kernel_attrs<Gm>();
   AZCHK((set_kernel_attrs_f<Gm, 64>(Forms<Gm, 64>{})));
   AZCHK((set_kernel_attrs_f<Gm, 128>(Forms<Gm, 128>{})));
   memset(e->d_geo, 0, sizeof e->d_geo);
@@ -303,6 +356,7 @@ static int launch_net_f(az_engine* e, hipStream_t st, float* hfeat, const GEnv* 
 template <class Gm, bool FROM_PLANES>
 static int launch_net(az_engine* e, hipStream_t st, float* hfeat, const GEnv* envs, const int* eslots, const int* n_ptr, int n_max, const float* X,
                       const float* Amask, float* Pout, float* Vout, float* Pinv, int pstride) {
+  if (e->cfg.oracle == AZ_ORACLE_SIMPLENET) return launch_simple<Gm, FROM_PLANES>(e, st, envs, eslots, n_ptr, n_max, X, Amask, Pout, Vout, Pinv, pstride);
   if (e->cfg.num_filters == 128) return launch_net_f<Gm, 128, FROM_PLANES>(e, st, hfeat, envs, eslots, n_ptr, n_max, X, Amask, Pout, Vout, Pinv, pstride);
   return launch_net_f<Gm, 64, FROM_PLANES>(e, st, hfeat, envs, eslots, n_ptr, n_max, X, Amask, Pout, Vout, Pinv, pstride);
 }
@@ -370,9 +424,7 @@ template <class Gm, int F> static int wave_net_f(az_engine* e, int g, bool split
   if (e->bg_signal && !tower_stops) {
     // a form that does not raise the word itself.  The tower has run: the background search of this wave winds up while the heads run.  The
     // word is set from a stream of its own behind an event (a one-thread launch IN the wave's stream sat 7.6 us between tower and heads)
-    HIPCHK(hipEventRecord(e->fr_ev[3], sn));
-    HIPCHK(hipStreamWaitEvent(e->fr_s[3], e->fr_ev[3], 0));
-    hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, e->fr_s[3], e->d_bg_stop, e->bg_seq);
+    AZCHK(raise_stop_word(e, sn));
   }
   if (split && !fr) { HIPCHK(hipEventRecord(e->ev_net[g], sn)); HIPCHK(hipStreamWaitEvent(st, e->ev_net[g], 0)); }
   AZCHK((launch_heads<Gm, F>(e, fr ? sn : st, e->g_hfeat[g], v.leaf_env, eslots, nev, N, (const float*)nullptr, v.Pout, v.Vout, (float*)nullptr, L)));
@@ -380,6 +432,7 @@ template <class Gm, int F> static int wave_net_f(az_engine* e, int g, bool split
   return AZ_OK;
 }
 template <class Gm> static int wave_net(az_engine* e, int g, bool split, int nmax) {
+  if (e->cfg.oracle == AZ_ORACLE_SIMPLENET) return wave_simple<Gm>(e, g, split, nmax);
   return e->cfg.num_filters == 128 ? wave_net_f<Gm, 128>(e, g, split, nmax) : wave_net_f<Gm, 64>(e, g, split, nmax);
 }
 

@@ -7,6 +7,8 @@
 //                    ORDER, named after the kernel that reads it; what is reordered is a `source`, a callable (tap, ci, co) -> blob
 //                    index (or -1), so one order serves a tower layer, the concatenated head convolution and the trainer alike.
 //   NetMaps          the maps of one engine's device arrays (they depend on the configuration only: built once per engine)
+//   SimpleLayout     the same for NetLib.SimpleNet, the dense two-headed network (at the end of this file): SimpleMaps for k_simplenet
+//                    (simplenet.h), SimpleTrainMaps for a dense optimiser chain
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -234,5 +236,91 @@ struct TrainMaps {
 inline std::vector<unsigned char> trainable_mask(const NetLayout& L) {
   std::vector<unsigned char> t(L.total, 1);
   for (const ConvAt& c : L.conv) for (int i = 0; i < 2 * c.cout; ++i) t[c.bn_vec(2) + i] = 0;
+  return t;
+}
+
+// ================================================================================================================== SimpleNet
+// NetLib.SimpleNet (src/networks/architectures/simplenet.jl:37-64): with h = width, indim = prod(state_dim), A = num_actions
+//   common = flatten, D(indim -> h), D(h -> h) x depth_common;  vhead = D(h -> h) x depth_vhead, Dense(h -> 1, tanh);
+//   phead  = D(h -> h) x depth_phead, Dense(h -> A), softmax;   D(i -> o) = Dense(i -> o) + BatchNorm(o, relu) or Dense(i -> o, relu)
+// Blob order, as the ResNet's: common, policy head, value head; per D the Flux arrays W(o, i) column-major (W[o + out i]), b(o) and --
+// with batch norm only, never zero-filled otherwise -- gamma, beta, running mean, running variance; the final layers W, b.
+// The shipped Tic-tac-toe network (games/tictactoe/params.jl: width 200, depth_common 6, batch norm, head depths 1) is 336 410 values,
+// of which Flux.trainables counts 332 810 (the 9 x 2 x 200 running statistics are state).
+struct SimpleShape { int indim, A, width, depth_common, depth_phead, depth_vhead, use_batch_norm; };
+// one Dense (+ BatchNorm) in the blob
+struct DenseAt {
+  int in, out;
+  bool bn, last;                                                  // last: Dense(h -> A) / Dense(h -> 1), no relu in the layer itself
+  size_t w, b, bnv;
+  size_t bn_vec(int k) const { return bnv + (size_t)k * out; }    // k = 0 .. 3: gamma, beta, running mean, running variance (bn only)
+  size_t nw() const { return (size_t)in * out; }
+  int32_t at(int i, int o) const { return i < in && o < out ? (int32_t)(w + o + (size_t)out * i) : -1; }   // W(o, i), -1 outside
+};
+struct SimpleLayout {
+  SimpleShape s;
+  std::vector<DenseAt> dense;    // [0 .. depth_common] common, then depth_phead D + the policy Dense, then depth_vhead D + the value Dense
+  size_t total;
+  explicit SimpleLayout(const SimpleShape& sh) : s(sh) {
+    size_t at = 0;
+    auto take = [&](size_t n) { const size_t o = at; at += n; return o; };
+    auto add = [&](int in, int out, bool last) {
+      DenseAt d{in, out, !last && s.use_batch_norm != 0, last, 0, 0, 0};
+      d.w = take(d.nw()); d.b = take(out);
+      if (d.bn) d.bnv = take(4 * (size_t)out);
+      dense.push_back(d);
+    };
+    add(s.indim, s.width, false);
+    for (int l = 0; l < s.depth_common; ++l) add(s.width, s.width, false);
+    for (int l = 0; l < s.depth_phead; ++l) add(s.width, s.width, false);
+    add(s.width, s.A, true);
+    for (int l = 0; l < s.depth_vhead; ++l) add(s.width, s.width, false);
+    add(s.width, 1, true);
+    total = at;
+  }
+  int ncommon() const { return 1 + s.depth_common; }
+  int pfirst() const { return ncommon(); }                        // first layer of the policy head; its Dense(h -> A) is pfirst() + depth_phead
+  int vfirst() const { return ncommon() + s.depth_phead + 1; }    // ... of the value head; its Dense(h -> 1) is the last entry
+};
+inline int pad_to(int n, int m) { return (n + m - 1) / m * m; }
+// k_simplenet (simplenet.h, 16x16x4 MFMA): B fragments of one layer [OP/16 column tiles][KP/16 k blocks][64 lanes][4], KP = in and OP = out
+// padded to 16; component q of lane l in k block j supplies input k = 16 j + 4 q + (l >> 4) for output column 16 ct + (l & 15): the
+// lane's float4 feeds four consecutive MFMAs, whose k slots (l >> 4) together run k upwards
+inline IndexMap order_simple16(const DenseAt& d) {
+  return map5(1, pad_to(d.out, 16) / 16, pad_to(d.in, 16) / 16, 64, 4, [&](int, int ct, int j, int l, int q) { return d.at(16 * j + 4 * q + (l >> 4), 16 * ct + (l & 15)); });
+}
+// the trainer's GEMM matrix of a dense layer, k-major [in][out]
+inline IndexMap order_simple_gemm(const DenseAt& d) { return map3(1, d.in, d.out, [&](int, int i, int o) { return d.at(i, o); }); }
+// The maps behind SimpleDev: per layer the fragments, and padded to OP its bias and (with batch norm) the four batch-norm vectors
+struct SimpleMaps {
+  struct Layer { IndexMap w, b, bn[4]; };
+  std::vector<Layer> layer;
+  explicit SimpleMaps(const SimpleLayout& L) {
+    for (const DenseAt& d : L.dense) {
+      Layer m;
+      const int OP = pad_to(d.out, 16);
+      m.w = order_simple16(d);
+      m.b = order_vector(d.b, d.out, OP);
+      if (d.bn) for (int k = 0; k < 4; ++k) m.bn[k] = order_vector(d.bn_vec(k), d.out, OP);
+      layer.push_back(m);
+    }
+  }
+};
+// The optimiser step's working matrices of a dense chain, work[j] = blob[map[j]]: every dense matrix once, k-major; scat: all of them
+// carry their gradient back to the blob
+struct SimpleTrainMaps {
+  std::vector<size_t> wm;                                         // offsets in the working array, as SimpleLayout::dense
+  IndexMap map, scat;
+  explicit SimpleTrainMaps(const SimpleLayout& L) {
+    for (const DenseAt& d : L.dense) {
+      wm.push_back(map.size());
+      append(map, order_simple_gemm(d));
+    }
+    for (size_t j = 0; j < map.size(); ++j) scat.push_back((int32_t)j);
+  }
+};
+inline std::vector<unsigned char> trainable_mask(const SimpleLayout& L) {
+  std::vector<unsigned char> t(L.total, 1);
+  for (const DenseAt& d : L.dense) if (d.bn) for (int i = 0; i < 2 * d.out; ++i) t[d.bn_vec(2) + i] = 0;
   return t;
 }

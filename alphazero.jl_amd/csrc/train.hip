@@ -394,6 +394,15 @@ struct TrConv {                 // one convolution + batch norm (3x3 of the towe
   float *col, *g, *a;           // im2col input [R][taps*cin] (taps == 1: alias of the input), GEMM output, activation
   float *mean, *invstd;
 };
+// One layer of a SimpleNet engine's dense chain (net_layout.h DenseAt): g = x Wm (x = the batch's planes or layer src's activation), then
+// a = relu(bn(g)) with batch statistics, or a = relu(g + b) in place (a == g), or the head's output g + b (last)
+struct TrDense {
+  int in, out, src;             // src: the layer whose activation is this layer's input, -1 = the batch's planes
+  bool bn, last;
+  size_t off_b, off_bn, wk_wm;  // blob offsets of the bias and of (gamma, beta, mean, var); the GEMM matrix [in][out] in the working array
+  float *g, *a, *da;            // GEMM output, activation, gradient with respect to the activation (the sum over the layer's consumers)
+  float *mean, *invstd;
+};
 struct az_trainer {               // every member starts here: az_trainer_destroy takes a half-built record apart
   az_engine* e = nullptr;
   az_dataset* d = nullptr;
@@ -408,6 +417,9 @@ struct az_trainer {               // every member starts here: az_trainer_destro
   long long R = 0;
   size_t nparams = 0;
   std::vector<TrConv> convs;    // stem, block convs..., then policy-head conv, value-head conv
+  bool simple = false;          // the engine's network is a SimpleNet: `dense` is the chain, `convs` is empty
+  std::vector<TrDense> dense;   // as SimpleLayout::dense: trunk, policy head + Dense(h -> A), value head + Dense(h -> 1)
+  int ipol = 0, ival = 0;       // the two final layers in `dense`
   size_t off_pd_b = 0, off_v1_b = 0, off_v2_b = 0;                         // dense-layer biases in the blob
   size_t wk_pd = 0, wk_v1 = 0, wk_v2 = 0, nwork = 0;
   float *blob = nullptr, *gblob = nullptr, *opt_m = nullptr, *opt_v = nullptr; unsigned char* trainable = nullptr;   // [nparams]
@@ -535,6 +547,51 @@ static int trainer_build(az_trainer* t) {
   return AZ_OK;
 }
 
+// the same for a SimpleNet engine: the dense chain's layer table, the working matrices (net_layout.h SimpleTrainMaps) and buffers
+static int trainer_build_simple(az_trainer* t) {
+  const GameInfo& gi = t->gi;
+  const int B = t->B, A = gi.A, xs = gi.C * gi.P;
+  const SimpleLayout lay = simple_layout(gi, t->e->shp);
+  const SimpleTrainMaps tm(lay);
+  const std::vector<unsigned char> trainable = trainable_mask(lay);
+  const size_t wk = tm.map.size();
+  int maxc = 64;
+  for (size_t l = 0; l < lay.dense.size(); ++l) {
+    const DenseAt& at = lay.dense[l];
+    TrDense d{};
+    d.in = at.in; d.out = at.out; d.bn = at.bn; d.last = at.last;
+    d.off_b = at.b; d.off_bn = at.bnv; d.wk_wm = tm.wm[l];
+    d.src = l == 0 ? -1 : ((int)l == lay.pfirst() || (int)l == lay.vfirst()) ? lay.ncommon() - 1 : (int)l - 1;   // each head starts from the trunk
+    maxc = std::max(maxc, d.out);
+    t->dense.push_back(d);
+  }
+  t->ipol = lay.vfirst() - 1; t->ival = (int)lay.dense.size() - 1;
+  t->nwork = wk; t->nscat = (long long)tm.scat.size();
+  AZCHK(tr_alloc(t, &t->scat, tm.scat.size()));
+  AZCHK(tr_alloc(t, &t->map, wk)); AZCHK(tr_alloc(t, &t->work, wk)); AZCHK(tr_alloc(t, &t->gwork, wk, true));
+  AZCHK(tr_alloc(t, &t->blob, t->nparams)); AZCHK(tr_alloc(t, &t->gblob, t->nparams, true));
+  AZCHK(tr_alloc(t, &t->opt_m, t->nparams, true)); AZCHK(tr_alloc(t, &t->opt_v, t->nparams, true));
+  AZCHK(tr_alloc(t, &t->trainable, t->nparams));
+  HIPCHK(hipMemcpyAsync(t->scat, tm.scat.data(), sizeof(int) * tm.scat.size(), hipMemcpyHostToDevice, t->stream));
+  HIPCHK(hipMemcpyAsync(t->map, tm.map.data(), sizeof(int) * wk, hipMemcpyHostToDevice, t->stream));
+  HIPCHK(hipMemcpyAsync(t->trainable, trainable.data(), t->nparams, hipMemcpyHostToDevice, t->stream));
+  HIPCHK(hipMemcpyAsync(t->blob, t->e->blob.data(), sizeof(float) * t->nparams, hipMemcpyHostToDevice, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));                         // host vectors go out of scope
+  for (TrDense& d : t->dense) {
+    AZCHK(tr_alloc(t, &d.g, (size_t)B * d.out)); AZCHK(tr_alloc(t, &d.da, (size_t)B * d.out));
+    if (d.bn) { AZCHK(tr_alloc(t, &d.a, (size_t)B * d.out)); AZCHK(tr_alloc(t, &d.mean, d.out)); AZCHK(tr_alloc(t, &d.invstd, d.out)); }
+    else d.a = d.g;                                                 // bias and relu act in place
+  }
+  AZCHK(tr_alloc(t, &t->d_idx, B)); AZCHK(tr_alloc(t, &t->bW, B)); AZCHK(tr_alloc(t, &t->bV, B));
+  AZCHK(tr_alloc(t, &t->bX, (size_t)B * xs)); AZCHK(tr_alloc(t, &t->bA, (size_t)B * A)); AZCHK(tr_alloc(t, &t->bP, (size_t)B * A));
+  const int nchunks = (B + TR_CHUNK - 1) / TR_CHUNK;
+  AZCHK(tr_alloc(t, &t->part, (size_t)nchunks * 2 * maxc));
+  AZCHK(tr_alloc(t, &t->sums, (size_t)2 * maxc)); AZCHK(tr_alloc(t, &t->bn_mf, (size_t)2 * maxc));
+  AZCHK(tr_alloc(t, &t->fin_counter, 4, true));
+  AZCHK(tr_alloc(t, &t->terms, (size_t)4 * B)); AZCHK(tr_alloc(t, &t->bsums, 8 + 1024));
+  return AZ_OK;
+}
+
 template <class Gm, int F, bool STATS, int NT> static int tr_conv16_f(az_trainer* t, const float* in, const float* frag, float* out, const float* addend, const BnIn& bn, const TrFinal& fin) {
   using T = T16<Gm, F, NT>;
   static bool attr_done = false;
@@ -602,10 +659,76 @@ static int tr_colsum(az_trainer* t, const float* x, const float* out_act, const 
   return AZ_OK;
 }
 
+// The step of a SimpleNet engine (simplenet.jl:37-64 in TRAIN mode): the dense chain on the kernels of the ResNet's step -- tr_gemm in
+// its three passes, k_tr_colsum / k_tr_colsum_final for the batch statistics (mode 0 -> TrFinal mode 1 over R = B rows: batch mean, biased
+// variance, running statistics), the batch-norm backward sums (mode 1) and the bias gradients (mode 2), k_tr_bn_apply, k_tr_bias_act,
+// k_tr_loss, k_tr_bn_bwd, k_tr_relu_bwd, k_tr_scatter.  No kernel of its own.  Same contract as tr_forward_backward.
+static int tr_forward_backward_simple(az_trainer* t, const int* idx_host, double* d_sums) {
+  const GameInfo& gi = t->gi;
+  const int A = gi.A, B = t->B, xs = gi.C * gi.P;
+  hipStream_t st = t->stream;
+  az_dataset* d = t->d;
+  float* blob = t->blob;
+  HIPCHK(hipMemcpyAsync(t->d_idx, idx_host, sizeof(int) * B, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_tr_batch, dim3(B), dim3(64), 0, st, t->d_idx, B, xs, A, d->d_W, d->d_X, d->d_A, d->d_P, d->d_V, t->bW, t->bX, t->bA, t->bP, t->bV);
+  hipLaunchKernelGGL(k_tr_gather, dim3(tr_grid((long long)t->nwork)), dim3(256), 0, st, blob, t->map, (long long)t->nwork, t->work);
+  HIPCHK(hipMemsetAsync(t->gblob, 0, sizeof(float) * t->nparams, st));
+  auto input_of = [&](const TrDense& c) -> const float* { return c.src < 0 ? t->bX : t->dense[c.src].a; };   // flatten of the planes = their memory order
+  // ---------------- forward ----------------
+  for (TrDense& c : t->dense) {
+    const long long n = (long long)B * c.out;
+    AZCHK(tr_gemm(t, false, false, B, c.out, c.in, 1.f, input_of(c), c.in, t->work + c.wk_wm, c.out, 0.f, c.g, c.out));
+    if (c.bn) {
+      // Dense's bias cancels in the batch-normalised value (the batch mean absorbs it); it moves the running mean only (TrFinal::bias)
+      TrFinal fin{}; fin.mode = 1; fin.R = B; fin.momentum = t->cfg.batch_norm_momentum; fin.bias = blob + c.off_b; fin.mean = c.mean; fin.invstd = c.invstd;
+      fin.run_mean = blob + c.off_bn + 2 * c.out; fin.run_var = blob + c.off_bn + 3 * c.out;
+      AZCHK(tr_colsum<0>(t, c.g, nullptr, nullptr, nullptr, nullptr, B, c.out, fin));
+      hipLaunchKernelGGL(k_tr_bn_apply, dim3(tr_grid(n)), dim3(256), 0, st, c.g, c.mean, c.invstd, blob + c.off_bn, blob + c.off_bn + c.out, (const float*)nullptr, n, c.out, c.a);
+    } else hipLaunchKernelGGL(k_tr_bias_act, dim3(tr_grid(n)), dim3(256), 0, st, c.g, blob + c.off_b, n, c.out, c.last ? 0 : 1);
+  }
+  TrDense& pol = t->dense[t->ipol];
+  TrDense& val = t->dense[t->ival];
+  // ---------------- loss ----------------
+  double *tw = t->terms, *tkl = t->terms + B, *tmse = t->terms + 2 * (size_t)B, *tinv = t->terms + 3 * (size_t)B;
+  hipLaunchKernelGGL(k_tr_loss, dim3(tr_grid(B)), dim3(256), 0, st, pol.g, val.g, t->bA, t->bP, t->bV, t->bW, B, A,
+                     (float)t->cfg.nonvalidity_penalty, (float)t->cfg.rewards_renormalization, 1.0f / ((float)B * d->Wmean), pol.da, val.da, tw, tkl, tmse, tinv);
+  hipLaunchKernelGGL(k_tr_sumsq, dim3(1024), dim3(256), 0, st, blob, t->trainable, (long long)t->nparams, t->bsums + 8);
+  hipLaunchKernelGGL(k_tr_step_sums, dim3(1), dim3(256), 0, st, tw, tkl, tmse, tinv, B, t->bsums + 8, 1024, d_sums);
+  // ---------------- backward ----------------
+  // The layers in reverse: every consumer of an activation comes before its producer, so da is complete when its layer's turn comes.
+  // The trunk's last activation has two consumers: the first writes its da, the second adds to it.
+  float* gw = t->gwork;
+  float* gb = t->gblob;
+  std::vector<char> written(t->dense.size(), 0);
+  for (int l = (int)t->dense.size() - 1; l >= 0; --l) {
+    TrDense& c = t->dense[l];
+    const long long n = (long long)B * c.out;
+    float* dg = c.da;                                                // becomes the gradient with respect to g in place
+    if (c.bn) {
+      TrFinal fin{}; fin.mode = 2; fin.R = B; fin.mf = t->bn_mf; fin.dgamma = gb + c.off_bn; fin.dbeta = gb + c.off_bn + c.out;
+      AZCHK(tr_colsum<1>(t, dg, c.a, c.g, c.mean, c.invstd, B, c.out, fin));
+      tr_bn_bwd(t, dg, c.a, c.g, c.mean, c.invstd, blob + c.off_bn, n, c.out, dg, nullptr);
+      // (the bias before a train-mode batch norm has gradient 0 exactly: its slot in gblob stays 0, only the L2 term moves it)
+    } else {
+      if (!c.last) hipLaunchKernelGGL(k_tr_relu_bwd, dim3(tr_grid(n)), dim3(256), 0, st, dg, c.a, n);
+      TrFinal fin{}; fin.mode = 3; fin.out0 = gb + c.off_b;
+      AZCHK(tr_colsum<2>(t, dg, nullptr, nullptr, nullptr, nullptr, B, c.out, fin));
+    }
+    AZCHK(tr_gemm(t, true, false, c.in, c.out, B, 1.f, input_of(c), c.in, dg, c.out, 0.f, gw + c.wk_wm, c.out));
+    if (c.src >= 0) {
+      AZCHK(tr_gemm(t, false, true, B, c.in, c.out, 1.f, dg, c.out, t->work + c.wk_wm, c.out, written[c.src] ? 1.f : 0.f, t->dense[c.src].da, c.in));
+      written[c.src] = 1;
+    }
+  }
+  hipLaunchKernelGGL(k_tr_scatter, dim3(tr_grid(t->nscat)), dim3(256), 0, st, gw, t->map, t->scat, t->nscat, gb);
+  return AZ_OK;
+}
+
 // forward (train mode) + loss + backward for the batch idx[0..B); the gradient of the DATA terms is left in t->gblob
 // (blob layout, L2 term not included); the step's five sums (w, kl, mse, inv, sum of squares) go to d_sums (device).
 // Nothing here waits for the GPU: idx_host must stay alive until the stream has consumed it.
 static int tr_forward_backward(az_trainer* t, const int* idx_host, double* d_sums) {
+  if (t->simple) return tr_forward_backward_simple(t, idx_host, d_sums);
   const GameInfo& gi = t->gi;
   const int F = t->F, C = gi.C, P = gi.P, A = gi.A, npf = t->npf, nvf = t->nvf, B = t->B;
   const long long R = t->R;
@@ -785,7 +908,7 @@ extern "C" int az_trainer_create(az_engine* e, az_dataset* d, const az_train_cfg
   if (!d || !cfg || !out) return fail(AZ_ERR_BAD_ARG, "NULL argument");
   *out = nullptr;
   if (cfg->struct_size != (int32_t)sizeof(az_train_cfg)) return fail(AZ_ERR_BAD_ARG, "az_train_cfg size mismatch: call az_train_cfg_init");
-  if (e->cfg.oracle != AZ_ORACLE_RESNET || !e->net_loaded) return fail(AZ_ERR_STATE, "az_net_set_params has not been called");
+  if (!oracle_is_net(e->cfg) || !e->net_loaded) return fail(AZ_ERR_STATE, "az_net_set_params has not been called");
   if (d->game != e->cfg.game || d->device != e->device) return fail(AZ_ERR_BAD_ARG, "data set and engine differ in game or device");
   if (cfg->optimiser != AZ_OPT_ADAM && cfg->optimiser != AZ_OPT_CYCLIC_NESTEROV) return fail(AZ_ERR_BAD_ARG, "unknown optimiser %d", cfg->optimiser);
   const int64_t B = std::min<int64_t>(cfg->batch_size, d->n);     // batchsize = min(params.batch_size, length(W)), learning.jl:113
@@ -796,6 +919,8 @@ extern "C" int az_trainer_create(az_engine* e, az_dataset* d, const az_train_cfg
   t->e = e; t->d = d; t->cfg = *cfg; t->game = e->cfg.game; t->device = e->device; t->gi = e->gi;
   t->B = (int)B; t->nblocks = e->cfg.num_blocks; t->F = e->cfg.num_filters; t->npf = e->cfg.num_policy_head_filters; t->nvf = e->cfg.num_value_head_filters;
   t->nA = e->gi.A; t->R = (long long)B * e->gi.P; t->nparams = e->blob.size();
+  t->simple = e->cfg.oracle == AZ_ORACLE_SIMPLENET;
+  if (t->simple) { t->nblocks = 0; t->F = e->shp.width; t->npf = t->nvf = 0; t->R = B; }   // a dense chain: one row per sample
   int st = [&]() -> int {
     // the chain of the step on a high-priority stream, the weight gradients beside it on a low-priority one
     int pr_least = 0, pr_greatest = 0;
@@ -804,7 +929,7 @@ extern "C" int az_trainer_create(az_engine* e, az_dataset* d, const az_train_cfg
     HIPCHK(hipStreamCreateWithPriority(&t->side, hipStreamNonBlocking, pr_least));
     t->gemm_ws_floats = (size_t)4 << 20;                            // 16 MB: partial tiles of the split weight-gradient reductions
     AZCHK(tr_alloc(t, &t->gemm_ws, t->gemm_ws_floats));
-    AZCHK(trainer_build(t));
+    AZCHK(t->simple ? trainer_build_simple(t) : trainer_build(t));
     return AZ_OK;
   }();
   if (st != AZ_OK) { az_trainer_destroy(t); return st; }
@@ -841,6 +966,14 @@ extern "C" int az_trainer_gradients(az_trainer* t, const int32_t* sample_idx, fl
 // entries by more than the tolerance the rest of the gradient meets.
 extern "C" int az_debug_trainer_activation(az_trainer* t, int32_t which, float* out, int64_t n) {
   TRAINER(t);
+  if (t->simple) {                                                  // a dense chain: the activation of layer `which` of SimpleLayout::dense, [batch][out]
+    if (which < 0 || which >= (int)t->dense.size()) return fail(AZ_ERR_BAD_ARG, "layer %d of %d", which, (int)t->dense.size());
+    const TrDense& c = t->dense[which];
+    if (!out || n != (int64_t)t->B * c.out) return fail(AZ_ERR_BAD_ARG, "buffer must hold %lld floats", (long long)t->B * c.out);
+    HIPCHK(hipStreamSynchronize(t->stream));
+    HIPCHK(hipMemcpy(out, c.a, sizeof(float) * (size_t)t->B * c.out, hipMemcpyDeviceToHost));
+    return AZ_OK;
+  }
   const int ntower = 1 + 2 * t->nblocks;
   const float* src = nullptr;
   int64_t want = 0;
@@ -862,7 +995,7 @@ static int tr_up(Scratch& tmp, float** p, const float* host, size_t n) {   // a 
   if (host) HIPCHK(hipMemcpy(*p, host, sizeof(float) * n, hipMemcpyHostToDevice));
   return AZ_OK;
 }
-#define TR_TOWER(t) if ((t)->nblocks < 1) return fail(AZ_ERR_BAD_ARG, "the trainer's tower has no F -> F convolution (num_blocks = 0)")
+#define TR_TOWER(t) if ((t)->simple) return fail(AZ_ERR_BAD_ARG, "the trainer of a SimpleNet engine has no convolution"); if ((t)->nblocks < 1) return fail(AZ_ERR_BAD_ARG, "the trainer's tower has no F -> F convolution (num_blocks = 0)")
 // weight gradient of a 3x3 F -> F convolution (tr_wgrad16 = k_wgrad16 + k_wgrad_reduce): a, dg = [B P][F] with row = board P + y W + x;
 // out[9][F][F] = [tap][ci][co], tap = 3 (dy + 1) + (dx + 1): sum over the rows whose neighbour (y + dy, x + dx) is on the board of a[neighbour][ci] dg[row][co]
 extern "C" int az_debug_trainer_wgrad(az_trainer* t, const float* a, const float* dg, int64_t n_in, float* out, int64_t n_out) {

@@ -83,8 +83,10 @@ typedef enum {
   AZ_ORACLE_UNIFORM = 0, /* MCTS.RandomOracle (src/mcts.jl:62-72): uniform prior, V = 0 */
   AZ_ORACLE_HASH = 1,    /* synthetic, exact: priors/value derived from the state key (tests) */
   AZ_ORACLE_RESNET = 2,  /* the two-headed ResNet (src/networks/architectures/resnet.jl) */
-  AZ_ORACLE_ROLLOUT = 3  /* MCTS.RolloutOracle (src/mcts.jl:35-60), gamma = 1 as Benchmark.MctsRollouts builds it
+  AZ_ORACLE_ROLLOUT = 3, /* MCTS.RolloutOracle (src/mcts.jl:35-60), gamma = 1 as Benchmark.MctsRollouts builds it
                             (src/benchmark.jl:141-143): uniform prior, V = outcome of one random playout */
+  AZ_ORACLE_SIMPLENET = 4 /* NetLib.SimpleNet (src/networks/architectures/simplenet.jl:37-64), the dense two-headed network of the
+                            tictactoe, ospiel_ttt and grid-world experiments: engines made by az_engine_create_simplenet only */
 } az_oracle_kind;
 
 #define AZ_MAX_ACTIONS 9
@@ -153,13 +155,31 @@ int az_abi_version(void);
 typedef enum {
   AZ_STRUCT_ENGINE_CFG = 0, AZ_STRUCT_MOVE_REC = 1, AZ_STRUCT_GAME_REC = 2, AZ_STRUCT_TRACE_BUF = 3, AZ_STRUCT_SELFPLAY_STATS = 4,
   AZ_STRUCT_SAMPLE = 5, AZ_STRUCT_DATASET_INFO = 6, AZ_STRUCT_LEARNING_STATUS = 7, AZ_STRUCT_TRAIN_CFG = 8, AZ_STRUCT_GATHER_STATS = 9,
-  AZ_STRUCT_PROF = 10, AZ_STRUCT_MINMAX_CFG = 11, AZ_STRUCT_SOLVER_CFG = 12, AZ_STRUCT_HOST_TREE_CFG = 13, AZ_STRUCT_HOST_TREE_STATS = 14
+  AZ_STRUCT_PROF = 10, AZ_STRUCT_MINMAX_CFG = 11, AZ_STRUCT_SOLVER_CFG = 12, AZ_STRUCT_HOST_TREE_CFG = 13, AZ_STRUCT_HOST_TREE_STATS = 14,
+  AZ_STRUCT_SIMPLENET_HP = 15
 } az_struct_id;
 int az_abi_struct_size(int32_t which);
 
 /* Defaults = games/connect-four/params.jl:5-30 with the 64-filter trunk. */
 int az_engine_cfg_init(az_engine_cfg* cfg);
 int az_engine_create(const az_engine_cfg* cfg, az_engine** out);
+/* SimpleNetHP (src/networks/architectures/simplenet.jl:15-22); the batch-norm momentum is az_train_cfg's. */
+typedef struct {
+  int32_t struct_size;        /* sizeof(az_simplenet_hp), set by az_simplenet_hp_init */
+  int32_t width;              /* 1 .. 256 */
+  int32_t depth_common;       /* each depth 0 .. 16 */
+  int32_t depth_phead;
+  int32_t depth_vhead;
+  int32_t use_batch_norm;     /* 0 or 1 */
+} az_simplenet_hp;
+/* Defaults = games/tictactoe/params.jl: width 200, depth_common 6, batch norm, head depths 1. */
+int az_simplenet_hp_init(az_simplenet_hp* hp);
+/* An engine whose oracle is a SimpleNet (cfg->oracle is taken as AZ_ORACLE_SIMPLENET, the ResNet fields of cfg are ignored, net_bf16
+ * must be 0; not for AZ_GAME_GO9_PLANES).  It serves what a ResNet engine serves -- az_net_*, az_mcts_*, az_selfplay_*, az_arena_run
+ * (num_iters_per_turn = 0 included, and against a ResNet engine), az_memory_push_engine, az_learning_status, az_comm_broadcast_params,
+ * az_host_tree_*, az_trainer_* (a dense chain; batch_norm_momentum from az_train_cfg).  az_engine_create with AZ_ORACLE_SIMPLENET fails
+ * and names this constructor. */
+int az_engine_create_simplenet(const az_engine_cfg* cfg, const az_simplenet_hp* hp, az_engine** out);
 int az_engine_destroy(az_engine* e);
 /* Device memory the engine holds (node pools, tables, network buffers, the phase buffer): a host that keeps engines alive
  * between phases (the reference rebuilds its MCTS.Env per phase, src/simulations.jl:216-218) budgets with it. */

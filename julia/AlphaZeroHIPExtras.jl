@@ -297,5 +297,7 @@ const UNBOUND = Dict(
   :az_host_tree_advance => "see az_host_tree_cfg_init",
   :az_host_tree_reset => "see az_host_tree_cfg_init; MCTS.reset!",
   :az_host_tree_get_stats => "see az_host_tree_cfg_init",
+  :az_simplenet_hp_init => "NetLib.SimpleNet engines (simplenet.jl:15-64): the glue builds ResNet engines only; az_simplenet_hp mirrors SimpleNetHP field by field when a SimpleNet constructor is added here",
+  :az_engine_create_simplenet => "see az_simplenet_hp_init; every other entry point takes the engine it returns unchanged",
 )
 
