@@ -16,6 +16,10 @@
 // dlopen'ed rocBLAS for the small GEMMs).  The fused inference tower is untouched: after training the new
 // parameters go back through az_net_set_params.
 //
+// One step for both networks: trainer_build writes a network down as a table of GEMM layers (TrLayer) -- a ResNet as stem, tower, the two
+// 1x1 head convolutions and the three dense head layers, a SimpleNet as its dense chain -- and tr_forward_backward walks that table:
+// gemm_layer_forward / gemm_layer_backward for every layer but the tower's F -> F convolutions, which keep their explicit MFMA block.
+//
 #include "engine.h"
 
 // ------------------------------------------------------------------------------------------ small GEMMs
@@ -385,22 +389,24 @@ __global__ void k_tr_sumsq(const float* __restrict__ w, const unsigned char* __r
 }
 
 // ------------------------------------------------------------------------------------------ host
-struct TrConv {                 // one convolution + batch norm (3x3 of the tower, or a 1x1 head convolution)
-  int cin, cout, taps;
+// One layer of a trainer's table: g = x Wm over `rows` rows (R = batch x positions for a convolution, the batch for a dense layer: the rows
+// of one board are contiguous, so [R][nf] is [B][P nf] with k = p nf + f), then a = relu(bn(g) (+ skip's activation)) with batch statistics,
+// or a = relu(g + b) in place (a == g), or a head's output g + b (no relu).  A convolution of the blob (net_layout.h ConvAt) or a Dense
+// (+ BatchNorm) of it (the ResNet's pd / v1 / v2, DenseAt of a SimpleNet).
+enum TrInput { TR_PLAIN,        // x = the activation of layer src as it lies (a 1x1 convolution, a dense layer; src = -1: the flattened planes)
+               TR_IM2COL,       // x = col, the 3x3 neighbourhoods of the batch's planes (the stem: K = 9 C, im2col + GEMM)
+               TR_MFMA };       // a tower F -> F convolution: forward and data gradient on k_conv16_layer, weight gradient on k_wgrad16
+struct TrLayer {
+  long long rows; int in, out, src;   // src: the layer whose activation is this layer's input, -1 = the batch's planes
+  TrInput input;
+  bool bn, relu;
+  int skip;                     // the tower's second convolutions: the layer whose activation joins before the relu (the block input), else -1
+  bool act_next;                // a is written by the next layer's convolution on its way in (BnIn), not by a launch of this layer
   size_t off_b, off_bn;         // blob offsets: bias, (gamma, beta, mean, var)
-  size_t wk_wm;                 // offset in the working-parameter array: GEMM matrix [taps*cin][cout]
-  size_t wk_ffwd, wk_fdg;       // tower convolutions F -> F: MFMA fragments of k_conv16_layer for forward / data gradient
-  bool mfma;                    // forward and data gradient on k_conv16_layer instead of im2col + GEMM
-  float *col, *g, *a;           // im2col input [R][taps*cin] (taps == 1: alias of the input), GEMM output, activation
-  float *mean, *invstd;
-};
-// One layer of a SimpleNet engine's dense chain (net_layout.h DenseAt): g = x Wm (x = the batch's planes or layer src's activation), then
-// a = relu(bn(g)) with batch statistics, or a = relu(g + b) in place (a == g), or the head's output g + b (last)
-struct TrDense {
-  int in, out, src;             // src: the layer whose activation is this layer's input, -1 = the batch's planes
-  bool bn, last;
-  size_t off_b, off_bn, wk_wm;  // blob offsets of the bias and of (gamma, beta, mean, var); the GEMM matrix [in][out] in the working array
-  float *g, *a, *da;            // GEMM output, activation, gradient with respect to the activation (the sum over the layer's consumers)
+  size_t wk_wm;                 // offset in the working-parameter array: GEMM matrix [in][out]
+  size_t wk_ffwd, wk_fdg;       // TR_MFMA: fragments of k_conv16_layer for forward / data gradient
+  float *col, *g, *a, *da;      // im2col input [rows][in] (TR_IM2COL), GEMM output, activation, gradient with respect to the activation (the sum
+                                // over the layer's consumers; becomes the gradient with respect to g in place)
   float *mean, *invstd;
 };
 struct az_trainer {               // every member starts here: az_trainer_destroy takes a half-built record apart
@@ -413,21 +419,19 @@ struct az_trainer {               // every member starts here: az_trainer_destro
   hipStream_t side = nullptr;                                                // the weight gradients of the tower run here, beside the batch-norm backward passes of the next layer
   std::vector<hipEvent_t> ev_dg, ev_wg;                                     // per tower layer: output gradient ready / weight gradient done
   float* gemm_ws = nullptr; size_t gemm_ws_floats = 0;                       // split-reduction workspace of gemm_f32
-  int B = 0, nblocks = 0, F = 0, npf = 0, nvf = 0, nA = 0;
-  long long R = 0;
+  int B = 0, F = 0;
+  long long R = 0;              // rows of a tower layer: batch x positions
   size_t nparams = 0;
-  std::vector<TrConv> convs;    // stem, block convs..., then policy-head conv, value-head conv
-  bool simple = false;          // the engine's network is a SimpleNet: `dense` is the chain, `convs` is empty
-  std::vector<TrDense> dense;   // as SimpleLayout::dense: trunk, policy head + Dense(h -> A), value head + Dense(h -> 1)
-  int ipol = 0, ival = 0;       // the two final layers in `dense`
-  size_t off_pd_b = 0, off_v1_b = 0, off_v2_b = 0;                         // dense-layer biases in the blob
-  size_t wk_pd = 0, wk_v1 = 0, wk_v2 = 0, nwork = 0;
+  // ResNet: stem, 2 num_blocks tower layers, policy-head conv, value-head conv, pd, v1, v2.  SimpleNet: as SimpleLayout::dense (trunk, policy
+  // head + Dense(h -> A), value head + Dense(h -> 1)).  Every layer comes after the layer it reads.
+  std::vector<TrLayer> layers;
+  int ntower = 0;               // the stem and the TR_MFMA layers at the front of the table; 0: a dense chain, the table has no convolution
+  int ipol = 0, ival = 0;       // the layers whose g are the policy logits and the value pre-activation
+  size_t nwork = 0;
   float *blob = nullptr, *gblob = nullptr, *opt_m = nullptr, *opt_v = nullptr; unsigned char* trainable = nullptr;   // [nparams]
   int* scat = nullptr; long long nscat = 0;                                  // working entries that carry a gradient (the primary ranges)
   float *work = nullptr, *gwork = nullptr; int* map = nullptr;               // working parameters and their blob map
-  // batch + head buffers
-  int* d_idx = nullptr; float *bW = nullptr, *bX = nullptr, *bA = nullptr, *bP = nullptr, *bV = nullptr;
-  float *logits = nullptr, *v1 = nullptr, *tpre = nullptr, *dlogits = nullptr, *dt = nullptr, *dv1 = nullptr;
+  int* d_idx = nullptr; float *bW = nullptr, *bX = nullptr, *bA = nullptr, *bP = nullptr, *bV = nullptr;   // the batch
   float *dact = nullptr, *dact2 = nullptr, *dact3 = nullptr, *dcol = nullptr;   // [R][F] gradients (dcol / dact / dact3 take turns as the running gradient, dact2 = the skip share)
   float* wg_part = nullptr; int wg_splits = 0, wg_bpw = 0;       // k_wgrad16: partial dW per row split, boards per workgroup
   double *part = nullptr, *sums = nullptr, *terms = nullptr, *bsums = nullptr;
@@ -474,69 +478,82 @@ extern "C" int az_trainer_destroy(az_trainer* t) {
   return AZ_OK;
 }
 
-// builds layer tables, parameter maps and buffers
-static int trainer_build(az_trainer* t) {
-  const GameInfo& gi = t->gi;
-  const int F = t->F, C = gi.C, P = gi.P, A = gi.A;
-  const long long R = t->R;
-  const NetLayout lay = net_layout(gi, t->e->cfg);
-  const TrainMaps tm(lay);                                            // net_layout.h: the working parameters and where each comes from
-  const IndexMap &map = tm.map, &scat = tm.scat;
-  const std::vector<unsigned char> trainable = trainable_mask(lay);
+// the parameter arrays: the blob with its gradient, the optimiser's state and the trainable mask; the working parameters with their blob map
+// (net_layout.h: work[j] = blob[map[j]]) and the working entries that carry a gradient back (scat)
+static int tr_upload_params(az_trainer* t, const IndexMap& map, const IndexMap& scat, const std::vector<unsigned char>& trainable) {
   const size_t wk = map.size();
-  // tr_forward_backward takes the input of every MFMA layer from the layer below (bn_of(l - 1)) and the stem's from the batch's planes:
-  // the stem is the one non-MFMA tower layer, whatever its plane count.
-  for (size_t l = 0; l < lay.conv.size(); ++l) {
-    const ConvAt& at = lay.conv[l];
-    TrConv c{};
-    c.cin = at.cin; c.cout = at.cout; c.taps = at.taps();
-    c.off_b = at.b; c.off_bn = at.bn;
-    c.wk_wm = tm.conv[l].wm; c.wk_ffwd = tm.conv[l].ffwd; c.wk_fdg = tm.conv[l].fdg;
-    c.mfma = l >= 1 && (int)l <= lay.ntower();                       // the tower's F -> F convolutions (F = 64 or 128: az_engine_create): MFMA layer kernels
-    t->convs.push_back(c);
-  }
-  t->off_pd_b = lay.pd_b; t->off_v1_b = lay.v1_b; t->off_v2_b = lay.v2_b;
-  t->wk_pd = tm.pd; t->wk_v1 = tm.v1; t->wk_v2 = tm.v2; t->nwork = wk;
-  t->nscat = (long long)scat.size();
+  t->nwork = wk; t->nscat = (long long)scat.size();
   AZCHK(tr_alloc(t, &t->scat, scat.size()));
-  HIPCHK(hipMemcpyAsync(t->scat, scat.data(), sizeof(int) * scat.size(), hipMemcpyHostToDevice, t->stream));
   AZCHK(tr_alloc(t, &t->map, wk)); AZCHK(tr_alloc(t, &t->work, wk)); AZCHK(tr_alloc(t, &t->gwork, wk, true));
   AZCHK(tr_alloc(t, &t->blob, t->nparams)); AZCHK(tr_alloc(t, &t->gblob, t->nparams, true));
   AZCHK(tr_alloc(t, &t->opt_m, t->nparams, true)); AZCHK(tr_alloc(t, &t->opt_v, t->nparams, true));
   AZCHK(tr_alloc(t, &t->trainable, t->nparams));
+  HIPCHK(hipMemcpyAsync(t->scat, scat.data(), sizeof(int) * scat.size(), hipMemcpyHostToDevice, t->stream));
   HIPCHK(hipMemcpyAsync(t->map, map.data(), sizeof(int) * wk, hipMemcpyHostToDevice, t->stream));
   HIPCHK(hipMemcpyAsync(t->trainable, trainable.data(), t->nparams, hipMemcpyHostToDevice, t->stream));
   HIPCHK(hipMemcpyAsync(t->blob, t->e->blob.data(), sizeof(float) * t->nparams, hipMemcpyHostToDevice, t->stream));
-  HIPCHK(hipStreamSynchronize(t->stream));                         // host vectors go out of scope
-  // activations
-  const int ntower = 1 + 2 * t->nblocks;
-  for (size_t l = 0; l < t->convs.size(); ++l) {
-    TrConv& c = t->convs[l];
-    if (c.taps == 9 && !c.mfma) AZCHK(tr_alloc(t, &c.col, (size_t)R * 9 * c.cin)); else c.col = nullptr;   // the stem's im2col (K = 9 C)
-    AZCHK(tr_alloc(t, &c.g, (size_t)R * c.cout)); AZCHK(tr_alloc(t, &c.a, (size_t)R * c.cout));
-    AZCHK(tr_alloc(t, &c.mean, c.cout)); AZCHK(tr_alloc(t, &c.invstd, c.cout));
-  }
-  for (int l = 0; l < ntower; ++l) {
-    hipEvent_t a = nullptr, b = nullptr;
-    HIPCHK(hipEventCreateWithFlags(&a, hipEventDisableTiming)); t->ev_dg.push_back(a);
-    HIPCHK(hipEventCreateWithFlags(&b, hipEventDisableTiming)); t->ev_wg.push_back(b);
-  }
-  const int B = t->B;
-  AZCHK(tr_alloc(t, &t->d_idx, B)); AZCHK(tr_alloc(t, &t->bW, B)); AZCHK(tr_alloc(t, &t->bV, B));
-  AZCHK(tr_alloc(t, &t->bX, (size_t)B * C * P)); AZCHK(tr_alloc(t, &t->bA, (size_t)B * A)); AZCHK(tr_alloc(t, &t->bP, (size_t)B * A));
-  AZCHK(tr_alloc(t, &t->logits, (size_t)B * A)); AZCHK(tr_alloc(t, &t->dlogits, (size_t)B * A));
-  AZCHK(tr_alloc(t, &t->v1, (size_t)B * F)); AZCHK(tr_alloc(t, &t->dv1, (size_t)B * F));
-  AZCHK(tr_alloc(t, &t->tpre, B)); AZCHK(tr_alloc(t, &t->dt, B));
-  AZCHK(tr_alloc(t, &t->dact, (size_t)R * F)); AZCHK(tr_alloc(t, &t->dact2, (size_t)R * F)); AZCHK(tr_alloc(t, &t->dact3, (size_t)R * F)); AZCHK(tr_alloc(t, &t->dcol, (size_t)R * F));
-  const int nchunks = (int)((R + TR_CHUNK - 1) / TR_CHUNK);
-  AZCHK(tr_alloc(t, &t->part, (size_t)std::max(nchunks, B + 1) * 2 * std::max(F, 64)));   // chunks of k_tr_colsum or workgroups of k_conv16_layer
-  AZCHK(tr_alloc(t, &t->sums, (size_t)2 * std::max({F, 64, A}))); AZCHK(tr_alloc(t, &t->bn_mf, (size_t)2 * std::max(F, 64)));   // sums: also the policy bias gradient, A columns (82 on a 9x9 board)
-  AZCHK(tr_alloc(t, &t->fin_counter, 4, true));                       // tr_finish: workgroups done (every launch leaves it at zero)
-  AZCHK(tr_alloc(t, &t->terms, (size_t)4 * B)); AZCHK(tr_alloc(t, &t->bsums, 8 + 1024));
-  // k_wgrad16: one round of workgroups over the chip
-  t->wg_part = nullptr; t->wg_splits = 0; t->wg_bpw = 0;
-  {
-    const int tg = F == 128 ? 3 : 1, per_cu = 1;                    // 82 KB (64 filters) / 145 KB (128) of LDS: one workgroup per CU either way
+  HIPCHK(hipStreamSynchronize(t->stream));                         // the host vectors go out of scope
+  return AZ_OK;
+}
+
+// builds the layer table, the parameter maps and the buffers
+static int trainer_build(az_trainer* t) {
+  const GameInfo& gi = t->gi;
+  const int B = t->B, F = t->F, A = gi.A, P = gi.P;
+  const long long R = t->R;
+  auto add = [&](long long rows, int in, int out, int src, TrInput input, bool bn, bool relu, size_t off_b, size_t off_bn, size_t wk_wm) -> TrLayer& {
+    TrLayer c{};
+    c.rows = rows; c.in = in; c.out = out; c.src = src; c.input = input; c.bn = bn; c.relu = relu; c.skip = -1;
+    c.off_b = off_b; c.off_bn = off_bn; c.wk_wm = wk_wm;
+    t->layers.push_back(c);
+    return t->layers.back();
+  };
+  if (t->e->cfg.oracle == AZ_ORACLE_SIMPLENET) {                     // the dense chain and its working matrices (net_layout.h SimpleTrainMaps)
+    const SimpleLayout lay = simple_layout(gi, t->e->shp);
+    const SimpleTrainMaps tm(lay);
+    for (size_t l = 0; l < lay.dense.size(); ++l) {
+      const DenseAt& at = lay.dense[l];
+      const int src = l == 0 ? -1 : ((int)l == lay.pfirst() || (int)l == lay.vfirst()) ? lay.ncommon() - 1 : (int)l - 1;   // each head starts from the trunk
+      add(B, at.in, at.out, src, TR_PLAIN, at.bn, !at.last, at.b, at.bnv, tm.wm[l]);
+    }
+    t->ipol = lay.vfirst() - 1; t->ival = (int)lay.dense.size() - 1;
+    AZCHK(tr_upload_params(t, tm.map, tm.scat, trainable_mask(lay)));
+  } else {
+    const NetLayout lay = net_layout(gi, t->e->cfg);
+    const TrainMaps tm(lay);                                          // net_layout.h: the working parameters and where each comes from
+    const int ntower = 1 + lay.ntower(), hp = ntower, hv = ntower + 1;
+    t->ntower = ntower;
+    // tr_forward_backward takes the input of every MFMA layer from the layer below (tr_bn_in) and the stem's from the batch's planes:
+    // the stem is the one non-MFMA tower layer, whatever its plane count.
+    for (int l = 0; l < (int)lay.conv.size(); ++l) {
+      const ConvAt& at = lay.conv[l];
+      const bool tower = l >= 1 && l < ntower;                       // the tower's F -> F convolutions (F = 64 or 128: az_engine_create): MFMA layer kernels
+      TrLayer& c = add(R, at.taps() * at.cin, at.cout, l == 0 ? -1 : tower ? l - 1 : ntower - 1, l == 0 ? TR_IM2COL : tower ? TR_MFMA : TR_PLAIN, true, true,
+                       at.b, at.bn, tm.conv[l].wm);
+      c.wk_ffwd = tm.conv[l].ffwd; c.wk_fdg = tm.conv[l].fdg;
+      if (tower && l % 2 == 0) c.skip = l - 2;                       // conv2 of a block: skip connection from the block input
+      c.act_next = l + 1 < ntower;
+    }
+    add(B, P * lay.s.npf, A, hp, TR_PLAIN, false, false, lay.pd_b, 0, tm.pd);
+    add(B, P * lay.s.nvf, F, hv, TR_PLAIN, false, true, lay.v1_b, 0, tm.v1);
+    add(B, F, 1, hv + 2, TR_PLAIN, false, false, lay.v2_b, 0, tm.v2);
+    t->ipol = hv + 1; t->ival = hv + 3;
+    AZCHK(tr_upload_params(t, tm.map, tm.scat, trainable_mask(lay)));
+    // The gradients of the convolutions share four [R][F] buffers.  The running gradient of the tower moves through a ring of three, from the
+    // trunk (where both head convolutions leave their share) down: the MFMA data-gradient convolution writes out of place (see the tower
+    // block of tr_forward_backward for why three).  The head convolutions' own gradients, [R][npf] and [R][nvf], lie in dact and dact2 until
+    // the tower's backward pass starts; from then on dact2 is the skip share.
+    AZCHK(tr_alloc(t, &t->dact, (size_t)R * F)); AZCHK(tr_alloc(t, &t->dact2, (size_t)R * F)); AZCHK(tr_alloc(t, &t->dact3, (size_t)R * F)); AZCHK(tr_alloc(t, &t->dcol, (size_t)R * F));
+    float* ring[3] = {t->dcol, t->dact, t->dact3};
+    for (int l = 0; l < ntower; ++l) t->layers[l].da = ring[(ntower - 1 - l) % 3];
+    t->layers[hp].da = t->dact; t->layers[hv].da = t->dact2;
+    for (int l = 0; l < ntower; ++l) {
+      hipEvent_t a = nullptr, b = nullptr;
+      HIPCHK(hipEventCreateWithFlags(&a, hipEventDisableTiming)); t->ev_dg.push_back(a);
+      HIPCHK(hipEventCreateWithFlags(&b, hipEventDisableTiming)); t->ev_wg.push_back(b);
+    }
+    // k_wgrad16: one round of workgroups over the chip
+    const int tg = F == 128 ? 3 : 1, per_cu = 1;                      // 82 KB (64 filters) / 145 KB (128) of LDS: one workgroup per CU either way
     // as many workgroups per tap group as the chip holds (one round), the boards spread evenly over them: 1024 boards at
     // 128 filters = 85 workgroups x 3 tap groups with 12 or 13 boards each (whole 3-board LDS chunks per workgroup made it
     // 69 x 3 workgroups with 15 boards: a fifth of the CUs idle and a fifth chunk for everyone)
@@ -544,50 +561,28 @@ static int trainer_build(az_trainer* t) {
     t->wg_bpw = (B + t->wg_splits - 1) / t->wg_splits;
     AZCHK(tr_alloc(t, &t->wg_part, (size_t)t->wg_splits * 9 * F * F));
   }
-  return AZ_OK;
-}
-
-// the same for a SimpleNet engine: the dense chain's layer table, the working matrices (net_layout.h SimpleTrainMaps) and buffers
-static int trainer_build_simple(az_trainer* t) {
-  const GameInfo& gi = t->gi;
-  const int B = t->B, A = gi.A, xs = gi.C * gi.P;
-  const SimpleLayout lay = simple_layout(gi, t->e->shp);
-  const SimpleTrainMaps tm(lay);
-  const std::vector<unsigned char> trainable = trainable_mask(lay);
-  const size_t wk = tm.map.size();
-  int maxc = 64;
-  for (size_t l = 0; l < lay.dense.size(); ++l) {
-    const DenseAt& at = lay.dense[l];
-    TrDense d{};
-    d.in = at.in; d.out = at.out; d.bn = at.bn; d.last = at.last;
-    d.off_b = at.b; d.off_bn = at.bnv; d.wk_wm = tm.wm[l];
-    d.src = l == 0 ? -1 : ((int)l == lay.pfirst() || (int)l == lay.vfirst()) ? lay.ncommon() - 1 : (int)l - 1;   // each head starts from the trunk
-    maxc = std::max(maxc, d.out);
-    t->dense.push_back(d);
-  }
-  t->ipol = lay.vfirst() - 1; t->ival = (int)lay.dense.size() - 1;
-  t->nwork = wk; t->nscat = (long long)tm.scat.size();
-  AZCHK(tr_alloc(t, &t->scat, tm.scat.size()));
-  AZCHK(tr_alloc(t, &t->map, wk)); AZCHK(tr_alloc(t, &t->work, wk)); AZCHK(tr_alloc(t, &t->gwork, wk, true));
-  AZCHK(tr_alloc(t, &t->blob, t->nparams)); AZCHK(tr_alloc(t, &t->gblob, t->nparams, true));
-  AZCHK(tr_alloc(t, &t->opt_m, t->nparams, true)); AZCHK(tr_alloc(t, &t->opt_v, t->nparams, true));
-  AZCHK(tr_alloc(t, &t->trainable, t->nparams));
-  HIPCHK(hipMemcpyAsync(t->scat, tm.scat.data(), sizeof(int) * tm.scat.size(), hipMemcpyHostToDevice, t->stream));
-  HIPCHK(hipMemcpyAsync(t->map, tm.map.data(), sizeof(int) * wk, hipMemcpyHostToDevice, t->stream));
-  HIPCHK(hipMemcpyAsync(t->trainable, trainable.data(), t->nparams, hipMemcpyHostToDevice, t->stream));
-  HIPCHK(hipMemcpyAsync(t->blob, t->e->blob.data(), sizeof(float) * t->nparams, hipMemcpyHostToDevice, t->stream));
-  HIPCHK(hipStreamSynchronize(t->stream));                         // host vectors go out of scope
-  for (TrDense& d : t->dense) {
-    AZCHK(tr_alloc(t, &d.g, (size_t)B * d.out)); AZCHK(tr_alloc(t, &d.da, (size_t)B * d.out));
-    if (d.bn) { AZCHK(tr_alloc(t, &d.a, (size_t)B * d.out)); AZCHK(tr_alloc(t, &d.mean, d.out)); AZCHK(tr_alloc(t, &d.invstd, d.out)); }
-    else d.a = d.g;                                                 // bias and relu act in place
+  // per layer: its buffers, and what it asks of the scratch the column sums share: part [partials][2][columns]; sums [2][the widest column
+  // sum] (also the policy bias gradient, A columns: 82 on a 9x9 board); bn_mf [2][the widest hidden layer] (those can carry a batch norm)
+  size_t npart = 0;
+  int wsum = 64, wbn = 64;
+  for (TrLayer& c : t->layers) {
+    const size_t n = (size_t)c.rows * c.out;
+    if (c.input == TR_IM2COL) AZCHK(tr_alloc(t, &c.col, (size_t)c.rows * c.in));
+    AZCHK(tr_alloc(t, &c.g, n));
+    if (c.bn) { AZCHK(tr_alloc(t, &c.a, n)); AZCHK(tr_alloc(t, &c.mean, c.out)); AZCHK(tr_alloc(t, &c.invstd, c.out)); }
+    else c.a = c.g;                                                   // bias and relu act in place
+    if (!c.da) AZCHK(tr_alloc(t, &c.da, n));                          // (a ResNet's convolutions: the shared buffers above)
+    long long parts = (c.rows + TR_CHUNK - 1) / TR_CHUNK;            // chunks of k_tr_colsum ...
+    if (c.input != TR_PLAIN) parts = std::max<long long>(parts, B + 1);   // ... or workgroups of k_conv16_layer (the stem alike: the scratch does not depend on the depth)
+    npart = std::max(npart, (size_t)parts * 2 * std::max(c.out, 64));
+    wsum = std::max(wsum, c.out);
+    if (c.relu) wbn = std::max(wbn, c.out);
   }
   AZCHK(tr_alloc(t, &t->d_idx, B)); AZCHK(tr_alloc(t, &t->bW, B)); AZCHK(tr_alloc(t, &t->bV, B));
-  AZCHK(tr_alloc(t, &t->bX, (size_t)B * xs)); AZCHK(tr_alloc(t, &t->bA, (size_t)B * A)); AZCHK(tr_alloc(t, &t->bP, (size_t)B * A));
-  const int nchunks = (B + TR_CHUNK - 1) / TR_CHUNK;
-  AZCHK(tr_alloc(t, &t->part, (size_t)nchunks * 2 * maxc));
-  AZCHK(tr_alloc(t, &t->sums, (size_t)2 * maxc)); AZCHK(tr_alloc(t, &t->bn_mf, (size_t)2 * maxc));
-  AZCHK(tr_alloc(t, &t->fin_counter, 4, true));
+  AZCHK(tr_alloc(t, &t->bX, (size_t)B * gi.C * P)); AZCHK(tr_alloc(t, &t->bA, (size_t)B * A)); AZCHK(tr_alloc(t, &t->bP, (size_t)B * A));
+  AZCHK(tr_alloc(t, &t->part, npart));
+  AZCHK(tr_alloc(t, &t->sums, (size_t)2 * wsum)); AZCHK(tr_alloc(t, &t->bn_mf, (size_t)2 * wbn));
+  AZCHK(tr_alloc(t, &t->fin_counter, 4, true));                       // tr_finish: workgroups done (every launch leaves it at zero)
   AZCHK(tr_alloc(t, &t->terms, (size_t)4 * B)); AZCHK(tr_alloc(t, &t->bsums, 8 + 1024));
   return AZ_OK;
 }
@@ -659,218 +654,145 @@ static int tr_colsum(az_trainer* t, const float* x, const float* out_act, const 
   return AZ_OK;
 }
 
-// The step of a SimpleNet engine (simplenet.jl:37-64 in TRAIN mode): the dense chain on the kernels of the ResNet's step -- tr_gemm in
-// its three passes, k_tr_colsum / k_tr_colsum_final for the batch statistics (mode 0 -> TrFinal mode 1 over R = B rows: batch mean, biased
-// variance, running statistics), the batch-norm backward sums (mode 1) and the bias gradients (mode 2), k_tr_bn_apply, k_tr_bias_act,
-// k_tr_loss, k_tr_bn_bwd, k_tr_relu_bwd, k_tr_scatter.  No kernel of its own.  Same contract as tr_forward_backward.
-static int tr_forward_backward_simple(az_trainer* t, const int* idx_host, double* d_sums) {
-  const GameInfo& gi = t->gi;
-  const int A = gi.A, B = t->B, xs = gi.C * gi.P;
-  hipStream_t st = t->stream;
-  az_dataset* d = t->d;
-  float* blob = t->blob;
-  HIPCHK(hipMemcpyAsync(t->d_idx, idx_host, sizeof(int) * B, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_tr_batch, dim3(B), dim3(64), 0, st, t->d_idx, B, xs, A, d->d_W, d->d_X, d->d_A, d->d_P, d->d_V, t->bW, t->bX, t->bA, t->bP, t->bV);
-  hipLaunchKernelGGL(k_tr_gather, dim3(tr_grid((long long)t->nwork)), dim3(256), 0, st, blob, t->map, (long long)t->nwork, t->work);
-  HIPCHK(hipMemsetAsync(t->gblob, 0, sizeof(float) * t->nparams, st));
-  auto input_of = [&](const TrDense& c) -> const float* { return c.src < 0 ? t->bX : t->dense[c.src].a; };   // flatten of the planes = their memory order
-  // ---------------- forward ----------------
-  for (TrDense& c : t->dense) {
-    const long long n = (long long)B * c.out;
-    AZCHK(tr_gemm(t, false, false, B, c.out, c.in, 1.f, input_of(c), c.in, t->work + c.wk_wm, c.out, 0.f, c.g, c.out));
-    if (c.bn) {
-      // Dense's bias cancels in the batch-normalised value (the batch mean absorbs it); it moves the running mean only (TrFinal::bias)
-      TrFinal fin{}; fin.mode = 1; fin.R = B; fin.momentum = t->cfg.batch_norm_momentum; fin.bias = blob + c.off_b; fin.mean = c.mean; fin.invstd = c.invstd;
-      fin.run_mean = blob + c.off_bn + 2 * c.out; fin.run_var = blob + c.off_bn + 3 * c.out;
-      AZCHK(tr_colsum<0>(t, c.g, nullptr, nullptr, nullptr, nullptr, B, c.out, fin));
-      hipLaunchKernelGGL(k_tr_bn_apply, dim3(tr_grid(n)), dim3(256), 0, st, c.g, c.mean, c.invstd, blob + c.off_bn, blob + c.off_bn + c.out, (const float*)nullptr, n, c.out, c.a);
-    } else hipLaunchKernelGGL(k_tr_bias_act, dim3(tr_grid(n)), dim3(256), 0, st, c.g, blob + c.off_b, n, c.out, c.last ? 0 : 1);
+// what k_tr_colsum_final / tr_finish do with a layer's column sums.  Forward: (sum, sum of squares) of g over the layer's rows -> batch mean,
+// biased variance, running statistics.  The bias before a train-mode batch norm cancels in the normalised value (the batch mean absorbs
+// it); it moves the running mean only (TrFinal::bias).
+static TrFinal tr_fin_stats(const az_trainer* t, const TrLayer& c) {
+  TrFinal fin{}; fin.mode = 1; fin.R = c.rows; fin.momentum = t->cfg.batch_norm_momentum; fin.bias = t->blob + c.off_b; fin.mean = c.mean; fin.invstd = c.invstd;
+  fin.run_mean = t->blob + c.off_bn + 2 * c.out; fin.run_var = t->blob + c.off_bn + 3 * c.out;
+  return fin;
+}
+// backward: (sum dy, sum dy xhat) -> dbeta, dgamma in the gradient blob and the two means k_tr_bn_bwd subtracts (bn_mf)
+static TrFinal tr_fin_bn_bwd(const az_trainer* t, const TrLayer& c) {
+  TrFinal fin{}; fin.mode = 2; fin.R = c.rows; fin.mf = t->bn_mf; fin.dgamma = t->gblob + c.off_bn; fin.dbeta = t->gblob + c.off_bn + c.out;
+  return fin;
+}
+// what turns g into a: for the convolution above to apply on its way in (BnIn), or for tr_layer_act
+static BnIn tr_bn_in(const az_trainer* t, const TrLayer& c) {
+  return BnIn{c.g, c.mean, c.invstd, t->blob + c.off_bn, t->blob + c.off_bn + c.out, c.skip >= 0 ? t->layers[c.skip].a : nullptr, c.a};
+}
+static void tr_layer_act(az_trainer* t, const TrLayer& c) {
+  const long long n = c.rows * c.out;
+  if (c.bn) {
+    const BnIn b = tr_bn_in(t, c);
+    hipLaunchKernelGGL(k_tr_bn_apply, dim3(tr_grid(n)), dim3(256), 0, t->stream, b.g, b.mean, b.invstd, b.gamma, b.beta, b.res, n, c.out, b.a_out);
+  } else hipLaunchKernelGGL(k_tr_bias_act, dim3(tr_grid(n)), dim3(256), 0, t->stream, c.g, t->blob + c.off_b, n, c.out, c.relu ? 1 : 0);
+}
+static const float* tr_input(const az_trainer* t, const TrLayer& c) {   // TR_PLAIN on the planes: flatten = their memory order
+  return c.input == TR_IM2COL ? c.col : c.src < 0 ? t->bX : t->layers[c.src].a;
+}
+// every layer but the tower's MFMA convolutions: the GEMM, then batch statistics + k_tr_bn_apply, or k_tr_bias_act
+static int gemm_layer_forward(az_trainer* t, TrLayer& c) {
+  if (c.input == TR_IM2COL)
+    hipLaunchKernelGGL((k_tr_im2col<true>), dim3(tr_grid(c.rows * c.in)), dim3(256), 0, t->stream, t->bX, c.rows, c.in / 9, t->gi.W, t->gi.H, c.col);
+  AZCHK(tr_gemm(t, false, false, (int)c.rows, c.out, c.in, 1.f, tr_input(t, c), c.in, t->work + c.wk_wm, c.out, 0.f, c.g, c.out));
+  if (c.bn) AZCHK(tr_colsum<0>(t, c.g, nullptr, nullptr, nullptr, nullptr, c.rows, c.out, tr_fin_stats(t, c)));
+  if (!c.act_next) tr_layer_act(t, c);
+  return AZ_OK;
+}
+// ... backward: da -> dg in place (batch-norm backward with dgamma / dbeta, or the relu mask and the bias gradient), the weight gradient,
+// and the data gradient into the producer's da -- written by its first consumer, added to by a second (accumulate)
+static int gemm_layer_backward(az_trainer* t, TrLayer& c, bool accumulate) {
+  const long long n = c.rows * c.out;
+  float* dg = c.da;
+  if (c.bn) {
+    AZCHK(tr_colsum<1>(t, dg, c.a, c.g, c.mean, c.invstd, c.rows, c.out, tr_fin_bn_bwd(t, c)));
+    tr_bn_bwd(t, dg, c.a, c.g, c.mean, c.invstd, t->blob + c.off_bn, n, c.out, dg, nullptr);
+    // the bias of a layer that feeds a train-mode BatchNorm has gradient sum(dg) = gamma invstd (sum dy - R m0 - m1 sum xhat)
+    // = 0 exactly (the batch mean absorbs it): its slot in gblob stays 0 and only the L2 term moves it
+  } else {
+    if (c.relu) hipLaunchKernelGGL(k_tr_relu_bwd, dim3(tr_grid(n)), dim3(256), 0, t->stream, dg, c.a, n);
+    TrFinal fin{}; fin.mode = 3; fin.out0 = t->gblob + c.off_b;
+    AZCHK(tr_colsum<2>(t, dg, nullptr, nullptr, nullptr, nullptr, c.rows, c.out, fin));
   }
-  TrDense& pol = t->dense[t->ipol];
-  TrDense& val = t->dense[t->ival];
-  // ---------------- loss ----------------
-  double *tw = t->terms, *tkl = t->terms + B, *tmse = t->terms + 2 * (size_t)B, *tinv = t->terms + 3 * (size_t)B;
-  hipLaunchKernelGGL(k_tr_loss, dim3(tr_grid(B)), dim3(256), 0, st, pol.g, val.g, t->bA, t->bP, t->bV, t->bW, B, A,
-                     (float)t->cfg.nonvalidity_penalty, (float)t->cfg.rewards_renormalization, 1.0f / ((float)B * d->Wmean), pol.da, val.da, tw, tkl, tmse, tinv);
-  hipLaunchKernelGGL(k_tr_sumsq, dim3(1024), dim3(256), 0, st, blob, t->trainable, (long long)t->nparams, t->bsums + 8);
-  hipLaunchKernelGGL(k_tr_step_sums, dim3(1), dim3(256), 0, st, tw, tkl, tmse, tinv, B, t->bsums + 8, 1024, d_sums);
-  // ---------------- backward ----------------
-  // The layers in reverse: every consumer of an activation comes before its producer, so da is complete when its layer's turn comes.
-  // The trunk's last activation has two consumers: the first writes its da, the second adds to it.
-  float* gw = t->gwork;
-  float* gb = t->gblob;
-  std::vector<char> written(t->dense.size(), 0);
-  for (int l = (int)t->dense.size() - 1; l >= 0; --l) {
-    TrDense& c = t->dense[l];
-    const long long n = (long long)B * c.out;
-    float* dg = c.da;                                                // becomes the gradient with respect to g in place
-    if (c.bn) {
-      TrFinal fin{}; fin.mode = 2; fin.R = B; fin.mf = t->bn_mf; fin.dgamma = gb + c.off_bn; fin.dbeta = gb + c.off_bn + c.out;
-      AZCHK(tr_colsum<1>(t, dg, c.a, c.g, c.mean, c.invstd, B, c.out, fin));
-      tr_bn_bwd(t, dg, c.a, c.g, c.mean, c.invstd, blob + c.off_bn, n, c.out, dg, nullptr);
-      // (the bias before a train-mode batch norm has gradient 0 exactly: its slot in gblob stays 0, only the L2 term moves it)
-    } else {
-      if (!c.last) hipLaunchKernelGGL(k_tr_relu_bwd, dim3(tr_grid(n)), dim3(256), 0, st, dg, c.a, n);
-      TrFinal fin{}; fin.mode = 3; fin.out0 = gb + c.off_b;
-      AZCHK(tr_colsum<2>(t, dg, nullptr, nullptr, nullptr, nullptr, B, c.out, fin));
-    }
-    AZCHK(tr_gemm(t, true, false, c.in, c.out, B, 1.f, input_of(c), c.in, dg, c.out, 0.f, gw + c.wk_wm, c.out));
-    if (c.src >= 0) {
-      AZCHK(tr_gemm(t, false, true, B, c.in, c.out, 1.f, dg, c.out, t->work + c.wk_wm, c.out, written[c.src] ? 1.f : 0.f, t->dense[c.src].da, c.in));
-      written[c.src] = 1;
-    }
-  }
-  hipLaunchKernelGGL(k_tr_scatter, dim3(tr_grid(t->nscat)), dim3(256), 0, st, gw, t->map, t->scat, t->nscat, gb);
+  AZCHK(tr_gemm(t, true, false, c.in, c.out, (int)c.rows, 1.f, tr_input(t, c), c.in, dg, c.out, 0.f, t->gwork + c.wk_wm, c.out));
+  if (c.src >= 0) AZCHK(tr_gemm(t, false, true, (int)c.rows, c.in, c.out, 1.f, dg, c.out, t->work + c.wk_wm, c.out, accumulate ? 1.f : 0.f, t->layers[c.src].da, c.in));
   return AZ_OK;
 }
 
 // forward (train mode) + loss + backward for the batch idx[0..B); the gradient of the DATA terms is left in t->gblob
 // (blob layout, L2 term not included); the step's five sums (w, kl, mse, inv, sum of squares) go to d_sums (device).
 // Nothing here waits for the GPU: idx_host must stay alive until the stream has consumed it.
+// A ResNet in TRAIN mode (resnet.jl:53-92) and a SimpleNet (simplenet.jl:37-64) alike: the table says which layers there are.
 static int tr_forward_backward(az_trainer* t, const int* idx_host, double* d_sums) {
-  if (t->simple) return tr_forward_backward_simple(t, idx_host, d_sums);
   const GameInfo& gi = t->gi;
-  const int F = t->F, C = gi.C, P = gi.P, A = gi.A, npf = t->npf, nvf = t->nvf, B = t->B;
+  const int A = gi.A, B = t->B, ntower = t->ntower, nlayers = (int)t->layers.size();
   const long long R = t->R;
   hipStream_t st = t->stream;
   az_dataset* d = t->d;
-  const int ntower = 1 + 2 * t->nblocks;
-  TrConv& hp = t->convs[ntower];
-  TrConv& hv = t->convs[ntower + 1];
   float* blob = t->blob;
   HIPCHK(hipMemcpyAsync(t->d_idx, idx_host, sizeof(int) * B, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_tr_batch, dim3(B), dim3(64), 0, st, t->d_idx, B, C * P, A, d->d_W, d->d_X, d->d_A, d->d_P, d->d_V, t->bW, t->bX, t->bA, t->bP, t->bV);
+  hipLaunchKernelGGL(k_tr_batch, dim3(B), dim3(64), 0, st, t->d_idx, B, gi.C * gi.P, A, d->d_W, d->d_X, d->d_A, d->d_P, d->d_V, t->bW, t->bX, t->bA, t->bP, t->bV);
   hipLaunchKernelGGL(k_tr_gather, dim3(tr_grid((long long)t->nwork)), dim3(256), 0, st, blob, t->map, (long long)t->nwork, t->work);
   HIPCHK(hipMemsetAsync(t->gblob, 0, sizeof(float) * t->nparams, st));
   // ---------------- forward ----------------
-  // (r4) one launch per tower layer: the convolution of layer l computes its INPUT a(l-1) = relu(bn(g(l-1)) (+ skip)) while the rows
-  // go into LDS (BnIn, and writes it for the backward pass), leaves the column sums of its output and its last workgroup turns them
-  // into the layer's batch statistics (tr_finish).  Were three launches (convolution, k_tr_colsum_final, k_tr_bn_apply).
-  auto bn_of = [&](int l) {                                          // what turns g(l) into a(l)
-    TrConv& c = t->convs[l];
-    const bool second = l > 0 && (l % 2) == 0;                       // conv2 of a block: skip connection from the block input
-    return BnIn{c.g, c.mean, c.invstd, blob + c.off_bn, blob + c.off_bn + c.cout, second ? t->convs[l - 2].a : nullptr, c.a};
-  };
-  for (int l = 0; l < ntower; ++l) {
-    TrConv& c = t->convs[l];
-    TrFinal fin{}; fin.mode = 1; fin.R = R; fin.momentum = t->cfg.batch_norm_momentum; fin.bias = blob + c.off_b; fin.mean = c.mean; fin.invstd = c.invstd;
-    fin.run_mean = blob + c.off_bn + 2 * c.cout; fin.run_var = blob + c.off_bn + 3 * c.cout;
-    if (c.mfma) {
-      int nparts = 0;
-      fin.counter = t->env.fin_inside ? t->fin_counter : nullptr;
-      AZCHK(tr_conv16(t, nullptr, t->work + c.wk_ffwd, c.g, true, &nparts, nullptr, bn_of(l - 1), fin));
-      if (!fin.counter) hipLaunchKernelGGL(k_tr_colsum_final, dim3(c.cout), dim3(64), 0, st, t->part, nparts, c.cout, t->sums, fin);
-    } else {                                                          // the stem: K = 9 C, im2col + GEMM
-      hipLaunchKernelGGL((k_tr_im2col<true>), dim3(tr_grid(R * 9 * c.cin)), dim3(256), 0, st, t->bX, R, c.cin, gi.W, gi.H, c.col);
-      AZCHK(tr_gemm(t, false, false, (int)R, c.cout, 9 * c.cin, 1.f, c.col, 9 * c.cin, t->work + c.wk_wm, c.cout, 0.f, c.g, c.cout));
-      AZCHK(tr_colsum<0>(t, c.g, nullptr, nullptr, nullptr, nullptr, R, c.cout, fin));
-    }
+  for (TrLayer& c : t->layers) {
+    if (c.input != TR_MFMA) { AZCHK(gemm_layer_forward(t, c)); continue; }
+    // (r4) one launch per tower layer: the convolution of layer l computes its INPUT a(l-1) = relu(bn(g(l-1)) (+ skip)) while the rows
+    // go into LDS (BnIn, and writes it for the backward pass), leaves the column sums of its output and its last workgroup turns them
+    // into the layer's batch statistics (tr_finish).  Were three launches (convolution, k_tr_colsum_final, k_tr_bn_apply).
+    int nparts = 0;
+    TrFinal fin = tr_fin_stats(t, c);
+    fin.counter = t->env.fin_inside ? t->fin_counter : nullptr;
+    AZCHK(tr_conv16(t, nullptr, t->work + c.wk_ffwd, c.g, true, &nparts, nullptr, tr_bn_in(t, t->layers[c.src]), fin));
+    if (!fin.counter) hipLaunchKernelGGL(k_tr_colsum_final, dim3(c.out), dim3(64), 0, st, t->part, nparts, c.out, t->sums, fin);
+    if (!c.act_next) tr_layer_act(t, c);                             // the trunk: the last layer's activation has no convolution after it to ride in
   }
-  { // the trunk: the last layer's activation has no convolution after it to ride in
-    const BnIn b = bn_of(ntower - 1);
-    TrConv& c = t->convs[ntower - 1];
-    hipLaunchKernelGGL(k_tr_bn_apply, dim3(tr_grid(R * c.cout)), dim3(256), 0, st, b.g, b.mean, b.invstd, b.gamma, b.beta, b.res, R * c.cout, c.cout, c.a);
-  }
-  const float* trunk = t->convs[ntower - 1].a;
-  for (TrConv* c : {&hp, &hv}) {
-    AZCHK(tr_gemm(t, false, false, (int)R, c->cout, F, 1.f, trunk, F, t->work + c->wk_wm, c->cout, 0.f, c->g, c->cout));
-    { TrFinal fin{}; fin.mode = 1; fin.R = R; fin.momentum = t->cfg.batch_norm_momentum; fin.bias = blob + c->off_b; fin.mean = c->mean; fin.invstd = c->invstd;
-      fin.run_mean = blob + c->off_bn + 2 * c->cout; fin.run_var = blob + c->off_bn + 3 * c->cout;
-      AZCHK(tr_colsum<0>(t, c->g, nullptr, nullptr, nullptr, nullptr, R, c->cout, fin)); }
-    hipLaunchKernelGGL(k_tr_bn_apply, dim3(tr_grid(R * c->cout)), dim3(256), 0, st, c->g, c->mean, c->invstd, blob + c->off_bn, blob + c->off_bn + c->cout, (const float*)nullptr, R * c->cout, c->cout, c->a);
-  }
-  // dense heads: rows of hp.a / hv.a of one board are contiguous: [B][P*nf] with k = p*nf + f
-  AZCHK(tr_gemm(t, false, false, B, A, P * npf, 1.f, hp.a, P * npf, t->work + t->wk_pd, A, 0.f, t->logits, A));
-  hipLaunchKernelGGL(k_tr_bias_act, dim3(tr_grid((long long)B * A)), dim3(256), 0, st, t->logits, blob + t->off_pd_b, (long long)B * A, A, 0);
-  AZCHK(tr_gemm(t, false, false, B, F, P * nvf, 1.f, hv.a, P * nvf, t->work + t->wk_v1, F, 0.f, t->v1, F));
-  hipLaunchKernelGGL(k_tr_bias_act, dim3(tr_grid((long long)B * F)), dim3(256), 0, st, t->v1, blob + t->off_v1_b, (long long)B * F, F, 1);
-  AZCHK(tr_gemm(t, false, false, B, 1, F, 1.f, t->v1, F, t->work + t->wk_v2, 1, 0.f, t->tpre, 1));
-  hipLaunchKernelGGL(k_tr_bias_act, dim3(tr_grid(B)), dim3(256), 0, st, t->tpre, blob + t->off_v2_b, (long long)B, 1, 0);
+  TrLayer& pol = t->layers[t->ipol];
+  TrLayer& val = t->layers[t->ival];
   // ---------------- loss ----------------
   // mean(W)/Wmean / sum(W) = 1 / (B Wmean): the gradient scale needs no reduction first (learning.jl:88)
   double *tw = t->terms, *tkl = t->terms + B, *tmse = t->terms + 2 * (size_t)B, *tinv = t->terms + 3 * (size_t)B;
   if (A <= AZ_MAX_ACTIONS)
-    hipLaunchKernelGGL(k_tr_loss, dim3(tr_grid(B)), dim3(256), 0, st, t->logits, t->tpre, t->bA, t->bP, t->bV, t->bW, B, A,
-                       (float)t->cfg.nonvalidity_penalty, (float)t->cfg.rewards_renormalization, 1.0f / ((float)B * d->Wmean), t->dlogits, t->dt, tw, tkl, tmse, tinv);
+    hipLaunchKernelGGL(k_tr_loss, dim3(tr_grid(B)), dim3(256), 0, st, pol.g, val.g, t->bA, t->bP, t->bV, t->bW, B, A,
+                       (float)t->cfg.nonvalidity_penalty, (float)t->cfg.rewards_renormalization, 1.0f / ((float)B * d->Wmean), pol.da, val.da, tw, tkl, tmse, tinv);
   else                                                              // 64 threads per workgroup: the rows of a wavefront's samples are 4 A bytes apart, so more CUs share the strided reads
-    hipLaunchKernelGGL(k_tr_loss_wide, dim3((B + 63) / 64), dim3(64), 0, st, t->logits, t->tpre, t->bA, t->bP, t->bV, t->bW, B, A,
-                       (float)t->cfg.nonvalidity_penalty, (float)t->cfg.rewards_renormalization, 1.0f / ((float)B * d->Wmean), t->dlogits, t->dt, tw, tkl, tmse, tinv);
+    hipLaunchKernelGGL(k_tr_loss_wide, dim3((B + 63) / 64), dim3(64), 0, st, pol.g, val.g, t->bA, t->bP, t->bV, t->bW, B, A,
+                       (float)t->cfg.nonvalidity_penalty, (float)t->cfg.rewards_renormalization, 1.0f / ((float)B * d->Wmean), pol.da, val.da, tw, tkl, tmse, tinv);
   hipLaunchKernelGGL(k_tr_sumsq, dim3(1024), dim3(256), 0, st, blob, t->trainable, (long long)t->nparams, t->bsums + 8);
   hipLaunchKernelGGL(k_tr_step_sums, dim3(1), dim3(256), 0, st, tw, tkl, tmse, tinv, B, t->bsums + 8, 1024, d_sums);
-  // ---------------- backward: dense heads ----------------
+  // ---------------- backward ----------------
+  // The layers in reverse: every consumer of an activation comes before its producer, so da is complete when its layer's turn comes.
+  // The trunk's last activation has two consumers (the heads): the first writes its da, the second adds to it.
   float* gw = t->gwork;
-  float* gb = t->gblob;
-  // policy: dWpd = hp_flat^T dlogits ; dbp = colsum(dlogits) ; dhp = dlogits Wpd^T
-  AZCHK(tr_gemm(t, true, false, P * npf, A, B, 1.f, hp.a, P * npf, t->dlogits, A, 0.f, gw + t->wk_pd, A));
-  { TrFinal fin{}; fin.mode = 3; fin.out0 = gb + t->off_pd_b; AZCHK(tr_colsum<2>(t, t->dlogits, nullptr, nullptr, nullptr, nullptr, B, A, fin)); }
-  float* dhp = t->dact;                                            // [R][npf]
-  AZCHK(tr_gemm(t, false, true, B, P * npf, A, 1.f, t->dlogits, A, t->work + t->wk_pd, A, 0.f, dhp, P * npf));
-  // value: dt -> dv1 = (dt wv2^T) .* (v1 > 0) ; dwv2 = v1^T dt ; db2 = sum dt ; dWv1 = hv_flat^T dv1 ; db1 ; dhv = dv1 Wv1^T
-  AZCHK(tr_gemm(t, true, false, F, 1, B, 1.f, t->v1, F, t->dt, 1, 0.f, gw + t->wk_v2, 1));
-  { TrFinal fin{}; fin.mode = 3; fin.out0 = gb + t->off_v2_b; AZCHK(tr_colsum<2>(t, t->dt, nullptr, nullptr, nullptr, nullptr, B, 1, fin)); }
-  AZCHK(tr_gemm(t, false, true, B, F, 1, 1.f, t->dt, 1, t->work + t->wk_v2, 1, 0.f, t->dv1, F));
-  hipLaunchKernelGGL(k_tr_relu_bwd, dim3(tr_grid((long long)B * F)), dim3(256), 0, st, t->dv1, t->v1, (long long)B * F);
-  AZCHK(tr_gemm(t, true, false, P * nvf, F, B, 1.f, hv.a, P * nvf, t->dv1, F, 0.f, gw + t->wk_v1, F));
-  { TrFinal fin{}; fin.mode = 3; fin.out0 = gb + t->off_v1_b; AZCHK(tr_colsum<2>(t, t->dv1, nullptr, nullptr, nullptr, nullptr, B, F, fin)); }
-  float* dhv = t->dact2;                                           // [R][nvf]
-  AZCHK(tr_gemm(t, false, true, B, P * nvf, F, 1.f, t->dv1, F, t->work + t->wk_v1, F, 0.f, dhv, P * nvf));
-  // head convolutions: BN backward, weight / bias gradients, gradient into the trunk
-  float* dtrunk = t->dcol;                                         // [R][F] (front of the big scratch)
-  bool first = true;
-  for (TrConv* c : {&hp, &hv}) {
-    float* dh = c == &hp ? dhp : dhv;
-    { TrFinal fin{}; fin.mode = 2; fin.R = R; fin.mf = t->bn_mf; fin.dgamma = gb + c->off_bn; fin.dbeta = gb + c->off_bn + c->cout;
-      AZCHK(tr_colsum<1>(t, dh, c->a, c->g, c->mean, c->invstd, R, c->cout, fin)); }
-    tr_bn_bwd(t, dh, c->a, c->g, c->mean, c->invstd, blob + c->off_bn, R * c->cout, c->cout, dh, nullptr);
-    AZCHK(tr_gemm(t, true, false, F, c->cout, (int)R, 1.f, trunk, F, dh, c->cout, 0.f, gw + c->wk_wm, c->cout));
-    // the bias of a convolution that feeds a train-mode BatchNorm has gradient sum(dg) = gamma invstd (sum dy - R m0 - m1 sum xhat)
-    // = 0 exactly (the batch mean absorbs it): its slot in gblob stays 0 and only the L2 term moves it
-    AZCHK(tr_gemm(t, false, true, (int)R, F, c->cout, 1.f, dh, c->cout, t->work + c->wk_wm, c->cout, first ? 0.f : 1.f, dtrunk, F));
-    first = false;
-  }
-  // ---------------- backward: tower ----------------
-  // da = gradient w.r.t. the activation convs[l].a; dskip (block input share) in dact2.  The MFMA data-gradient convolution
-  // writes out of place, so the running gradient moves through three buffers (the front of the big scratch, where the head
-  // convolutions left the trunk gradient, dact and dact3) instead of being copied.
-  // (r3) The weight gradient of a layer is off the chain dg(l) -> da(l-1) -> dg(l-1): it runs on a second stream, so the
-  // HBM-bound batch-norm backward passes of layer l-1 share the chip with the MFMA-bound k_wgrad16 of layer l.  Three
-  // buffers because the data-gradient convolution of layer l-1 must not overwrite the dg that k_wgrad16 of layer l still
-  // reads: it writes the buffer last read by the weight gradient of layer l+1 and waits for that one only.
-  float* ring[3] = {dtrunk, t->dact, t->dact3};
-  int cur = 0;
-  for (int l = ntower - 1; l >= 0; --l) {
-    TrConv& c = t->convs[l];
-    float* da = ring[cur];
-    const bool second = l > 0 && (l % 2) == 0;
-    { TrFinal fin{}; fin.mode = 2; fin.R = R; fin.mf = t->bn_mf; fin.dgamma = gb + c.off_bn; fin.dbeta = gb + c.off_bn + c.cout;
-      AZCHK(tr_colsum<1>(t, da, c.a, c.g, c.mean, c.invstd, R, c.cout, fin)); }
+  std::vector<char> written(t->layers.size(), 0);
+  for (int l = nlayers - 1; l >= 0; --l) {
+    TrLayer& c = t->layers[l];
+    if (c.input != TR_MFMA) {
+      AZCHK(gemm_layer_backward(t, c, c.src >= 0 && written[c.src]));
+      if (c.src >= 0) written[c.src] = 1;
+      continue;
+    }
+    // The tower.  da = gradient w.r.t. the activation c.a; dskip (block input share) in dact2.  The MFMA data-gradient convolution
+    // writes out of place, so the running gradient moves through three buffers (the front of the big scratch, where the head
+    // convolutions left the trunk gradient, dact and dact3: the da of the table) instead of being copied.
+    // (r3) The weight gradient of a layer is off the chain dg(l) -> da(l-1) -> dg(l-1): it runs on a second stream, so the
+    // HBM-bound batch-norm backward passes of layer l-1 share the chip with the MFMA-bound k_wgrad16 of layer l.  Three
+    // buffers because the data-gradient convolution of layer l-1 must not overwrite the dg that k_wgrad16 of layer l still
+    // reads: it writes the buffer last read by the weight gradient of layer l+1 and waits for that one only.
+    float* da = c.da;
+    AZCHK(tr_colsum<1>(t, da, c.a, c.g, c.mean, c.invstd, R, c.out, tr_fin_bn_bwd(t, c)));
     // dg overwrites da; for conv2 the masked gradient dy also flows to the block input (dact2)
-    tr_bn_bwd(t, da, c.a, c.g, c.mean, c.invstd, blob + c.off_bn, R * c.cout, c.cout, da, second ? t->dact2 : nullptr);
-    if (!c.mfma) AZCHK(tr_gemm(t, true, false, 9 * c.cin, c.cout, (int)R, 1.f, c.col, 9 * c.cin, da, c.cout, 0.f, gw + c.wk_wm, c.cout));
-    if (c.mfma && !t->env.wg_late) HIPCHK(hipEventRecord(t->ev_dg[l], st));    // dg(l) is ready: the weight gradient may start beside the data gradient
-    if (l > 0) {
-      // data gradient da_prev = conv(dg, mirrored taps, ci <-> co): the same MFMA layer kernel with the wk_fdg fragments, out of place
-      const bool first_of_block = (l % 2) == 1;                    // conv1: its input is the block input, which also gets the skip share
-      const int nxt = (cur + 1) % 3;                               // last read by the weight gradient of layer l + 2
-      if (l + 2 < ntower && t->convs[l + 2].mfma) HIPCHK(hipStreamWaitEvent(st, t->ev_wg[l + 2], 0));
-      AZCHK(tr_conv16(t, da, t->work + c.wk_fdg, ring[nxt], false, nullptr, first_of_block ? t->dact2 : nullptr));   // (r3) the add rides in the epilogue
-      cur = nxt;
-    }
-    if (c.mfma) {
-      // the weight gradient starts when the data gradient of its layer is done: two MFMA kernels side by side only halve each
-      // other's share of the chip (measured), while the HBM-bound passes of layer l-1 do fit beside k_wgrad16
-      if (t->env.wg_late) HIPCHK(hipEventRecord(t->ev_dg[l], st));
-      if (!t->env.one_stream) HIPCHK(hipStreamWaitEvent(t->side, t->ev_dg[l], 0));
-      AZCHK(tr_wgrad16(t, t->convs[l - 1].a, da, gw + c.wk_wm, t->env.one_stream ? st : t->side));
-      HIPCHK(hipEventRecord(t->ev_wg[l], t->env.one_stream ? st : t->side));
-    }
+    tr_bn_bwd(t, da, c.a, c.g, c.mean, c.invstd, blob + c.off_bn, R * c.out, c.out, da, c.skip >= 0 ? t->dact2 : nullptr);
+    if (!t->env.wg_late) HIPCHK(hipEventRecord(t->ev_dg[l], st));    // dg(l) is ready: the weight gradient may start beside the data gradient
+    // data gradient da_prev = conv(dg, mirrored taps, ci <-> co): the same MFMA layer kernel with the wk_fdg fragments, out of place
+    const bool first_of_block = (l % 2) == 1;                        // conv1: its input is the block input, which also gets the skip share
+    if (l + 2 < ntower) HIPCHK(hipStreamWaitEvent(st, t->ev_wg[l + 2], 0));   // the weight gradient that last read the buffer about to be written
+    AZCHK(tr_conv16(t, da, t->work + c.wk_fdg, t->layers[c.src].da, false, nullptr, first_of_block ? t->dact2 : nullptr));   // (r3) the add rides in the epilogue
+    // the weight gradient starts when the data gradient of its layer is done: two MFMA kernels side by side only halve each
+    // other's share of the chip (measured), while the HBM-bound passes of layer l-1 do fit beside k_wgrad16
+    if (t->env.wg_late) HIPCHK(hipEventRecord(t->ev_dg[l], st));
+    if (!t->env.one_stream) HIPCHK(hipStreamWaitEvent(t->side, t->ev_dg[l], 0));
+    AZCHK(tr_wgrad16(t, t->layers[c.src].a, da, gw + c.wk_wm, t->env.one_stream ? st : t->side));
+    HIPCHK(hipEventRecord(t->ev_wg[l], t->env.one_stream ? st : t->side));
   }
-  for (int l = 1; l < ntower && l <= 2; ++l) if (t->convs[l].mfma) HIPCHK(hipStreamWaitEvent(st, t->ev_wg[l], 0));   // the side stream is in order: its last two launches
+  for (int l = 1; l < ntower && l <= 2; ++l) HIPCHK(hipStreamWaitEvent(st, t->ev_wg[l], 0));   // the side stream is in order: its last two launches
   // working-layout weight gradients -> blob layout (the rotated copies carry no gradient of their own: their slots in
   // gwork stay zero and map to the same blob entries, so scatter only the primary ranges)
-  hipLaunchKernelGGL(k_tr_scatter, dim3(tr_grid(t->nscat)), dim3(256), 0, st, gw, t->map, t->scat, t->nscat, gb);
+  hipLaunchKernelGGL(k_tr_scatter, dim3(tr_grid(t->nscat)), dim3(256), 0, st, gw, t->map, t->scat, t->nscat, t->gblob);
   return AZ_OK;
 }
+
 // `losses` from the five sums of a step (learning.jl:67-90): L and (Lp, Lv, Lreg, Linv, mean(W)/Wmean)
 static void tr_losses(const az_trainer* t, const double* sums, float* L, float* parts) {
   const double sw = sums[0];
@@ -917,10 +839,7 @@ extern "C" int az_trainer_create(az_engine* e, az_dataset* d, const az_train_cfg
   az_trainer* t = new (std::nothrow) az_trainer();
   if (!t) return fail(AZ_ERR_HIP, "out of host memory");
   t->e = e; t->d = d; t->cfg = *cfg; t->game = e->cfg.game; t->device = e->device; t->gi = e->gi;
-  t->B = (int)B; t->nblocks = e->cfg.num_blocks; t->F = e->cfg.num_filters; t->npf = e->cfg.num_policy_head_filters; t->nvf = e->cfg.num_value_head_filters;
-  t->nA = e->gi.A; t->R = (long long)B * e->gi.P; t->nparams = e->blob.size();
-  t->simple = e->cfg.oracle == AZ_ORACLE_SIMPLENET;
-  if (t->simple) { t->nblocks = 0; t->F = e->shp.width; t->npf = t->nvf = 0; t->R = B; }   // a dense chain: one row per sample
+  t->B = (int)B; t->F = e->cfg.num_filters; t->R = (long long)B * e->gi.P; t->nparams = e->blob.size();   // (F, R: of a ResNet's tower; a dense chain has neither)
   int st = [&]() -> int {
     // the chain of the step on a high-priority stream, the weight gradients beside it on a low-priority one
     int pr_least = 0, pr_greatest = 0;
@@ -929,7 +848,7 @@ extern "C" int az_trainer_create(az_engine* e, az_dataset* d, const az_train_cfg
     HIPCHK(hipStreamCreateWithPriority(&t->side, hipStreamNonBlocking, pr_least));
     t->gemm_ws_floats = (size_t)4 << 20;                            // 16 MB: partial tiles of the split weight-gradient reductions
     AZCHK(tr_alloc(t, &t->gemm_ws, t->gemm_ws_floats));
-    AZCHK(t->simple ? trainer_build_simple(t) : trainer_build(t));
+    AZCHK(trainer_build(t));
     return AZ_OK;
   }();
   if (st != AZ_OK) { az_trainer_destroy(t); return st; }
@@ -961,28 +880,19 @@ extern "C" int az_trainer_gradients(az_trainer* t, const int32_t* sample_idx, fl
 
 // debug aid (not part of the ABI in azhip.h): the post-ReLU activation the last forward pass left for layer `which` -- tower
 // layers 0 .. 2 num_blocks ([R][F], R = batch x positions), then the policy / value head convolutions ([R][npf], [R][nvf]), then
-// the value head's first dense layer ([batch][F]).  tests/test_train_gpu.py reads the ReLU masks (a > 0) off them: an fp32 chain
+// the value head's first dense layer ([batch][F]); of a dense chain, layer `which` of SimpleLayout::dense ([batch][out]).  tests/test_train_gpu.py reads the ReLU masks (a > 0) off them: an fp32 chain
 // and an fp64 reference disagree on activations within rounding of zero, and ONE flipped unit moves single weight-gradient
 // entries by more than the tolerance the rest of the gradient meets.
 extern "C" int az_debug_trainer_activation(az_trainer* t, int32_t which, float* out, int64_t n) {
   TRAINER(t);
-  if (t->simple) {                                                  // a dense chain: the activation of layer `which` of SimpleLayout::dense, [batch][out]
-    if (which < 0 || which >= (int)t->dense.size()) return fail(AZ_ERR_BAD_ARG, "layer %d of %d", which, (int)t->dense.size());
-    const TrDense& c = t->dense[which];
-    if (!out || n != (int64_t)t->B * c.out) return fail(AZ_ERR_BAD_ARG, "buffer must hold %lld floats", (long long)t->B * c.out);
-    HIPCHK(hipStreamSynchronize(t->stream));
-    HIPCHK(hipMemcpy(out, c.a, sizeof(float) * (size_t)t->B * c.out, hipMemcpyDeviceToHost));
-    return AZ_OK;
-  }
-  const int ntower = 1 + 2 * t->nblocks;
-  const float* src = nullptr;
-  int64_t want = 0;
-  if (which >= 0 && which < ntower + 2) { src = t->convs[which].a; want = (int64_t)t->R * t->convs[which].cout; }
-  else if (which == ntower + 2) { src = t->v1; want = (int64_t)t->B * t->F; }
-  else return fail(AZ_ERR_BAD_ARG, "layer %d of %d", which, ntower + 3);
+  // an index into the table, but for a ResNet's last one: the table holds the policy head's dense layer before the value head's
+  const int nact = t->ntower ? t->ntower + 3 : (int)t->layers.size();
+  if (which < 0 || which >= nact) return fail(AZ_ERR_BAD_ARG, "layer %d of %d", which, nact);
+  const TrLayer& c = t->layers[t->ntower && which == t->ntower + 2 ? t->ival - 1 : which];
+  const int64_t want = (int64_t)c.rows * c.out;
   if (!out || n != want) return fail(AZ_ERR_BAD_ARG, "buffer must hold %lld floats", (long long)want);
   HIPCHK(hipStreamSynchronize(t->stream));
-  HIPCHK(hipMemcpy(out, src, sizeof(float) * (size_t)want, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out, c.a, sizeof(float) * (size_t)want, hipMemcpyDeviceToHost));
   return AZ_OK;
 }
 
@@ -995,7 +905,7 @@ static int tr_up(Scratch& tmp, float** p, const float* host, size_t n) {   // a 
   if (host) HIPCHK(hipMemcpy(*p, host, sizeof(float) * n, hipMemcpyHostToDevice));
   return AZ_OK;
 }
-#define TR_TOWER(t) if ((t)->simple) return fail(AZ_ERR_BAD_ARG, "the trainer of a SimpleNet engine has no convolution"); if ((t)->nblocks < 1) return fail(AZ_ERR_BAD_ARG, "the trainer's tower has no F -> F convolution (num_blocks = 0)")
+#define TR_TOWER(t) if (!(t)->ntower) return fail(AZ_ERR_BAD_ARG, "the trainer of a SimpleNet engine has no convolution"); if ((t)->ntower < 3) return fail(AZ_ERR_BAD_ARG, "the trainer's tower has no F -> F convolution (num_blocks = 0)")
 // weight gradient of a 3x3 F -> F convolution (tr_wgrad16 = k_wgrad16 + k_wgrad_reduce): a, dg = [B P][F] with row = board P + y W + x;
 // out[9][F][F] = [tap][ci][co], tap = 3 (dy + 1) + (dx + 1): sum over the rows whose neighbour (y + dy, x + dx) is on the board of a[neighbour][ci] dg[row][co]
 extern "C" int az_debug_trainer_wgrad(az_trainer* t, const float* a, const float* dg, int64_t n_in, float* out, int64_t n_out) {
@@ -1008,7 +918,7 @@ extern "C" int az_debug_trainer_wgrad(az_trainer* t, const float* a, const float
   HIPCHK(hipStreamSynchronize(t->side));
   HIPCHK(hipMemcpy(t->dact, a, sizeof(float) * (size_t)want_in, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(t->dact2, dg, sizeof(float) * (size_t)want_in, hipMemcpyHostToDevice));
-  float* dw = t->gwork + t->convs[1].wk_wm;
+  float* dw = t->gwork + t->layers[1].wk_wm;
   AZCHK(tr_wgrad16(t, t->dact, t->dact2, dw, t->stream));
   HIPCHK(hipStreamSynchronize(t->stream));
   HIPCHK(hipGetLastError());
@@ -1024,13 +934,13 @@ extern "C" int az_debug_trainer_conv(az_trainer* t, int32_t layer, int32_t dgrad
                                      int64_t n, float* out, float* a_out, double* sums, int32_t* nparts) {
   TRAINER(t);
   TR_TOWER(t);
-  if (layer < 1 || layer > 2 * t->nblocks) return fail(AZ_ERR_BAD_ARG, "layer %d: the F -> F convolutions are 1 .. %d", layer, 2 * t->nblocks);
+  if (layer < 1 || layer >= t->ntower) return fail(AZ_ERR_BAD_ARG, "layer %d: the F -> F convolutions are 1 .. %d", layer, t->ntower - 1);
   const int F = t->F;
   const int64_t want = (int64_t)t->R * F;
   if (!in || !out || n != want) return fail(AZ_ERR_BAD_ARG, "in and out must hold %lld floats", (long long)want);
   if (dgrad ? (bn || res || a_out || sums) : (addend || !bn || !a_out || !sums))
     return fail(AZ_ERR_BAD_ARG, dgrad ? "the data gradient takes in, addend and out only" : "the forward pass takes in, bn, res, out, a_out and sums");
-  const TrConv& c = t->convs[layer];
+  const TrLayer& c = t->layers[layer];
   const size_t bytes = sizeof(float) * (size_t)want;
   HIPCHK(hipStreamSynchronize(t->stream));
   HIPCHK(hipStreamSynchronize(t->side));
