@@ -228,23 +228,23 @@ static int vm_grow(az_engine* e, long long ahead) {
 }
 // the most nodes a slot of a free-running phase can add in one wave: the pending leaf's node and, with an evaluation cache, one per
 // simulation the cache answers -- up to run_k in the wave's launch, up to fr_kbg in the background launch behind it
-static long long fr_per_wave(const az_engine* e) { return e->d_ec ? (long long)e->fr_k + 1 + (long long)e->fr_kbg : 1; }
+static long long fr_per_wave(const az_engine* e) { return e->d_ec ? (long long)e->ph.fr_k + 1 + (long long)e->ph.fr_kbg : 1; }
 // waves between two looks of the host at the node counts: fr_round's, every fr_round_waves waves -- and, where a slot can add so much per
 // wave that a round's worth would map a good part of a chunk ahead of every slot (8192 Mancala slots: 9 GB), looks of their own in
 // between (fr_look), so that a slot is provisioned about an eighth of a chunk ahead
 static int fr_look_interval(const az_engine* e) {
-  if (!e->vm_rows) return e->fr_round_waves;
-  return (int)std::max<long long>(1, std::min<long long>(e->fr_round_waves, (e->vm_chunk_nodes / 8) / fr_per_wave(e)));
+  if (!e->vm_rows) return e->ph.fr_round_waves;
+  return (int)std::max<long long>(1, std::min<long long>(e->ph.fr_round_waves, (e->vm_chunk_nodes / 8) / fr_per_wave(e)));
 }
 // the most nodes a slot of a free-running phase can add between two looks (64-bit: AZHIP_RUN_K, AZHIP_RUN_KBG, AZHIP_FR_ROUND go up to INT_MAX)
 static long long fr_ahead(const az_engine* e) {
   const long long cap = e->v.cap_nodes;
-  return std::min<long long>(std::min<long long>(e->fr_look_waves, cap) * std::min(fr_per_wave(e), cap) + 2, cap);
+  return std::min<long long>(std::min<long long>(e->ph.fr_look_waves, cap) * std::min(fr_per_wave(e), cap) + 2, cap);
 }
 // a look at the node counts alone, between two rounds (a mapped-on-demand pool only).  It reads nothing the step report holds -- the
 // counts come from k_node_counts through vm_grow's own copy -- so it keeps its plain wait for the group's streams.
 static int fr_look(az_engine* e) {
-  e->fr_since_look = 0;
+  e->ph.fr_since_look = 0;
   AZCHK(sync_groups(e));
   return vm_grow(e, fr_ahead(e));
 }
@@ -609,10 +609,10 @@ extern "C" int az_engine_device_bytes(az_engine* e, int64_t* bytes) {
 }
 extern "C" int az_engine_release_phase(az_engine* e) {
   ENGINE(e);
-  if (e->running) return fail(AZ_ERR_STATE, "self-play in progress");
+  if (e->ph.running) return fail(AZ_ERR_STATE, "self-play in progress");
   AZCHK(sync_all(e));
   if (e->d_phase) HIPCHK(hipFree(e->d_phase));
-  e->d_phase = nullptr; e->phase_cap = 0; e->phase_n = 0; e->ph_games.clear(); e->ph_off.clear();
+  e->d_phase = nullptr; e->phase_cap = 0; e->ph.dev_n = 0; e->ph.dev_games.clear(); e->ph.dev_off.clear();
   return AZ_OK;
 }
 
@@ -800,7 +800,7 @@ static int simple_set_params(az_engine* e, const float* blob, int64_t n) {
 extern "C" int az_net_set_params(az_engine* e, const float* blob, int64_t n) {
   ENGINE(e);
   if (!oracle_is_net(e->cfg)) return fail(AZ_ERR_STATE, "engine was created without a network oracle");
-  if (e->running) return fail(AZ_ERR_STATE, "self-play in progress");
+  if (e->ph.running) return fail(AZ_ERR_STATE, "self-play in progress");
   if (e->cfg.oracle == AZ_ORACLE_SIMPLENET) return simple_set_params(e, blob, n);
   const az_engine_cfg& c = e->cfg;
   const NetLayout lay = net_layout(e->gi, c);
@@ -872,7 +872,7 @@ static bool split_gave_up(az_engine* e) {
   (void)hipMemcpy(e->v.err, &code, sizeof(int), hipMemcpyHostToDevice);
   *e->h_xflag = 0;
   e->split_off = true;
-  e->stats.tower_fallbacks++;
+  e->ph.stats.tower_fallbacks++;
   return true;
 }
 // One launch of the network seam on the engine's stream, m boards: from_planes ? d_X / d_A : the states in d_tmp_env (count in d_ntmp).
@@ -990,40 +990,40 @@ template <class Gm> static int wave_group(az_engine* e, int g, uint32_t sim_idx)
   const int G = v.G;
   const int gb = (G * L + 255) / 256;
   const int par = (e->wave_par[g] ^= 1);
-  e->stats.slot_launches += e->group_active[g];                     // (the host's count: as of its last look in a free-running phase)
-  LAUNCH_ON(e, st, AZ_K_SELECT, G, (k_tree<Gm>), gb, 256, 0, v, e->p, (e->pending[g] || e->fr_on) ? 1 : 0, 1, par);
+  e->ph.stats.slot_launches += e->group_active[g];                     // (the host's count: as of its last look in a free-running phase)
+  LAUNCH_ON(e, st, AZ_K_SELECT, G, (k_tree<Gm>), gb, 256, 0, v, e->p, (e->pending[g] || e->ph.fr_on) ? 1 : 0, 1, par);
   e->pending[g] = true;
   // One slot group, free-running: the wave's launch, the tower and the heads follow each other on ONE stream (no event between them: a
   // dependency across streams costs ~10 us, three of them per wave were 3 % of it); the move step and the background search go to two side
   // streams, behind an event recorded here, and the next wave's launch waits for ONE event that stands for both (below).
   hipStream_t s2 = st;
   e->bg_signal = false;
-  const bool side = e->fr_on && !split && oracle_is_net(e->cfg) && e->fr_s[1] && st == e->fr_s[0];
+  const bool side = e->ph.fr_on && !split && oracle_is_net(e->cfg) && e->fr_s[1] && st == e->fr_s[0];
   // (the stop word of the background search: without it a background launch of fr_kbg simulations outlasts a SHORT tower and the next wave
   // waits for it -- Mancala, 8192 slots: 19.8 instead of 39.7 M sims/s; AZHIP_BG_STOP=0 switches it off)
-  if (side) { s2 = e->fr_s[1]; HIPCHK(hipEventRecord(e->fr_ev[0], st)); ++e->bg_seq; e->bg_signal = env_process().bg_stop && e->fr_kbg > 0; }
+  if (side) { s2 = e->fr_s[1]; HIPCHK(hipEventRecord(e->fr_ev[0], st)); ++e->bg_seq; e->bg_signal = env_process().bg_stop && e->ph.fr_kbg > 0; }
   if (oracle_is_net(e->cfg)) {
     AZCHK(net_wave(e, g, split, e->group_active[g]));
   } else {
     LAUNCH_ON(e, st, AZ_K_SYNTH, G, (k_synth_oracle<Gm>), (G + 255) / 256, 256, 0, v, e->p, sim_idx, par);
   }
-  if (e->fr_on) {
+  if (e->ph.fr_on) {
     // Under the wave's network launch (the tree stream has not been made to wait for it yet): the slots whose explore! is complete play
     // their move (and take their next game if it was the last one), then every slot that has no question pending -- it moved just now,
     // or the wave's launch left it without one -- searches on in the background; what it finds joins the NEXT wave's batch.
     FRArgs fa;
     fa.st = e->d_fr; fa.done = e->d_done; fa.done_off = e->d_done_off;
     fa.recs = e->d_phase ? e->d_phase : e->d_stage; fa.recs_cap = e->d_phase ? (long long)e->phase_cap : (long long)e->v.G * e->v.max_moves;
-    fa.done_cap = e->done_cap; fa.total_games = e->total_games; fa.first_game_id = (uint32_t)e->first_game_id; fa.group = g; fa.host_words = e->d_fr_words;
+    fa.done_cap = e->done_cap; fa.total_games = e->ph.ids.total_games; fa.first_game_id = (uint32_t)e->ph.ids.first_game_id; fa.group = g; fa.host_words = e->d_fr_words;
     // (side streams: the move step and the background search touch different slots -- explore! complete / still searching -- and run
     // side by side: one serial move under a busy tower takes 0.4 ms, which the background search would otherwise wait out)
     hipStream_t s3 = side ? e->fr_s[2] : s2;
     if (side) { HIPCHK(hipStreamWaitEvent(s2, e->fr_ev[0], 0)); HIPCHK(hipStreamWaitEvent(s3, e->fr_ev[0], 0)); }
     { DView mv = v; mv.low_prio = env_process().bg_prio ? 0 : 1; LAUNCH_ON(e, s3, AZ_K_MOVE, G, (k_move_fr<Gm>), (G + 255) / 256, 256, 0, mv, e->p, fa); }
-    if (e->fr_kbg > 0) {
+    if (e->ph.fr_kbg > 0) {
       AZCHK(ec_next_launch(e, &e->gv[g]));
       DView bv = e->gv[g];
-      bv.run_k = e->fr_kbg; bv.low_prio = env_process().bg_prio ? 0 : 1;
+      bv.run_k = e->ph.fr_kbg; bv.low_prio = env_process().bg_prio ? 0 : 1;
       if (side && e->bg_signal) { bv.bg_stop = e->d_bg_stop; bv.bg_seq = e->bg_seq; }   // ... until the wave's tower has run (the tower raises the word, or wave_net_f has it set: net_impl.h)
       LAUNCH_ON(e, s2, AZ_K_EXPAND, G, (k_tree<Gm>), gb, 256, 0, bv, e->p, 0, 1, par ^ 1);
     }
@@ -1056,7 +1056,7 @@ template <class Gm> static int recover_split(az_engine* e) {
   for (int g = 0; g < e->ngroups; ++g) any = any || xerr[g] == DERR_EXCHANGE;
   if (!any) return AZ_OK;                                            // raised by the network seam's launch: split_gave_up handles that one
   e->split_off = true;
-  e->stats.tower_fallbacks++;
+  e->ph.stats.tower_fallbacks++;
   for (int g = 0; g < e->ngroups; ++g) {
     e->wave_par[g] ^= (skipped[2 * g] & 1);                          // back to the leaf counter of the last wave that really ran
     if (skipped[2 * g + 1]) e->pending[g] = true;                    // its expand + backup did not happen
@@ -1065,7 +1065,7 @@ template <class Gm> static int recover_split(az_engine* e) {
     for (int g = 0; g < e->ngroups; ++g)
       if (e->pending[g] && e->group_active[g] > 0) {
         AZCHK(net_wave(e, g, e->gs[g] != e->gt[g], e->group_active[g]));
-        if (e->fr_on && e->gs[g] != e->gt[g]) HIPCHK(hipStreamWaitEvent(e->gs[g], e->ev_net[g], 0));   // (a free-running wave_group waits at its end; this launch has none)
+        if (e->ph.fr_on && e->gs[g] != e->gt[g]) HIPCHK(hipStreamWaitEvent(e->gs[g], e->ev_net[g], 0));   // (a free-running wave_group waits at its end; this launch has none)
       }
   for (int g = 0; g < e->ngroups; ++g)
     for (int i = 0; i < skipped[2 * g]; ++i) AZCHK(wave_group<Gm>(e, g, 0));
@@ -1077,7 +1077,7 @@ template <class Gm> static int wave(az_engine* e, int ngroups_active, uint32_t s
     if (e->group_active[g] == 0) continue;                         // nothing left to search in this group
     AZCHK(wave_group<Gm>(e, g, sim_idx));
   }
-  e->stats.waves++;
+  e->ph.stats.waves++;
   return AZ_OK;
 }
 // completes the simulations the last wave started (expand + backup only); every group, asynchronous
@@ -1091,6 +1091,16 @@ template <class Gm> static int flush_pending(az_engine* e) {
     e->pending[g] = false;
   }
   return AZ_OK;
+}
+// Split towers have run: did one give up? (the word is only valid once the device is idle)  flush: the caller stands at the end of an
+// explore! and has flushed already; recover_split may leave a simulation pending again, which is then completed as well.
+template <class Gm> static int split_check(az_engine* e, bool flush) {
+  if (!e->xch_epoch || e->split_off) return AZ_OK;
+  AZCHK(sync_all(e));
+  if (!*(volatile int*)e->h_xflag) return AZ_OK;
+  AZCHK(recover_split<Gm>(e));
+  if (flush) AZCHK(flush_pending<Gm>(e));
+  return sync_all(e);
 }
 
 // Two consecutive waves of the single slot group as ONE hipGraph launch (k_tree, tower, heads, k_tree, tower, heads):
@@ -1111,10 +1121,10 @@ template <class Gm> static int wave_pair_graph(az_engine* e, hipGraphExec_t* out
   if (it != e->wave_graphs.end()) { *out = it->second; return AZ_OK; }
   hipGraph_t g = nullptr;
   HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-  const int64_t waves0 = e->stats.waves;
+  const int64_t waves0 = e->ph.stats.waves;
   int st = wave<Gm>(e, 1, 0);
   if (st == AZ_OK) st = wave<Gm>(e, 1, 1);
-  e->stats.waves = waves0;                                          // nothing ran: the capture only recorded the launches
+  e->ph.stats.waves = waves0;                                          // nothing ran: the capture only recorded the launches
   const hipError_t ce = hipStreamEndCapture(e->stream, &g);
   if (st != AZ_OK) { if (g) (void)hipGraphDestroy(g); return st; }
   if (ce != hipSuccess) return fail(AZ_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
@@ -1136,7 +1146,7 @@ template <class Gm> static int run_waves(az_engine* e, int nga, int n, uint32_t 
       AZCHK(wave_pair_graph<Gm>(e, &ex));
       HIPCHK(hipGraphLaunch(ex, e->stream));
       e->report_fresh = false;
-      e->stats.waves += 2;
+      e->ph.stats.waves += 2;
       done += 2;
     } else {
       AZCHK(wave<Gm>(e, nga, sim0 + (uint32_t)done));
@@ -1172,7 +1182,7 @@ static int start_games(az_engine* e, const std::vector<int>& slots, const std::v
 
 extern "C" int az_mcts_reset(az_engine* e) {
   ENGINE(e);
-  if (e->running) return fail(AZ_ERR_STATE, "self-play in progress");
+  if (e->ph.running) return fail(AZ_ERR_STATE, "self-play in progress");
   const int G = e->v.G;
   HIPCHK(hipMemsetAsync(e->v.ht, 0, sizeof(unsigned long long) * (size_t)G * e->v.ht_size, e->stream));
   hipLaunchKernelGGL(k_slot_records, dim3((G + 255) / 256), dim3(256), 0, e->stream, e->v, (int)SR_RESET_TREE);
@@ -1205,23 +1215,29 @@ static int explore_begin(az_engine* e, const std::vector<int>& slots, const std:
   for (int sl : slots) e->group_active[sl / e->gv[0].G]++;
   // (round 6) the explore! runs ahead: inside one launch a slot completes every simulation that ends on a terminal state or on a
   // state the evaluation cache answers (tree.h k_tree, run_k > 0 with fr = 0), every slot exactly nsims of them; the host launches
-  // waves until the device reports nobody busy (explore_waves).  Not for the rollout oracle (keyed by the wave's index) nor under hipGraph replay.
+  // waves until the device reports nobody busy (explore_loop).  Not for the rollout oracle (keyed by the wave's index) nor under hipGraph replay.
   const bool ahead = e->env.explore_k > 1 && e->cfg.oracle != AZ_ORACLE_ROLLOUT && !e->env.use_graphs && !e->env.tree_sort;
   for (int g = 0; g < e->ngroups; ++g) { e->gv[g].run_k = ahead ? e->env.explore_k : 0; e->gv[g].fr = 0; e->gv[g].busy_host = ahead ? e->d_busy + g : nullptr; e->h_busy[g] = -1; }
   return AZ_OK;
 }
-// the waves of an explore! of `nsims` simulations per slot on `nga` slot groups: nsims lock-step waves, or -- running ahead -- as many
-// as it takes until every slot has done its nsims (at most nsims; the device's count of busy slots is looked at every 16 waves)
-template <class Gm> static int explore_waves(az_engine* e, int nga, int nsims) {
-  if (!e->gv[0].run_k) return run_waves<Gm>(e, nga, nsims, 0);
-  for (int i = 0; i < nsims + 1; ++i) {
-    AZCHK(wave<Gm>(e, nga, (uint32_t)i));
-    if ((i & 15) == 15) {
-      AZCHK(sync_groups(e)); HIPCHK(hipStreamSynchronize(e->stream));
-      bool busy = false;
-      for (int g = 0; g < nga; ++g) busy = busy || (e->group_active[g] > 0 && ((volatile int*)e->h_busy)[g] != 0);
-      if (!busy) break;
+// The waves of the explores in progress on n = 1 or 2 engines (the arena's players), engine k on nga[k] slot groups: wave i of engine 0,
+// then wave i of engine 1, each on its own streams, so the searches overlap.  An engine is done after p.nsims waves or -- running
+// ahead (explore_begin) -- when its device reports no busy slot (looked at every 16 waves), after p.nsims + 1 waves at the latest.
+template <class Gm> static int explore_loop(int n, az_engine* const* eng, const int* nga) {
+  bool done[2] = {true, true};
+  for (int k = 0; k < n; ++k) done[k] = nga[k] == 0;
+  for (int i = 0; !(done[0] && done[1]); ++i) {
+    for (int k = 0; k < n; ++k) if (!done[k]) {
+      if (i >= eng[k]->p.nsims + (eng[k]->gv[0].run_k > 0 ? 1 : 0)) { done[k] = true; continue; }
+      HIPCHK(hipSetDevice(eng[k]->device)); AZCHK(wave<Gm>(eng[k], nga[k], (uint32_t)i));
     }
+    if ((i & 15) == 15)
+      for (int k = 0; k < n; ++k) if (!done[k] && eng[k]->gv[0].run_k > 0) {
+        HIPCHK(hipSetDevice(eng[k]->device)); AZCHK(sync_groups(eng[k])); HIPCHK(hipStreamSynchronize(eng[k]->stream));
+        bool busy = false;
+        for (int g = 0; g < nga[k]; ++g) busy = busy || (eng[k]->group_active[g] > 0 && ((volatile int*)eng[k]->h_busy)[g] != 0);
+        done[k] = !busy;
+      }
   }
   return AZ_OK;
 }
@@ -1235,10 +1251,7 @@ template <class Gm> static int explore_end(az_engine* e, int nga) {
   if (!nga) return AZ_OK;
   AZCHK(flush_pending<Gm>(e));                                     // the last simulation's expand + backup
   AZCHK(sync_groups(e));
-  if (e->xch_epoch && !e->split_off) {                              // split towers have run: did one give up? (the word is only valid once the device is idle)
-    AZCHK(sync_all(e));
-    if (*(volatile int*)e->h_xflag) { AZCHK(recover_split<Gm>(e)); AZCHK(flush_pending<Gm>(e)); AZCHK(sync_all(e)); }
-  }
+  AZCHK(split_check<Gm>(e, true));
   hipLaunchKernelGGL(k_slot_records, dim3((e->v.G + 255) / 256), dim3(256), 0, e->stream, e->v, (int)SR_CLEAR_ACTIVE);
   return check_device_error(e);
 }
@@ -1251,14 +1264,14 @@ static int explore_slots(az_engine* e, const std::vector<int>& slots, const std:
   AZCHK(vm_grow(e, (long long)nsims + 2));                         // mapped-on-demand pool: room for this explore! (a no-op for plain pools)
   struct Sims { az_engine* e; int keep; ~Sims() { e->p.nsims = keep; } } sims{e, e->p.nsims};   // the kernel counts a slot's simulations against DParams::nsims
   e->p.nsims = nsims;
-  if (nga) AZCHK(explore_waves<Gm>(e, nga, nsims));
+  if (nga) AZCHK(e->gv[0].run_k ? explore_loop<Gm>(1, &e, &nga) : run_waves<Gm>(e, nga, nsims, 0));   // (not ahead: run_waves, so hipGraph replay)
   return explore_end<Gm>(e, nga);
 }
 
 extern "C" int az_mcts_explore(az_engine* e, const uint64_t* root_keys, int32_t nslots, int32_t nsims,
                                const double* eta, const uint32_t* game_ids, const uint32_t* moves) {
   ENGINE(e);
-  if (e->running) return fail(AZ_ERR_STATE, "self-play in progress");
+  if (e->ph.running) return fail(AZ_ERR_STATE, "self-play in progress");
   if (e->mm_on) return fail(AZ_ERR_STATE, "the engine is a MinMax player (az_engine_set_minmax): it has no search to explore");
   if (!root_keys || nslots < 1 || nslots > e->v.G) return fail(AZ_ERR_BAD_ARG, "nslots must be in 1..num_workers");
   if (nsims < 1) return fail(AZ_ERR_BAD_ARG, "nsims must be >= 1");
@@ -1341,9 +1354,8 @@ extern "C" int az_mcts_counters(az_engine* e, int32_t slot, int64_t* ts, int64_t
 }
 
 // ------------------------------------------------------------------------------- self-play
-extern "C" int az_selfplay_begin(az_engine* e, int32_t num_games, int32_t first_game_id) {
-  ENGINE(e);
-  if (e->running) return fail(AZ_ERR_STATE, "self-play already in progress");
+static int selfplay_begin(az_engine* e, int num_games, int first_game_id, bool host_moves) {
+  if (e->ph.running) return fail(AZ_ERR_STATE, "self-play already in progress");
   if (e->mm_on) return fail(AZ_ERR_STATE, "the engine is a MinMax player (az_engine_set_minmax): self-play needs an MCTS player");
   if (num_games == 0) return fail(AZ_ERR_BAD_ARG, "num_games must be != 0");
   if (e->p.nsims < 2) return fail(AZ_ERR_BAD_ARG, "num_iters_per_turn = 0 (NetworkPlayer) is for az_arena_run only");
@@ -1357,99 +1369,113 @@ extern "C" int az_selfplay_begin(az_engine* e, int32_t num_games, int32_t first_
     if (nosym) return fail(AZ_ERR_BAD_ARG, "flip_probability != 0 but no symmetries were declared for this game (game.jl:332)");
   }
   if (oracle_is_net(e->cfg) && !e->net_loaded) return fail(AZ_ERR_STATE, "az_net_set_params has not been called");
+  // a fresh phase record: nothing carries over from the phase before (`running` stays false until the end)
+  e->ph = Phase();
+  e->ph.host_moves = host_moves; e->ph.ids.total_games = num_games; e->ph.ids.first_game_id = first_game_id;
   const int G = e->v.G;
   // a fresh player per worker (simulations.jl:217-218): empty trees, zero counters
   AZCHK(reset_wave_state(e));
   hipLaunchKernelGGL(k_slot_records, dim3((G + 255) / 256), dim3(256), 0, e->stream, e->v, (int)(SR_CLEAR_ACTIVE | SR_CLEAR_TOTALS));
   HIPCHK(hipMemsetAsync(e->v.finished, 0, sizeof(int) * G, e->stream));
   HIPCHK(hipMemsetAsync(e->v.worker_sim_id, 0, sizeof(int) * G, e->stream));
-
   HIPCHK(hipMemsetAsync(e->gv[0].stat, 0, sizeof(long long) * e->stat_words, e->stream));   // gv[0].stat = the base of the accumulator array
-  e->total_games = num_games; e->first_game_id = first_game_id; e->next_game = 0; e->games_done = 0; e->wave_in_move = 0;
-  e->q_games.clear(); e->q_moves.clear();
-  e->ph_games.clear(); e->ph_off.clear(); e->phase_n = 0;
-  {
-    // the phase's move records also stay on the device (az_memory_push_engine, az_comm_gather_push): a bounded phase only
-    const int64_t want = num_games > 0 ? (int64_t)num_games * e->v.max_moves : 0;
-    if (want > e->phase_cap || want == 0) { if (e->d_phase) (void)hipFree(e->d_phase); e->d_phase = nullptr; e->phase_cap = 0; }
-    if (want > 0 && !e->d_phase) {
-      if (want * (int64_t)sizeof(az_move_rec) > (16LL << 30)) return fail(AZ_ERR_CAPACITY, "num_games x max_moves_per_game move records exceed the 16 GB phase buffer: split the phase");
-      HIPCHK(hipMalloc((void**)&e->d_phase, sizeof(az_move_rec) * (size_t)want));
-      e->phase_cap = want;
-    }
+  // the phase's move records also stay on the device (az_memory_push_engine, az_comm_gather_push): a bounded phase only
+  const int64_t want = num_games > 0 ? (int64_t)num_games * e->v.max_moves : 0;
+  if (want > e->phase_cap || want == 0) { if (e->d_phase) (void)hipFree(e->d_phase); e->d_phase = nullptr; e->phase_cap = 0; }
+  if (want > 0 && !e->d_phase) {
+    if (want * (int64_t)sizeof(az_move_rec) > (16LL << 30)) return fail(AZ_ERR_CAPACITY, "num_games x max_moves_per_game move records exceed the 16 GB phase buffer: split the phase");
+    HIPCHK(hipMalloc((void**)&e->d_phase, sizeof(az_move_rec) * (size_t)want));
+    e->phase_cap = want;
   }
-  memset(&e->stats, 0, sizeof e->stats);
   e->report_fresh = false;
-  e->aborted_ids.clear();
   const int n0 = num_games < 0 ? G : std::min(G, (int)num_games);
   std::vector<int> slots(n0);
   std::vector<uint32_t> gids(n0);
-  for (int i = 0; i < n0; ++i) { slots[i] = i; gids[i] = (uint32_t)(first_game_id + e->next_game++); }
+  for (int i = 0; i < n0; ++i) { slots[i] = i; gids[i] = e->ph.ids.take(); }
   DISPATCH_GAME(e->cfg.game, AZCHK(start_games<Gm>(e, slots, gids, nullptr, 1, 1)));
   AZCHK(vm_grow(e, e->p.nsims + 2));                                 // every slot can take its first explore!
-  e->active_slots = n0;
+  e->ph.active_slots = n0;
   for (int g = 0; g < AZ_MAX_GROUPS; ++g) e->group_active[g] = 0;
   for (int i = 0; i < n0; ++i) e->group_active[i / e->gv[0].G]++;
-  {
-    // free-running or lock step (az_engine_cfg.lock_step; AZHIP_FREE_RUN=0|1 overrides).  Always lock step: the rollout oracle (its
-    // answer is keyed by the simulation's index in the wave sequence), hipGraph replay (fixed launch sequences), the depth-ordering experiment
-    const EnvPhase ph;                                                // AZHIP_FREE_RUN, AZHIP_RUN_K, AZHIP_RUN_KBG, AZHIP_FR_ROUND
-    const bool want = ph.free_run >= 0 ? ph.free_run != 0 : e->cfg.lock_step == 0;
-    const bool on = want && e->cfg.oracle != AZ_ORACLE_ROLLOUT && !e->env.use_graphs && !e->env.tree_sort;
-    // wave launch: up to 3 simulations per slot (it is on the wave's critical path: 35 / 50 / 62 / 75 us for 1 / 2 / 3 / 4 at 4096 slots);
-    // background launch: one slot group -- up to 32 more, or until the tower has run (the stop word); several groups -- a few (it runs on
-    // the group's tree stream, ahead of the next wave's launch).  profiles/r6/README.md has the sweeps.
-    e->fr_k = ph.run_k; e->fr_kbg = ph.run_kbg >= 0 ? ph.run_kbg : (e->ngroups == 1 ? 32 : 8); e->fr_round_waves = ph.round_waves;
-    e->fr_look_waves = fr_look_interval(e); e->fr_since_look = 0;
-    if (on) AZCHK(vm_grow(e, fr_ahead(e)));                          // mapped-on-demand pool: the host's first look comes fr_look_waves waves from now
-    if (on) {
-      const int want_cap = num_games > 0 ? num_games : G;
-      if (want_cap > e->done_cap) {
-        if (e->d_done) (void)hipFree(e->d_done);
-        if (e->d_done_off) (void)hipFree(e->d_done_off);
-        e->d_done = nullptr; e->d_done_off = nullptr; e->done_cap = 0;
-        HIPCHK(hipMalloc((void**)&e->d_done, sizeof(az_game_rec) * (size_t)want_cap));
-        HIPCHK(hipMalloc((void**)&e->d_done_off, sizeof(long long) * (size_t)want_cap));
-        e->done_cap = want_cap;
-      }
-      if (num_games < 0) e->done_cap = std::min(e->done_cap, G);     // an unbounded phase's staging area holds G games' records
-      FRState fs;
-      memset(&fs, 0, sizeof fs);
-      fs.next_game = e->next_game;
-      for (int g = 0; g < AZ_MAX_GROUPS; ++g) fs.active[g] = e->group_active[g];
-      HIPCHK(hipMemcpyAsync(e->d_fr, &fs, sizeof fs, hipMemcpyHostToDevice, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
-      e->h_fr_words[0] = 0; e->h_fr_words[1] = n0;
-      e->fr_prev_done = 0; e->fr_prev_recs = 0; e->fr_since_round = 0; e->fr_given_up = 0;
+  // free-running or lock step (az_engine_cfg.lock_step; AZHIP_FREE_RUN=0|1 overrides).  Always lock step: the rollout oracle (its
+  // answer is keyed by the simulation's index in the wave sequence), hipGraph replay (fixed launch sequences), the depth-ordering experiment
+  const EnvPhase ph;                                                // AZHIP_FREE_RUN, AZHIP_RUN_K, AZHIP_RUN_KBG, AZHIP_FR_ROUND
+  const bool asked = ph.free_run >= 0 ? ph.free_run != 0 : e->cfg.lock_step == 0;
+  const bool on = asked && e->cfg.oracle != AZ_ORACLE_ROLLOUT && !e->env.use_graphs && !e->env.tree_sort;
+  // wave launch: up to 3 simulations per slot (it is on the wave's critical path: 35 / 50 / 62 / 75 us for 1 / 2 / 3 / 4 at 4096 slots);
+  // background launch: one slot group -- up to 32 more, or until the tower has run (the stop word); several groups -- a few (it runs on
+  // the group's tree stream, ahead of the next wave's launch).  profiles/r6/README.md has the sweeps.
+  e->ph.fr_k = ph.run_k; e->ph.fr_kbg = ph.run_kbg >= 0 ? ph.run_kbg : (e->ngroups == 1 ? 32 : 8); e->ph.fr_round_waves = ph.round_waves;
+  e->ph.fr_look_waves = fr_look_interval(e);
+  if (on) AZCHK(vm_grow(e, fr_ahead(e)));                          // mapped-on-demand pool: the host's first look comes fr_look_waves waves from now
+  if (on) {
+    const int want_cap = num_games > 0 ? num_games : G;
+    if (want_cap > e->done_cap) {
+      if (e->d_done) (void)hipFree(e->d_done);
+      if (e->d_done_off) (void)hipFree(e->d_done_off);
+      e->d_done = nullptr; e->d_done_off = nullptr; e->done_cap = 0;
+      HIPCHK(hipMalloc((void**)&e->d_done, sizeof(az_game_rec) * (size_t)want_cap));
+      HIPCHK(hipMalloc((void**)&e->d_done_off, sizeof(long long) * (size_t)want_cap));
+      e->done_cap = want_cap;
     }
-    for (int g = 0; g < e->ngroups; ++g) { e->gv[g].run_k = on ? e->fr_k : 0; e->gv[g].fr = on ? 1 : 0; e->gv[g].fr_active = on ? &e->d_fr->active[g] : nullptr; }
-    if (on && e->ngroups == 1 && oracle_is_net(e->cfg)) {   // tree kernels under the group's own network launch: two streams (ev_* with them)
-      HIPCHK(hipStreamSynchronize(e->stream));
-      e->gs[0] = e->gt[0] = e->fr_s[0];                                // (the second stream, fr_s[1], carries the move step and the background search: wave_group)
-    }
-    e->fr_on = on;
+    if (num_games < 0) e->done_cap = std::min(e->done_cap, G);     // an unbounded phase's staging area holds G games' records
+    FRState fs;
+    memset(&fs, 0, sizeof fs);
+    fs.next_game = e->ph.ids.next_game;
+    for (int g = 0; g < AZ_MAX_GROUPS; ++g) fs.active[g] = e->group_active[g];
+    HIPCHK(hipMemcpyAsync(e->d_fr, &fs, sizeof fs, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->h_fr_words[0] = 0; e->h_fr_words[1] = n0;
   }
+  for (int g = 0; g < e->ngroups; ++g) { e->gv[g].run_k = on ? e->ph.fr_k : 0; e->gv[g].fr = on ? 1 : 0; e->gv[g].fr_active = on ? &e->d_fr->active[g] : nullptr; }
+  if (on && e->ngroups == 1 && oracle_is_net(e->cfg)) {   // tree kernels under the group's own network launch: two streams (ev_* with them)
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->gs[0] = e->gt[0] = e->fr_s[0];                                // (the second stream, fr_s[1], carries the move step and the background search: wave_group)
+  }
+  e->ph.fr_on = on;
   split_register(e, e->ngroups);
   e->p.retire = 1;                                                  // an overflowing slot is retired, the phase goes on; set only once
                                                                     // nothing can fail any more (the hooks must never see it: ADVICE r3)
-  e->running = true;
-  e->t_begin = std::chrono::steady_clock::now();
+  e->ph.running = true;
+  e->ph.t_begin = std::chrono::steady_clock::now();
   return AZ_OK;
 }
+extern "C" int az_selfplay_begin(az_engine* e, int32_t num_games, int32_t first_game_id) {
+  ENGINE(e);
+  return selfplay_begin(e, num_games, first_game_id, true);
+}
 
-// another game id to hand out?  An unbounded phase (bench, polling) stops refilling before its ids reach the replacement bit.
-static inline bool more_games(const az_engine* e) {
-  return e->total_games < 0 ? (long long)e->first_game_id + e->next_game < (long long)AZ_REPLACEMENT_GAME_BIT : e->next_game < e->total_games;
+// A look found slots retired (`finished` word 2; fetch: the words are still to be fetched): the rule of phase_books.h retire_slots and its
+// books -- aborted ids, counters, ids handed out.  The caller adjusts its schedule's active counts and starts R's slots with empty trees.
+static int retire(az_engine* e, bool fetch, Retirement* R) {
+  const int G = e->v.G;
+  std::vector<uint32_t> gid(G);
+  if (fetch) HIPCHK(hipMemcpyAsync(e->h_finished.data(), e->v.finished, sizeof(int) * G, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(gid.data(), e->v.game_id, sizeof(uint32_t) * G, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  std::vector<int> aslots;
+  for (int s = 0; s < G; ++s) if (e->h_finished[s] == 2) aslots.push_back(s);
+  *R = retire_slots(aslots, gid.data(), e->gv[0].G, e->ngroups, &e->ph.ids, &e->ph.aborted_ids);
+  e->ph.stats.aborted_games += (int64_t)aslots.size();
+  e->ph.games_done += R->given_up;
+  return AZ_OK;
+}
+// a finished game is queued for az_selfplay_collect and, in a bounded phase, listed among the device-resident games: first_move / dev_off =
+// where its move records start among the host's (q_moves) / in d_phase
+static void queue_game(az_engine* e, az_game_rec g, long long first_move, int64_t dev_off) {
+  g.first_move = (int32_t)first_move;
+  if (e->d_phase) { e->ph.dev_games.push_back(g); e->ph.dev_off.push_back(dev_off); }
+  e->ph.q_games.push_back(g);
+  e->ph.games_done++;
+  e->ph.stats.games++;
 }
 // the move step (play.jl:308-313) for every slot, then collection of finished games and refill
 template <class Gm> static int move_round(az_engine* e) {
   const int G = e->v.G;
+  Phase& ph = e->ph;
   AZCHK(flush_pending<Gm>(e));                                     // explore! is over: the last simulation's expand + backup
   AZCHK(sync_groups(e));
-  if (e->xch_epoch && !e->split_off) {                              // split towers have run: did one give up? (the word is only valid once the device is idle)
-    AZCHK(sync_all(e));
-    if (*(volatile int*)e->h_xflag) { AZCHK(recover_split<Gm>(e)); AZCHK(flush_pending<Gm>(e)); AZCHK(sync_all(e)); }
-  }
+  AZCHK(split_check<Gm>(e, true));
   LAUNCH(e, AZ_K_MOVE, G, (k_move<Gm>), (G + 255) / 256, 256, 0, e->v, e->p);
   if (e->env.tree_sort)                                                // the explore! that just ended says how deep each slot searches now
     for (int g = 0; g < e->ngroups; ++g) {
@@ -1459,41 +1485,20 @@ template <class Gm> static int move_round(az_engine* e) {
   HIPCHK(hipMemcpyAsync(e->h_finished.data(), e->v.finished, sizeof(int) * G, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipMemcpyAsync(e->h_grec.data(), e->v.grec, sizeof(az_game_rec) * G, hipMemcpyDeviceToHost, e->stream));
   AZCHK(check_device_error(e));   // synchronises
-  std::vector<int> fslots, offs, aslots;
-  int total = 0;
+  std::vector<int> fslots, offs;
+  int total = 0, nretired = 0;
   for (int s = 0; s < G; ++s) {
     if (e->h_finished[s] == 1) { fslots.push_back(s); offs.push_back(total); total += e->h_grec[s].num_moves; }
-    else if (e->h_finished[s] == 2) aslots.push_back(s);             // retired: node pool or move record full
+    else if (e->h_finished[s] == 2) ++nretired;                      // retired: node pool or move record full
   }
-  e->stats.moves += e->active_slots - (int)aslots.size();
-  std::vector<int> rslots, aslots_refill;
-  std::vector<uint32_t> rgids, agids;
-  if (!aslots.empty()) {
-    // the retired slots' games are reported as aborted (their ids via az_selfplay_aborted), count as done, and the slots
-    // take the next games with an empty tree
-    std::vector<uint32_t> gid(G);
-    HIPCHK(hipMemcpyAsync(gid.data(), e->v.game_id, sizeof(uint32_t) * G, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    for (int sl : aslots) {
-      const int32_t id = (int32_t)gid[sl];
-      e->aborted_ids.push_back(id);
-      e->stats.aborted_games++;
-      e->active_slots--; e->group_active[sl / e->gv[0].G]--;
-      if (!(id & AZ_REPLACEMENT_GAME_BIT)) {
-        // the phase still owes the caller this game: ONE replacement with its own RNG streams (id | bit 30) takes the slot, so
-        // that num_games games come back and every game_simulated() callback a host waits for arrives
-        aslots_refill.push_back(sl); agids.push_back((uint32_t)(id | AZ_REPLACEMENT_GAME_BIT));
-        e->active_slots++; e->group_active[sl / e->gv[0].G]++;
-        continue;
-      }
-      e->games_done++;                                               // the replacement overflowed too: given up, counted, reported
-      if (more_games(e)) {
-        aslots_refill.push_back(sl); agids.push_back((uint32_t)(e->first_game_id + e->next_game++));
-        e->active_slots++; e->group_active[sl / e->gv[0].G]++;
-      }
-    }
+  ph.stats.moves += ph.active_slots - nretired;
+  Retirement R;
+  if (nretired) {
+    // the retired slots' games are reported as aborted (their ids via az_selfplay_aborted); a slot that does not play on leaves its group
+    AZCHK(retire(e, false, &R));
+    for (int g = 0; g < e->ngroups; ++g) { e->group_active[g] -= R.idle[g]; ph.active_slots -= R.idle[g]; }
   }
-  if (fslots.empty() && aslots.empty()) return vm_grow(e, e->p.nsims + 2);
+  if (fslots.empty() && !nretired) return vm_grow(e, e->p.nsims + 2);
   const int nf = (int)fslots.size();
   if (nf) {
     HIPCHK(hipMemcpyAsync(e->d_slots, fslots.data(), sizeof(int) * nf, hipMemcpyHostToDevice, e->stream));
@@ -1501,35 +1506,28 @@ template <class Gm> static int move_round(az_engine* e) {
   }
   // the finished games' records: packed behind the phase's earlier games in HBM (or into the staging area when the
   // phase is unbounded), and from there to the host only if the caller wants host traces
-  if (e->d_phase && e->phase_n + total > e->phase_cap) return fail(AZ_ERR_CAPACITY, "phase buffer overflow");
-  az_move_rec* dst = e->d_phase ? e->d_phase + e->phase_n : e->d_stage;
+  if (e->d_phase && ph.dev_n + total > e->phase_cap) return fail(AZ_ERR_CAPACITY, "phase buffer overflow");
+  az_move_rec* dst = e->d_phase ? e->d_phase + ph.dev_n : e->d_stage;
   if (nf) hipLaunchKernelGGL(k_gather_traces, dim3(nf), dim3(64), 0, e->stream, e->v, e->d_slots, e->d_offsets, nf, dst);
-  const size_t m0 = e->q_moves.size();
-  if ((e->host_moves || !e->d_phase) && total) {
-    e->q_moves.resize(m0 + total);
-    HIPCHK(hipMemcpyAsync(e->q_moves.data() + m0, dst, sizeof(az_move_rec) * total, hipMemcpyDeviceToHost, e->stream));
+  const size_t m0 = ph.q_moves.size();
+  if ((ph.host_moves || !e->d_phase) && total) {
+    ph.q_moves.resize(m0 + total);
+    HIPCHK(hipMemcpyAsync(ph.q_moves.data() + m0, dst, sizeof(az_move_rec) * total, hipMemcpyDeviceToHost, e->stream));
   }
   HIPCHK(hipMemsetAsync(e->v.finished, 0, sizeof(int) * G, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
+  std::vector<int> rslots;
+  std::vector<uint32_t> rgids;
   for (int i = 0; i < nf; ++i) {
-    az_game_rec g = e->h_grec[fslots[i]];
-    g.first_move = (int32_t)(m0 + offs[i]);
-    if (e->d_phase) { e->ph_games.push_back(g); e->ph_off.push_back(e->phase_n + offs[i]); }
-    e->q_games.push_back(g);
-    e->games_done++;
-    e->stats.games++;
-    e->active_slots--;
-    e->group_active[fslots[i] / e->gv[0].G]--;
-    if (more_games(e)) {      // next id, in slot order (util.jl:181-188)
+    queue_game(e, e->h_grec[fslots[i]], (long long)m0 + offs[i], ph.dev_n + offs[i]);
+    if (ph.ids.more()) {      // next id, in slot order (util.jl:181-188)
       rslots.push_back(fslots[i]);
-      rgids.push_back((uint32_t)(e->first_game_id + e->next_game++));
-      e->active_slots++;
-      e->group_active[fslots[i] / e->gv[0].G]++;
-    }
+      rgids.push_back(ph.ids.take());
+    } else { ph.active_slots--; e->group_active[fslots[i] / e->gv[0].G]--; }
   }
-  if (e->d_phase) e->phase_n += total;
+  if (e->d_phase) ph.dev_n += total;
   AZCHK(start_games<Gm>(e, rslots, rgids, nullptr, 0, 1));
-  AZCHK(start_games<Gm>(e, aslots_refill, agids, nullptr, 1, 1));    // a retired slot starts over with an empty tree
+  AZCHK(start_games<Gm>(e, R.slots, R.gids, nullptr, 1, 1));         // a retired slot starts over with an empty tree
   return vm_grow(e, e->p.nsims + 2);                                 // chunks for the next explore! of every slot
 }
 
@@ -1565,17 +1563,16 @@ static __global__ void __launch_bounds__(256) k_step_report(FRState* st, const i
 // the slots' `finished` words are fetched only when the report counts a retired slot.
 template <class Gm> static int fr_round(az_engine* e) {
   const int G = e->v.G;
-  e->fr_since_round = 0; e->fr_since_look = 0;
+  e->ph.fr_since_round = 0; e->ph.fr_since_look = 0;
   // One slot group: the group's stream has been made to wait for the side streams at the end of every wave (wave_group), so the report
   // kernel, launched on it, is ordered behind everything it reports and one wait covers the wave and the report.  Several groups: their
   // streams are joined by the host first and the report runs on the engine's stream.
   const bool one = e->ngroups == 1;
   hipStream_t rs = one ? e->gs[0] : e->stream;
   if (!one) AZCHK(sync_groups(e));
-  if (e->xch_epoch && !e->split_off) {                              // split towers have run: did one give up? (the word is only valid once the device is idle)
-    AZCHK(sync_all(e));
-    if (*(volatile int*)e->h_xflag) { AZCHK(recover_split<Gm>(e)); AZCHK(sync_all(e)); }
-  }
+  // No flush behind a recovery, on purpose: a look is not the end of an explore!.  A free-running phase never flushes -- every wave's k_tree
+  // completes the simulation before it (wave_group: e->ph.fr_on in place of pending[g]) -- so what recover_split leaves pending is the next wave's.
+  AZCHK(split_check<Gm>(e, false));
   hipLaunchKernelGGL(k_step_report, dim3(1), dim3(256), 0, rs, e->d_fr, e->v.err, e->v.finished, G, e->gv[0].stat, (int)(e->stat_words / 4),
                      e->d_phase ? 0 : 1, e->d_report);
   HIPCHK(hipStreamSynchronize(rs));
@@ -1587,111 +1584,87 @@ template <class Gm> static int fr_round(az_engine* e) {
   bool dirty = false;
   const int done = (int)(fs.resv >> 40);
   const long long nrec = (long long)(fs.resv & ((1ULL << 40) - 1));
-  const int nd = done - e->fr_prev_done;
+  const int nd = done - e->ph.fr_prev_done;
   if (nd > 0) {
-    const size_t m0 = e->q_moves.size();
-    const long long nm = nrec - e->fr_prev_recs;
-    const bool to_host = (e->host_moves || !e->d_phase) && nm > 0;
+    const size_t m0 = e->ph.q_moves.size();
+    const long long nm = nrec - e->ph.fr_prev_recs;
+    const bool to_host = (e->ph.host_moves || !e->d_phase) && nm > 0;
     const size_t b_rec = sizeof(az_game_rec) * (size_t)nd, b_off = sizeof(long long) * (size_t)nd, b_mv = to_host ? sizeof(az_move_rec) * (size_t)nm : 0;
     const bool pinned = b_rec + b_off + b_mv <= FETCH_BYTES;         // (all three hold 8-byte words and are multiples of 8 bytes long)
     az_game_rec* h_rec; long long* h_off; az_move_rec* h_mv = nullptr;
-    if (to_host) e->q_moves.resize(m0 + (size_t)nm);
+    if (to_host) e->ph.q_moves.resize(m0 + (size_t)nm);
     if (pinned) {
       h_off = (long long*)e->h_fetch; h_rec = (az_game_rec*)(e->h_fetch + b_off); h_mv = (az_move_rec*)(e->h_fetch + b_off + b_rec);
     } else {
       e->h_done.resize(nd); e->h_done_off.resize(nd);
-      h_rec = e->h_done.data(); h_off = e->h_done_off.data(); if (to_host) h_mv = e->q_moves.data() + m0;
+      h_rec = e->h_done.data(); h_off = e->h_done_off.data(); if (to_host) h_mv = e->ph.q_moves.data() + m0;
     }
-    HIPCHK(hipMemcpyAsync(h_rec, e->d_done + e->fr_prev_done, b_rec, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(h_off, e->d_done_off + e->fr_prev_done, b_off, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(h_rec, e->d_done + e->ph.fr_prev_done, b_rec, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(h_off, e->d_done_off + e->ph.fr_prev_done, b_off, hipMemcpyDeviceToHost, e->stream));
     if (to_host) {
-      const az_move_rec* src = (e->d_phase ? e->d_phase : e->d_stage) + e->fr_prev_recs;
+      const az_move_rec* src = (e->d_phase ? e->d_phase : e->d_stage) + e->ph.fr_prev_recs;
       HIPCHK(hipMemcpyAsync(h_mv, src, b_mv, hipMemcpyDeviceToHost, e->stream));
     }
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (pinned && to_host) memcpy(e->q_moves.data() + m0, h_mv, b_mv);
-    for (int i = 0; i < nd; ++i) {
-      az_game_rec g = h_rec[i];
-      g.first_move = (int32_t)((long long)m0 + h_off[i] - e->fr_prev_recs);
-      if (e->d_phase) { e->ph_games.push_back(g); e->ph_off.push_back(h_off[i]); }
-      e->q_games.push_back(g);
-      e->games_done++;
-      e->stats.games++;
-    }
-    if (e->d_phase) e->phase_n = nrec;
+    if (pinned && to_host) memcpy(e->ph.q_moves.data() + m0, h_mv, b_mv);
+    for (int i = 0; i < nd; ++i) queue_game(e, h_rec[i], (long long)m0 + h_off[i] - e->ph.fr_prev_recs, h_off[i]);
+    if (e->d_phase) e->ph.dev_n = nrec;
   }
-  e->fr_prev_done = done; e->fr_prev_recs = nrec;
-  e->stats.moves = fs.moves;
-  if (e->total_games >= 0) fs.next_game = std::min(fs.next_game, e->total_games);   // slots that asked in vain pushed the counter past the end
-  e->next_game = fs.next_game;
+  e->ph.fr_prev_done = done; e->ph.fr_prev_recs = nrec;
+  e->ph.stats.moves = fs.moves;
+  if (e->ph.ids.total_games >= 0) fs.next_game = std::min(fs.next_game, e->ph.ids.total_games);   // slots that asked in vain pushed the counter past the end
+  e->ph.ids.next_game = fs.next_game;
   if (!e->d_phase && (done > 0 || nrec > 0)) {                      // unbounded phase: the staging area has been drained -- and k_step_report
-    fs.resv = 0; e->fr_prev_done = 0; e->fr_prev_recs = 0;           // has set the device's word back already
+    fs.resv = 0; e->ph.fr_prev_done = 0; e->ph.fr_prev_recs = 0;           // has set the device's word back already
   }
   // retired slots (node pool or move records full; the kernels have taken them out of the counts): reported as aborted; the slot
-  // plays ONE replacement game, or the next game, with an empty tree -- as in lock step (move_round)
+  // plays ONE replacement game, or the next game, with an empty tree (retire); a slot that plays on joins its group again
   if (rp.retired > 0) {
-    std::vector<int> aslots, aslots_refill;
-    std::vector<uint32_t> agids, gid(G);
-    HIPCHK(hipMemcpyAsync(e->h_finished.data(), e->v.finished, sizeof(int) * G, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(gid.data(), e->v.game_id, sizeof(uint32_t) * G, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    for (int sl = 0; sl < G; ++sl) if (e->h_finished[sl] == 2) aslots.push_back(sl);
-    for (int sl : aslots) {
-      const int32_t id = (int32_t)gid[sl];
-      e->aborted_ids.push_back(id);
-      e->stats.aborted_games++;
-      if (!(id & AZ_REPLACEMENT_GAME_BIT)) {
-        aslots_refill.push_back(sl); agids.push_back((uint32_t)(id | AZ_REPLACEMENT_GAME_BIT));
-        fs.active[sl / e->gv[0].G]++;
-        continue;
-      }
-      e->games_done++; e->fr_given_up++;                             // the replacement overflowed too: given up, counted, reported
-      if (more_games(e)) {
-        aslots_refill.push_back(sl); agids.push_back((uint32_t)(e->first_game_id + e->next_game++));
-        fs.active[sl / e->gv[0].G]++;
-      }
-    }
-    fs.next_game = e->next_game;
+    Retirement R;
+    AZCHK(retire(e, true, &R));
+    for (int sl : R.slots) fs.active[sl / e->gv[0].G]++;
+    e->ph.fr_given_up += R.given_up;
+    fs.next_game = e->ph.ids.next_game;
     HIPCHK(hipMemsetAsync(e->v.finished, 0, sizeof(int) * G, e->stream));
-    AZCHK(start_games<Gm>(e, aslots_refill, agids, nullptr, 1, 1));  // a retired slot starts over with an empty tree
+    AZCHK(start_games<Gm>(e, R.slots, R.gids, nullptr, 1, 1));       // a retired slot starts over with an empty tree
     dirty = true;
   }
   if (dirty) {                                                      // the host changed the phase's words: only then do they go back
     HIPCHK(hipMemcpyAsync(e->d_fr, &fs, sizeof fs, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
   }
-  e->active_slots = 0;
-  for (int g = 0; g < AZ_MAX_GROUPS; ++g) { e->group_active[g] = g < e->ngroups ? std::max(0, fs.active[g]) : 0; e->active_slots += e->group_active[g]; }
-  e->h_fr_words[0] = e->fr_prev_done; e->h_fr_words[1] = e->active_slots;
+  e->ph.active_slots = 0;
+  for (int g = 0; g < AZ_MAX_GROUPS; ++g) { e->group_active[g] = g < e->ngroups ? std::max(0, fs.active[g]) : 0; e->ph.active_slots += e->group_active[g]; }
+  e->h_fr_words[0] = e->ph.fr_prev_done; e->h_fr_words[1] = e->ph.active_slots;
   AZCHK(vm_grow(e, fr_ahead(e)));                                   // what a slot can add before the next look
   e->report_fresh = !e->vm_rows && !dirty;                           // nothing launched since the report: its statistics sums are current
   return AZ_OK;
 }
 template <class Gm> static int fr_step(az_engine* e, int nwaves) {
   for (int w = 0; w < nwaves; ++w) {
-    if (e->active_slots == 0) break;
+    if (e->ph.active_slots == 0) break;
     // the device's own progress words, one wave late and read without synchronising: every game played, or nobody left searching?
     const int seen_done = ((volatile int*)e->h_fr_words)[0], seen_active = ((volatile int*)e->h_fr_words)[1];
-    if (seen_active == 0 || (e->total_games > 0 && e->d_phase && seen_done + e->fr_given_up >= e->total_games)) break;
+    if (seen_active == 0 || (e->ph.ids.total_games > 0 && e->d_phase && seen_done + e->ph.fr_given_up >= e->ph.ids.total_games)) break;
     AZCHK(wave<Gm>(e, e->ngroups, 0));
-    ++e->fr_since_look;
-    if (++e->fr_since_round >= e->fr_round_waves) AZCHK(fr_round<Gm>(e));
-    else if (e->fr_since_look >= e->fr_look_waves) AZCHK(fr_look(e));
+    ++e->ph.fr_since_look;
+    if (++e->ph.fr_since_round >= e->ph.fr_round_waves) AZCHK(fr_round<Gm>(e));
+    else if (e->ph.fr_since_look >= e->ph.fr_look_waves) AZCHK(fr_look(e));
   }
   return fr_round<Gm>(e);                                           // the call returns with the device idle and every finished game collectable
 }
 
 extern "C" int az_selfplay_step(az_engine* e, int32_t nwaves) {
   ENGINE(e);
-  if (!e->running) return fail(AZ_ERR_STATE, "az_selfplay_begin has not been called");
-  if (e->fr_on) { DISPATCH_GAME(e->cfg.game, AZCHK(fr_step<Gm>(e, nwaves))); return AZ_OK; }
+  if (!e->ph.running) return fail(AZ_ERR_STATE, "az_selfplay_begin has not been called");
+  if (e->ph.fr_on) { DISPATCH_GAME(e->cfg.game, AZCHK(fr_step<Gm>(e, nwaves))); return AZ_OK; }
   for (int w = 0; w < nwaves;) {
-    if (e->active_slots == 0) break;
-    const int chunk = std::min(nwaves - w, e->p.nsims - e->wave_in_move);      // up to the next move step
-    DISPATCH_GAME(e->cfg.game, AZCHK(run_waves<Gm>(e, e->ngroups, chunk, (uint32_t)e->wave_in_move)));
+    if (e->ph.active_slots == 0) break;
+    const int chunk = std::min(nwaves - w, e->p.nsims - e->ph.wave_in_move);      // up to the next move step
+    DISPATCH_GAME(e->cfg.game, AZCHK(run_waves<Gm>(e, e->ngroups, chunk, (uint32_t)e->ph.wave_in_move)));
     w += chunk;
-    if ((e->wave_in_move += chunk) == e->p.nsims) {
-      e->wave_in_move = 0;
+    if ((e->ph.wave_in_move += chunk) == e->p.nsims) {
+      e->ph.wave_in_move = 0;
       DISPATCH_GAME(e->cfg.game, AZCHK(move_round<Gm>(e)));
     }
   }
@@ -1701,7 +1674,7 @@ extern "C" int az_selfplay_step(az_engine* e, int32_t nwaves) {
 extern "C" int az_selfplay_active(az_engine* e, int32_t* n) {
   ENGINE(e);
   if (!n) return fail(AZ_ERR_BAD_ARG, "NULL");
-  *n = e->running ? e->active_slots : 0;
+  *n = e->ph.running ? e->ph.active_slots : 0;
   return AZ_OK;
 }
 
@@ -1718,51 +1691,42 @@ extern "C" int az_selfplay_get_stats(az_engine* e, az_selfplay_stats* s) {
     HIPCHK(hipStreamSynchronize(e->stream));
     for (size_t i = 0; i < e->stat_words; ++i) st[i & 3] += e->h_stat[i];
   }
-  e->stats.simulations = st[0]; e->stats.nodes_traversed = st[1]; e->stats.leaf_evals = st[2]; e->stats.evals_reused = st[3];
-  e->stats.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - e->t_begin).count();
-  *s = e->stats;
+  e->ph.stats.simulations = st[0]; e->ph.stats.nodes_traversed = st[1]; e->ph.stats.leaf_evals = st[2]; e->ph.stats.evals_reused = st[3];
+  e->ph.stats.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - e->ph.t_begin).count();
+  *s = e->ph.stats;
   return AZ_OK;
 }
 
 extern "C" int az_selfplay_collect(az_engine* e, az_trace_buf* out) {
   ENGINE(e);
   if (!out) return fail(AZ_ERR_BAD_ARG, "NULL");
-  const int64_t ng = (int64_t)e->q_games.size(), nm = (int64_t)e->q_moves.size();
-  if (!e->host_moves && e->d_phase) {                              // device-only phase: game records only, first_move = -1
-    if (ng > out->games_cap || (ng && !out->games)) return fail(AZ_ERR_CAPACITY, "trace buffer too small: need %lld games", (long long)ng);
-    std::vector<int> ord(ng);
-    for (int i = 0; i < ng; ++i) ord[i] = i;
-    std::sort(ord.begin(), ord.end(), [&](int a, int b) { return e->q_games[a].game_id < e->q_games[b].game_id; });
-    for (int64_t i = 0; i < ng; ++i) { out->games[i] = e->q_games[ord[i]]; out->games[i].first_move = -1; }
-    out->num_games = ng; out->num_moves = 0;
-    e->q_games.clear();
-    return AZ_OK;
-  }
-  if (ng > out->games_cap || nm > out->moves_cap || (ng && !out->games) || (nm && !out->moves))
-    return fail(AZ_ERR_CAPACITY, "trace buffer too small: need %lld games / %lld moves", (long long)ng, (long long)nm);
+  Phase& ph = e->ph;
+  const bool repack = ph.host_moves || !e->d_phase;                 // (device-only phase: game records only, first_move = -1)
+  const int64_t ng = (int64_t)ph.q_games.size(), nm = repack ? (int64_t)ph.q_moves.size() : 0;
+  if (ng > out->games_cap || (ng && !out->games) || (repack && (nm > out->moves_cap || (nm && !out->moves))))
+    return repack ? fail(AZ_ERR_CAPACITY, "trace buffer too small: need %lld games / %lld moves", (long long)ng, (long long)nm)
+                  : fail(AZ_ERR_CAPACITY, "trace buffer too small: need %lld games", (long long)ng);
   // sorted by game id, move records re-packed in that order
-  std::vector<int> ord(ng);
-  for (int i = 0; i < ng; ++i) ord[i] = i;
-  std::sort(ord.begin(), ord.end(), [&](int a, int b) { return e->q_games[a].game_id < e->q_games[b].game_id; });
+  const std::vector<int> ord = order_by_game_id(ph.q_games);
   int64_t m = 0;
   for (int64_t i = 0; i < ng; ++i) {
-    az_game_rec g = e->q_games[ord[i]];
-    memcpy(out->moves + m, e->q_moves.data() + g.first_move, sizeof(az_move_rec) * (size_t)g.num_moves);
-    g.first_move = (int32_t)m;
-    m += g.num_moves;
+    az_game_rec g = ph.q_games[ord[i]];
+    if (repack) memcpy(out->moves + m, ph.q_moves.data() + g.first_move, sizeof(az_move_rec) * (size_t)g.num_moves);
+    g.first_move = repack ? (int32_t)m : -1;
+    if (repack) m += g.num_moves;
     out->games[i] = g;
   }
   out->num_games = ng; out->num_moves = nm;
-  e->q_games.clear(); e->q_moves.clear();
+  ph.q_games.clear(); ph.q_moves.clear();                           // (a device-only phase has queued no move records)
   return AZ_OK;
 }
 
 extern "C" int az_selfplay_aborted(az_engine* e, int32_t* game_ids, int32_t cap, int32_t* n) {
   ENGINE(e);
   if (!n || (cap > 0 && !game_ids)) return fail(AZ_ERR_BAD_ARG, "NULL");
-  *n = (int32_t)e->aborted_ids.size();
+  *n = (int32_t)e->ph.aborted_ids.size();
   if (*n > cap) return cap == 0 ? AZ_OK : fail(AZ_ERR_CAPACITY, "%d aborted games, room for %d", *n, cap);
-  for (int i = 0; i < *n; ++i) game_ids[i] = e->aborted_ids[i];
+  for (int i = 0; i < *n; ++i) game_ids[i] = e->ph.aborted_ids[i];
   return AZ_OK;
 }
 
@@ -1770,14 +1734,14 @@ extern "C" int az_selfplay_end(az_engine* e) {
   ENGINE(e);
   e->p.retire = 0;
   split_register(e, 0);
-  if (!e->running) return AZ_OK;
+  if (!e->ph.running) return AZ_OK;
   AZCHK(reset_wave_state(e));                                      // an unfinished simulation (stepping form stopped mid-move) is dropped
   hipLaunchKernelGGL(k_slot_records, dim3((e->v.G + 255) / 256), dim3(256), 0, e->stream, e->v, (int)SR_CLEAR_ACTIVE);
   e->report_fresh = false;
   HIPCHK(hipStreamSynchronize(e->stream));
-  e->running = false;
-  e->active_slots = 0;
-  e->fr_on = false;
+  e->ph.running = false;
+  e->ph.active_slots = 0;
+  e->ph.fr_on = false;
   for (int g = 0; g < e->ngroups; ++g) { e->gv[g].run_k = 0; e->gv[g].fr = 0; e->gv[g].fr_active = nullptr; }
   if (e->ngroups == 1 && e->gs[0] != e->stream) {                    // back to the engine's one stream
     HIPCHK(hipStreamSynchronize(e->gs[0])); for (int i = 1; i < 4; ++i) HIPCHK(hipStreamSynchronize(e->fr_s[i]));
@@ -1793,15 +1757,13 @@ extern "C" int az_selfplay_run(az_engine* e, int32_t num_games, int32_t first_ga
   if (out->games_cap < num_games) return fail(AZ_ERR_CAPACITY, "games_cap %lld < num_games %d", (long long)out->games_cap, num_games);
   // out->moves == NULL: device-only phase -- the move records stay in HBM for az_memory_push_engine / az_comm_gather_push,
   // only the game records (56 B per game) come back
-  e->host_moves = out->moves != nullptr;
-  const int bst = az_selfplay_begin(e, num_games, first_game_id);
-  if (bst != AZ_OK) { e->host_moves = true; return bst; }
+  AZCHK(selfplay_begin(e, num_games, first_game_id, out->moves != nullptr));
   int reported = 0;
   int st = AZ_OK;
-  while (e->games_done < num_games) {
-    st = az_selfplay_step(e, e->fr_on ? e->fr_round_waves : e->p.nsims);
+  while (e->ph.games_done < num_games) {
+    st = az_selfplay_step(e, e->ph.fr_on ? e->ph.fr_round_waves : e->p.nsims);
     if (st != AZ_OK) break;
-    if (cb) for (; reported < e->games_done; ++reported) cb(user);   // game_simulated()
+    if (cb) for (; reported < e->ph.games_done; ++reported) cb(user);   // game_simulated()
   }
   if (st == AZ_OK && stats) st = az_selfplay_get_stats(e, stats);
   std::string keep = g_err;
@@ -1810,7 +1772,6 @@ extern "C" int az_selfplay_run(az_engine* e, int32_t num_games, int32_t first_ga
   const int cst = az_selfplay_collect(e, out);
   if (st == AZ_OK) { st = cst; keep = g_err; }
   az_selfplay_end(e);
-  e->host_moves = true;
   if (st != AZ_OK) g_err = keep;
   return st;
 }
@@ -1915,23 +1876,7 @@ static int arena_run(az_engine* ec, az_engine* eb, int num_games, int first_game
       AZCHK(explore_begin<Gm>(eng[k], slots[k], roots[k], gids[k], mvs[k], nullptr, &nga[k]));
       AZCHK(vm_grow(eng[k], (long long)eng[k]->p.nsims + 2));       // mapped-on-demand pool: room for this ply's explore! (a no-op for plain pools)
     }
-    // (round 6: the explores run ahead -- explore_begin -- and a player is done when its device reports no busy slot: looked at every 16 waves)
-    bool done[2] = {nga[0] == 0, nga[1] == 0};
-    const int nsims_k[2] = {kind[0] == PL_MCTS ? ec->p.nsims : 0, kind[1] == PL_MCTS ? eb->p.nsims : 0};
-    for (int i = 0; i < std::max(nsims_k[0], nsims_k[1]) + 1 && !(done[0] && done[1]); ++i) {
-      for (int k = 0; k < 2; ++k) if (!done[k]) {
-        const bool ahead = eng[k]->gv[0].run_k > 0;
-        if (i >= eng[k]->p.nsims + (ahead ? 1 : 0)) { done[k] = true; continue; }
-        HIPCHK(hipSetDevice(eng[k]->device)); AZCHK(wave<Gm>(eng[k], nga[k], (uint32_t)i));
-      }
-      if ((i & 15) == 15)
-        for (int k = 0; k < 2; ++k) if (!done[k] && eng[k]->gv[0].run_k > 0) {
-          HIPCHK(hipSetDevice(eng[k]->device)); AZCHK(sync_groups(eng[k])); HIPCHK(hipStreamSynchronize(eng[k]->stream));
-          bool busy = false;
-          for (int g = 0; g < nga[k]; ++g) busy = busy || (eng[k]->group_active[g] > 0 && ((volatile int*)eng[k]->h_busy)[g] != 0);
-          done[k] = !busy;
-        }
-    }
+    AZCHK(explore_loop<Gm>(2, eng, nga));                           // (the explores run ahead -- explore_begin -- where they can)
     for (int k = 0; k < 2; ++k) {
       HIPCHK(hipSetDevice(eng[k]->device));
       if (kind[k] == PL_MINMAX) {
@@ -2015,7 +1960,7 @@ extern "C" int az_arena_run(az_engine* contender, az_engine* baseline, int32_t n
   ENGINE(contender);
   ENGINE(baseline);
   if (contender == baseline) return fail(AZ_ERR_BAD_ARG, "contender and baseline must be two engines (two trees per worker, play.jl:248-251)");
-  if (contender->running || baseline->running) return fail(AZ_ERR_STATE, "self-play in progress");
+  if (contender->ph.running || baseline->ph.running) return fail(AZ_ERR_STATE, "self-play in progress");
   if (contender->cfg.game != baseline->cfg.game) return fail(AZ_ERR_BAD_ARG, "the two engines play different games");
   if (num_games < 1) return fail(AZ_ERR_BAD_ARG, "num_games must be >= 1");
   if (baseline->v.G < std::min(contender->v.G, (int)num_games)) return fail(AZ_ERR_BAD_ARG, "baseline engine has fewer workers (%d) than the arena needs (%d)", baseline->v.G, std::min(contender->v.G, (int)num_games));

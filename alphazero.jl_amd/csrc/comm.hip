@@ -246,26 +246,19 @@ extern "C" int az_comm_gather_push(az_comm* c, az_engine* e, az_memory* m, doubl
   if (!e) local = fail(AZ_ERR_BAD_ARG, "NULL engine");
   else if (e->device != c->device || (m && m->device != c->device)) local = fail(AZ_ERR_BAD_ARG, "engine / memory / communicator are on different devices");
   else if (m && m->game != e->cfg.game) local = fail(AZ_ERR_BAD_ARG, "memory and engine differ in game");
-  else if (e->running) local = fail(AZ_ERR_STATE, "self-play in progress");
+  else if (e->ph.running) local = fail(AZ_ERR_STATE, "self-play in progress");
   else if (!e->d_phase) local = fail(AZ_ERR_STATE, "the engine holds no device-resident phase (az_selfplay_run first)");
   else local = sync_all(e);
   const Verdict own(local);
   const auto t0 = std::chrono::steady_clock::now();
   const int W = c->world;
-  const size_t ng = local == AZ_OK ? e->ph_games.size() : 0;
-  std::vector<int> ord(ng);
-  for (size_t i = 0; i < ng; ++i) ord[i] = (int)i;
-  std::sort(ord.begin(), ord.end(), [&](int a, int b) { return e->ph_games[a].game_id < e->ph_games[b].game_id; });
-  std::vector<long long> src(ng), dst(ng);
-  std::vector<int> cnt(ng);
-  std::vector<az_game_rec> gsend(ng);
+  std::vector<long long> src, dst;
+  std::vector<int> cnt;
+  std::vector<az_game_rec> gsend;
+  if (local == AZ_OK) phase_games_by_id(e, &src, &cnt, &gsend);
+  const size_t ng = gsend.size();
   long long nm = 0;
-  for (size_t i = 0; i < ng; ++i) {
-    const az_game_rec& r = e->ph_games[ord[i]];
-    src[i] = e->ph_off[ord[i]]; dst[i] = nm; cnt[i] = r.num_moves;
-    gsend[i] = r; gsend[i].first_move = (int32_t)nm;
-    nm += r.num_moves;
-  }
+  for (size_t i = 0; i < ng; ++i) { dst.push_back(nm); gsend[i].first_move = (int32_t)nm; nm += cnt[i]; }
   // 1. counts and status of every rank
   const long long hc[3] = {(long long)ng, nm, (long long)local};
   std::vector<long long> all;

@@ -25,6 +25,7 @@
 #include "env.h"
 #include "games.h"
 #include "net_layout.h"
+#include "phase_books.h"
 #include "resnet.h"
 #include "resnet16.h"
 #include "resnet16b.h"
@@ -106,6 +107,26 @@ enum TowerForm : int {
   TW_MIXED = -1    // k_tower16x2m: not an AZHIP_TOWER value -- wave_net_f launches it where AZHIP_TOWER_MIXED allows
 };
 // AZ_MAX_GROUPS: tree.h
+// Everything that describes ONE self-play phase; the default value means "no phase".  az_selfplay_begin assigns a fresh record, so no
+// member carries over; az_selfplay_end leaves it (statistics, aborted ids, uncollected and device-resident games are read after it).
+// Buffers, streams, events and what explores outside a phase use as well (group_active, pending, wave_par) are az_engine's.
+struct Phase {
+  bool running = false;
+  bool fr_on = false;                // free-running (az_engine_cfg.lock_step = 0): the device hands out game ids and moves by itself
+  bool host_moves = true;            // the caller wants the move records on the host (false: az_selfplay_run with out->moves == NULL)
+  GameIds ids;                       // phase_books.h; a free-running phase's device counter (FRState::next_game) is mirrored at every look
+  int games_done = 0, wave_in_move = 0, active_slots = 0;
+  int fr_k = 0, fr_kbg = 0, fr_round_waves = 0;  // simulations a slot may select per wave launch / per background launch (DView::run_k); waves between two looks of the host
+  int fr_prev_done = 0, fr_since_round = 0, fr_given_up = 0; long long fr_prev_recs = 0;
+  int fr_look_waves = 0, fr_since_look = 0;      // mapped-on-demand pool: waves between two looks at the node counts (fr_look, azhip.hip; <= fr_round_waves) / since the last one
+  std::vector<az_game_rec> q_games;  // finished, not yet collected (az_selfplay_collect) ...
+  std::vector<az_move_rec> q_moves;  // ... and their move records where they come to the host
+  std::vector<az_game_rec> dev_games;   // a bounded phase's finished games, in finishing order ...
+  std::vector<int64_t> dev_off; int64_t dev_n = 0;   // ... the offset of each one's first move record in d_phase; records in use
+  std::vector<int32_t> aborted_ids;  // games retired because their slot ran out of nodes / move records (az_selfplay_aborted)
+  az_selfplay_stats stats = {};
+  std::chrono::steady_clock::time_point t_begin;
+};
 struct ProfRec { hipEvent_t a = nullptr, b = nullptr; int cls = 0; };
 // Every member has its initial value here: az_engine_create builds the record step by step and az_engine_destroy takes it apart at
 // any point in between.  DView / DParams go to the kernels by value and stay trivially copyable (memset by the step that fills them).
@@ -154,7 +175,6 @@ struct az_engine {
   // evaluation cache (tree.h ECEnt): one table per engine = per network; az_net_set_params empties it
   ECEnt* d_ec = nullptr; uint32_t ec_mask = 0; uint32_t ec_seq = 0; int* d_ec_claim = nullptr; float* d_Phit = nullptr; float* d_Vhit = nullptr;
   size_t stat_words = 0; std::vector<long long> h_stat;   // per-workgroup statistics accumulators of k_tree (DView::stat), summed on request
-  std::vector<int32_t> aborted_ids;   // games retired because their slot ran out of nodes / move records (az_selfplay_aborted)
   std::vector<void*> net_allocs;   // device copies of the packed network (replaced by az_net_set_params)
   // network
   bool net_loaded = false;
@@ -181,9 +201,7 @@ struct az_engine {
   char* d_nodebuf = nullptr;
   int* d_visits = nullptr;
   int io_cap = 0;
-  // self-play state
-  bool running = false;
-  int total_games = 0, next_game = 0, first_game_id = 0, games_done = 0, wave_in_move = 0, active_slots = 0;
+  Phase ph;                      // the self-play phase in progress, or the last one's leavings (above)
   // hipGraphs of wave pairs (env.use_graphs, one slot group only): key = upper bound of the leaves of a launch (decides the tower
   // kernel and its grid); rebuilt after az_net_set_params (new device pointers)
   std::map<int, hipGraphExec_t> wave_graphs;
@@ -192,16 +210,12 @@ struct az_engine {
   int group_active[AZ_MAX_GROUPS] = {};   // active slots per slot group (host count; bounds the leaves of a network launch)
   // (r6) free-running phases (az_engine_cfg.lock_step = 0; tree.h k_tree / k_move_fr): the device hands out game ids and writes
   // finished games into the phase buffer itself; the host looks every fr_round_waves waves (fr_round, azhip.hip)
-  bool fr_on = false;                // the phase in progress is free-running
-  int fr_k = 0, fr_kbg = 0, fr_round_waves = 0;  // simulations a slot may select per wave launch / per background launch (DView::run_k); waves between two looks of the host
   hipStream_t fr_s[4] = {}; hipEvent_t fr_ev[4] = {};   // one slot group: the streams and events of its free-running phases (gs[0] = gt[0] = fr_s[0] meanwhile): [0] the wave, [1] background search, [2] move step, [3] k_set_word behind a tower form that does not raise the stop word itself
   FRState* d_fr = nullptr; az_game_rec* d_done = nullptr; long long* d_done_off = nullptr; int done_cap = 0;
   int* h_busy = nullptr; int* d_busy = nullptr;      // [AZ_MAX_GROUPS] host-mapped: slots of each group still inside an explore! that runs ahead (DView::busy_host); -1 = no report
   int* d_bg_stop = nullptr; int bg_seq = 0; bool bg_signal = false;   // the background search's stop word: raised to bg_seq by the wave's tower near its end (paired forms) or by k_set_word behind it (bg_signal: this wave has one)
   int* h_fr_words = nullptr; int* d_fr_words = nullptr;  // host-mapped: finished games / searching slots as of the previous wave (FRArgs::host_words)
-  int fr_prev_done = 0, fr_since_round = 0, fr_given_up = 0; long long fr_prev_recs = 0;
-  int fr_look_waves = 0, fr_since_look = 0;      // mapped-on-demand pool: waves between two looks at the node counts (fr_look, azhip.hip; <= fr_round_waves) / since the last one
-  std::vector<az_game_rec> h_done; std::vector<long long> h_done_off;
+  std::vector<az_game_rec> h_done; std::vector<long long> h_done_off;   // a look's finished games where they outgrow h_fetch
   // the step report (tree.h StepReport, pinned and host-mapped: k_step_report writes it behind the wave, fr_round reads it after one
   // synchronisation); report_fresh: no kernel has been launched since it was written, so az_selfplay_get_stats may take its sums from it
   // (report_fresh holds only while EVERY launch that can write the statistics accumulators clears it: today that is k_tree alone, and all
@@ -209,15 +223,9 @@ struct az_engine {
   // outside the macro that touches DView::stat must clear it too.)
   StepReport* h_report = nullptr; StepReport* d_report = nullptr; bool report_fresh = false;
   char* h_fetch = nullptr;           // pinned staging of a look's finished games: records, offsets, move records (FETCH_BYTES; larger batches go straight to the vectors)
-  std::vector<az_game_rec> q_games;
-  std::vector<az_move_rec> q_moves;
   // device-resident records of the current phase (az_selfplay_run / begin with num_games > 0): the move records of every
-  // finished game stay in HBM (d_phase, game after game in finishing order)
-  az_move_rec* d_phase = nullptr; int64_t phase_cap = 0, phase_n = 0; bool host_moves = true;
-  std::vector<az_game_rec> ph_games;
-  std::vector<int64_t> ph_off;       // offset of each ph_games entry's first move record in d_phase
-  az_selfplay_stats stats = {};
-  std::chrono::steady_clock::time_point t_begin;
+  // finished game stay in HBM (d_phase, game after game in finishing order; Phase::dev_games says where)
+  az_move_rec* d_phase = nullptr; int64_t phase_cap = 0;
   // profiling
   bool prof_on = false;
   int prof_mask = 0;             // 0 = every kernel class, else bit per az_kernel_class
@@ -266,7 +274,7 @@ inline int sync_groups(az_engine* e) {
     HIPCHK(hipStreamSynchronize(e->gt[g]));
     HIPCHK(hipStreamSynchronize(e->gs[g]));
   }
-  if (e->fr_on && e->fr_s[1]) for (int i = 1; i < 4; ++i) HIPCHK(hipStreamSynchronize(e->fr_s[i]));   // one slot group, free-running: the side stream (move step, background search)
+  if (e->ph.fr_on && e->fr_s[1]) for (int i = 1; i < 4; ++i) HIPCHK(hipStreamSynchronize(e->fr_s[i]));   // one slot group, free-running: the side stream (move step, background search)
   return AZ_OK;
 }
 inline int sync_all(az_engine* e) {
@@ -315,6 +323,14 @@ inline int prof_end(az_engine* e, hipStream_t st, int cls) {
 #define ENGINE(e)                                              \
   if (!(e)) return fail(AZ_ERR_BAD_ARG, "engine is NULL");      \
   HIPCHK(hipSetDevice((e)->device))
+
+// the engine's last bounded phase as memory_push_device takes it: game k in id order (games[k], when asked for) = d_phase[first[k] .. + cnt[k])
+inline void phase_games_by_id(const az_engine* e, std::vector<long long>* first, std::vector<int>* cnt, std::vector<az_game_rec>* games = nullptr) {
+  for (int i : order_by_game_id(e->ph.dev_games)) {
+    first->push_back(e->ph.dev_off[(size_t)i]); cnt->push_back(e->ph.dev_games[(size_t)i].num_moves);
+    if (games) games->push_back(e->ph.dev_games[(size_t)i]);
+  }
+}
 
 // azhip.hip: waits for the engine's streams and turns a device-side error code (tree.h DERR_*, resnet16.h DERR_EXCHANGE) into a status
 int check_device_error(az_engine* e);

@@ -332,16 +332,12 @@ extern "C" int az_memory_push(az_memory* m, const az_trace_buf* tr, double gamma
 extern "C" int az_memory_push_engine(az_memory* m, az_engine* e, double gamma) {
   MEMORY(m);
   if (!e) return fail(AZ_ERR_BAD_ARG, "engine is NULL");
-  if (e->running) return fail(AZ_ERR_STATE, "self-play in progress");
+  if (e->ph.running) return fail(AZ_ERR_STATE, "self-play in progress");
   if (e->cfg.game != m->game || e->device != m->device) return fail(AZ_ERR_BAD_ARG, "memory and engine differ in game or device");
   if (!e->d_phase) return fail(AZ_ERR_STATE, "the engine holds no device-resident phase (az_selfplay_run / az_selfplay_begin with num_games > 0 first)");
-  const size_t ng = e->ph_games.size();
-  std::vector<int> ord(ng);
-  for (size_t i = 0; i < ng; ++i) ord[i] = (int)i;
-  std::sort(ord.begin(), ord.end(), [&](int a, int b) { return e->ph_games[a].game_id < e->ph_games[b].game_id; });
-  std::vector<long long> first(ng);
-  std::vector<int> cnt(ng);
-  for (size_t i = 0; i < ng; ++i) { first[i] = e->ph_off[ord[i]]; cnt[i] = e->ph_games[ord[i]].num_moves; }
+  std::vector<long long> first;
+  std::vector<int> cnt;
+  phase_games_by_id(e, &first, &cnt);
   AZCHK(sync_all(e));
   return memory_push_device(m, e->d_phase, first, cnt, gamma);
 }
@@ -640,7 +636,7 @@ extern "C" int az_learning_status(az_engine* e, az_dataset* d, double l2_regular
                                   double rewards_renormalization, int64_t loss_computation_batch_size, az_learning_status_t* out) {
   ENGINE(e);
   if (!d || !out) return fail(AZ_ERR_BAD_ARG, "NULL argument");
-  if (e->running) return fail(AZ_ERR_STATE, "self-play in progress");
+  if (e->ph.running) return fail(AZ_ERR_STATE, "self-play in progress");
   if (!oracle_is_net(e->cfg) || !e->net_loaded) return fail(AZ_ERR_STATE, "az_net_set_params has not been called");
   if (d->game != e->cfg.game || d->device != e->device) return fail(AZ_ERR_BAD_ARG, "data set and engine differ in game or device");
   if (d->n < 1) return fail(AZ_ERR_BAD_ARG, "empty data set");

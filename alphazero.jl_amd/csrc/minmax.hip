@@ -38,7 +38,7 @@ extern "C" int az_minmax_policy(const double* q, int32_t n, double tau, double* 
 extern "C" int az_engine_set_minmax(az_engine* e, const az_minmax_cfg* cfg) {
   if (cfg) AZCHK(check_minmax_cfg(cfg));
   ENGINE(e);
-  if (e->running) return fail(AZ_ERR_STATE, "self-play in progress");
+  if (e->ph.running) return fail(AZ_ERR_STATE, "self-play in progress");
   if (!cfg) { e->mm_on = false; return AZ_OK; }
   AZCHK(check_minmax_game(e));
   e->mm = *cfg;

@@ -163,7 +163,7 @@ template <class Gm> static int wave_simple(az_engine* e, int g, bool split, int 
   if (e->bg_signal) AZCHK(raise_stop_word(e, sn));
   if (split) {
     HIPCHK(hipEventRecord(e->ev_net[g], sn));
-    if (!e->fr_on) HIPCHK(hipStreamWaitEvent(st, e->ev_net[g], 0));   // (a free-running wave_group waits for ev_net at its end)
+    if (!e->ph.fr_on) HIPCHK(hipStreamWaitEvent(st, e->ev_net[g], 0));   // (a free-running wave_group waits for ev_net at its end)
   }
   return AZ_OK;
 }
@@ -378,7 +378,7 @@ template <class Gm, int F> static int wave_net_f(az_engine* e, int g, bool split
   int npick = N;
   if (v.nleaf_host) { const int seen = ((volatile int*)e->h_nleaf)[g]; if (seen >= 0) npick = std::max(1, std::min(N, seen + seen / 8 + 8)); }
   int tw = pick_tower<Gm, F>(e, npick, N);
-  if (tw == TW_P21 && e->fr_on && e->ngroups == 1 && e->env.tower_pick == 0 && e->fr_kbg > 0 && v.nleaf_host && v.needy_host) {
+  if (tw == TW_P21 && e->ph.fr_on && e->ngroups == 1 && e->env.tower_pick == 0 && e->ph.fr_kbg > 0 && v.nleaf_host && v.needy_host) {
     // The paired tower beside the side streams' kernels (resnet16.h k_tower16x2c): a CU that holds a workgroup of the background search
     // (256 threads = 32 Connect-Four slots of the needy list) takes no workgroup of the 198-register form for as long as that search
     // runs.  Measured: in the steady state (~8 such workgroups on average, more in some waves) the launch gains a round of workgroups
@@ -420,7 +420,7 @@ template <class Gm, int F> static int wave_net_f(az_engine* e, int g, bool split
   // Free-running phase: the heads follow the tower on the network stream and the tree stream is NOT made to wait here -- the caller
   // (wave_group, azhip.hip) first queues the group's move step and its background search behind k_tree, then the wait for ev_net: both
   // run under this tower.
-  const bool fr = e->fr_on && split;
+  const bool fr = e->ph.fr_on && split;
   if (e->bg_signal && !tower_stops) {
     // a form that does not raise the word itself.  The tower has run: the background search of this wave winds up while the heads run.  The
     // word is set from a stream of its own behind an event (a one-thread launch IN the wave's stream sat 7.6 us between tower and heads)
