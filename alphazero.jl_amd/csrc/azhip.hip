@@ -50,7 +50,7 @@ extern "C" int az_abi_struct_size(int32_t which) {
 // Streams of this process that may launch split towers (k_tower16s) on a device at the same time: the sum of the slot groups of
 // all engines with 128-filter fp32 networks that have a search IN PROGRESS (between az_selfplay_begin / explore_begin and their
 // end: an arena drives two engines side by side; an idle engine -- a host keeps them cached between phases -- holds no CU and is
-// not counted: counting it cost the arena of a training iteration 12.7 s instead of 5.6).  pick_tower keeps the split only
+// not counted: counting it cost the arena of a training iteration 12.7 s instead of 5.6).  choose_tower (tower_choice.h) keeps the split only
 // while all of them together fit the chip, so that every pair of workgroups is co-resident.
 static std::mutex g_split_mu;
 static std::map<int, int> g_split_streams;

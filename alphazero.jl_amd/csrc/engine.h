@@ -30,6 +30,7 @@
 #include "resnet16.h"
 #include "resnet16b.h"
 #include "simplenet.h"
+#include "tower_choice.h"
 #include "tree.h"
 
 // ------------------------------------------------------------------------------- errors
@@ -91,21 +92,6 @@ inline SimpleLayout simple_layout(const GameInfo& gi, const az_simplenet_hp& h) 
 inline bool oracle_is_net(const az_engine_cfg& c) { return c.oracle == AZ_ORACLE_RESNET || c.oracle == AZ_ORACLE_SIMPLENET; }
 
 // ------------------------------------------------------------------------------- engine
-// The tower forms.  The values are the AZHIP_TOWER numbers (az_engine::env.tower_pick); net_impl.h holds one descriptor per form
-// (kernel, layout, geometry table, availability, name, tower_hist bucket) and pick_tower, which chooses among them.
-enum TowerForm : int {
-  TW_AUTO = 0,     // AZHIP_TOWER unset: pick_tower chooses per launch
-  TW_SPLIT = 2,    // k_tower16s: two workgroups per board tile (fp32, 128 filters, where the pairs can be co-resident)
-  TW_NTS = 3,      // k_tower16 / k_tower16b with the game's latency tile count NTS
-  TW_NTM = 7,      // k_tower16 with the game's exact-fit tile count NTM (fp32, games that have one)
-  TW_11 = 16,      // k_tower16 / k_tower16b with 11 row tiles
-  TW_P19 = 19,     // k_tower16x2 with 10 + 9 row tiles (fp32, 64 filters)
-  TW_P21C = 20,    // k_tower16x2c: 11 + 10 row tiles within 176 registers (fp32, 64 filters)
-  TW_P21 = 21,     // k_tower16x2 with 11 + 10 row tiles (fp32, 64 filters)
-  TW_B22 = 22,     // k_tower16b with 22 row tiles (bf16, 128 filters)
-  TW_32 = 32,      // k_tower (32x32x2 MFMA, every tap; fp32)
-  TW_MIXED = -1    // k_tower16x2m: not an AZHIP_TOWER value -- wave_net_f launches it where AZHIP_TOWER_MIXED allows
-};
 // AZ_MAX_GROUPS: tree.h
 // Everything that describes ONE self-play phase; the default value means "no phase".  az_selfplay_begin assigns a fresh record, so no
 // member carries over; az_selfplay_end leaves it (statistics, aborted ids, uncollected and device-resident games are read after it).
@@ -153,7 +139,7 @@ struct az_engine {
   // (r4) a split tower whose exchange gives up degrades instead of failing the phase (azhip.hip recover_split)
   int* d_xerr = nullptr; int* d_skipped = nullptr;   // [AZ_MAX_GROUPS + 1] exchange words, [..][2] counters of idle k_tree launches (DView::xerr / skipped)
   int* h_needy = nullptr; int* d_needy = nullptr;    // [AZ_MAX_GROUPS] host-mapped: slots each group's previous wave launch left to the background search (tree.h DView::needy_host)
-  int* h_nleaf = nullptr; int* d_nleaf = nullptr;    // [AZ_MAX_GROUPS] host-mapped: network batch of each group's previous wave (k_tree writes, pick_tower's estimate reads); -1 = nothing reported yet
+  int* h_nleaf = nullptr; int* d_nleaf = nullptr;    // [AZ_MAX_GROUPS] host-mapped: network batch of each group's previous wave (k_tree writes, choose_wave_tower's estimate reads); -1 = nothing reported yet
   int* h_xflag = nullptr; int* d_xflag = nullptr;    // host-mapped word the kernel sets when an exchange gives up; looked at before every launch
   bool split_off = false;        // the split is disabled for this engine after the first time
   long long xch_launches = 0;    // split launches so far (env.xch_fail_at: the n-th loses a partner)

@@ -1,5 +1,5 @@
-// net_impl.h -- launch logic of the network kernels (resnet.h, resnet16.h), templated on the game: which tower kernel
-// serves a launch (pick_tower) and the launches themselves.  Instantiated once per game in net_c4.hip / net_ttt.hip /
+// net_impl.h -- the launches of the network kernels (resnet.h, resnet16.h), templated on the game: the tower forms' descriptors and
+// the launch of what tower_choice.h chooses among them.  Instantiated once per game in net_c4.hip / net_ttt.hip /
 // net_mancala.hip (three translation units, so that the big fully unrolled tower kernels compile in parallel);
 // net.hip dispatches on the engine's game.
 #pragma once
@@ -7,16 +7,16 @@
 
 // ---- the tower forms --------------------------------------------------------------------------------------------------------
 // One descriptor per form, templated on the game and the filter count, states everything a launch needs:
-//   ID, OK   its TowerForm (engine.h) and whether the form exists for this game and F
-//   BF16     which network it serves (pick_tower returns TW_NTS / TW_11 for both: the engine's network decides between the two descriptors)
-//   T        its layout struct: T::TB boards per workgroup, T::THREADS, T::BYTES of LDS, T::Geo / T::GEO its row permutation table
+//   ID, OK   its TowerForm (tower_choice.h) and whether the form exists for this game and F
+//   BF16     which network it serves (choose_tower returns TW_NTS / TW_11 for both: the engine's network decides between the two descriptors)
+//   T        its layout struct: T::TB boards and T::RPAD rows per workgroup, T::THREADS, T::BYTES of LDS, T::Geo / T::GEO its row permutation table
 //   K        its kernel, for FROM_PLANES false and true;  net(e): the fragments that kernel takes
 //   frac()   the fraction of a 3x3 convolution's (row tile, tap) products it executes (Geo16 skips the products whose tap falls off the
 //            board for a whole tile; k_tower computes every tap).  az_prof.exec_units weighs a launch's boards with it, so that a roofline
 //            can count the work DONE instead of the dense convolution's
 //   HIST     its tower_hist bucket;  name(): its az_net_last_kernel spelling
 //   STOP     its kernel takes the background search's stop word (TowerIn::stop) and raises it from its last round of workgroups
-// set_kernel_attrs_f and launch_tower walk Forms<Gm, F>; a form's properties are stated nowhere else.
+// set_kernel_attrs_f, upload_geos, tower_table and launch_tower walk Forms<Gm, F>; a form's properties are stated nowhere else.
 template <class T> static constexpr double geo_frac() { return T::Geo::tab.cost / (9.0 * (T::RPAD / 16)); }
 // what the k_tower16 family of the fp32 network shares
 template <class T_, int ID_, bool OK_, int HIST_> struct FormFp32 {
@@ -55,7 +55,7 @@ template <class Gm, int F> struct FormMixed : FormFp32<T16P<Gm, F>, TW_MIXED, F 
   static void name(char* s, size_t n, const char* g) { snprintf(s, n, "k_tower16x2m<%s,%d>", g, F); }
 };
 template <class Gm, int F> struct Form32 {
-  struct T { static constexpr int TB = TOWER_ROWS / Gm::P, THREADS = TowerCfg<F>::THREADS, BYTES = TowerLds<F>::BYTES; };
+  struct T { static constexpr int RPAD = TOWER_ROWS, TB = RPAD / Gm::P, THREADS = TowerCfg<F>::THREADS, BYTES = TowerLds<F>::BYTES; };
   static constexpr int ID = TW_32, HIST = 3;
   static constexpr bool OK = true, BF16 = false, STOP = false;
   template <bool FP> static constexpr auto K = &k_tower<Gm, F, FP>;
@@ -77,6 +77,16 @@ template <class Gm, int F> using Forms = FormList<
     FormSplit<Gm, F>, Form16<Gm, F, NTS<Gm>, TW_NTS, 1>, Form16<Gm, F, NTM<Gm>, TW_NTM, 3>, Form16<Gm, F, 11, TW_11, 2>,
     FormPaired<Gm, F, 11, 10, TW_P21>, FormPaired<Gm, F, 10, 9, TW_P19>, FormPairedC<Gm, F>, Form32<Gm, F>,
     Form16b<Gm, F, NTS<Gm>, TW_NTS, 1>, Form16b<Gm, F, 11, TW_11, 2>, Form16b<Gm, F, 22, TW_B22, 3>>;
+// what the choice (tower_choice.h) knows of form D, and of all forms of one game and F
+template <class D, int F> static constexpr TowerFacts facts() {
+  if constexpr (!D::OK) return TowerFacts{D::ID, D::BF16};
+  else return TowerFacts{D::ID, D::BF16, true, D::STOP, D::T::TB, D::T::RPAD, D::frac(), D::BF16 && F == 64 ? 2 : 1};
+}
+template <class Gm, int F, class... D> static TowerTable tower_table(FormList<D...>) {
+  static constexpr TowerFacts forms[] = {facts<D, F>()...};
+  return TowerTable{forms, (int)sizeof...(D), F, Gm::P, Gm::APAD};
+}
+template <class Gm, int F> static TowerTable tower_table() { return tower_table<Gm, F>(Forms<Gm, F>{}); }
 
 template <class D, bool FP> static int set_form_attr() {
   if constexpr (D::OK) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(D::template K<FP>), hipFuncAttributeMaxDynamicSharedMemorySize, D::T::BYTES));
@@ -108,6 +118,16 @@ template <class T> static int upload_geo(az_engine* e) {
   HIPCHK(hipStreamSynchronize(e->stream));
   e->d_geo[T::GEO] = d;
   return AZ_OK;
+}
+// ... of every form that exists (k_tower has no table)
+template <class D> static int upload_form_geo(az_engine* e) {
+  if constexpr (D::OK && D::ID != TW_32) AZCHK((upload_geo<typename D::T>(e)));
+  return AZ_OK;
+}
+template <class... D> static int upload_geos(az_engine* e, FormList<D...>) {
+  int r = AZ_OK;
+  (void)(((r = upload_form_geo<D>(e)) == AZ_OK) && ...);
+  return r;
 }
 template <class G> static int geometry_out(uint16_t* out, int64_t cap, int* rows, int* products) {
   if (cap < (int64_t)10 * G::RPAD) return fail(AZ_ERR_CAPACITY, "need %d words", 10 * G::RPAD);
@@ -150,22 +170,38 @@ static int launch_simple(az_engine* e, hipStream_t st, const GEnv* envs, const i
     return AZ_OK;
   }
 }
-// The network part of a wave: the one launch takes the place of tower + heads on the group's network stream; the streams meet as in
-// wave_net_f, and the background search's stop word is raised behind the launch (k_simplenet does not raise it itself).
-template <class Gm> static int wave_simple(az_engine* e, int g, bool split, int nmax) {
-  const DView& v = e->gv[g];
+// The network part of one search wave of slot group g, for both kinds of engine: the group's network stream `sn` starts behind its tree
+// stream (split: they are two), net(sn) launches the network there and sees to the stop word, and ev_net marks its end.  The tree stream
+// waits for that here -- but not in a free-running phase: there the caller (wave_group, azhip.hip) first queues the group's move step and
+// its background search behind k_tree, then the wait for ev_net: both run under this network.
+template <class Net> static int wave_frame(az_engine* e, int g, bool split, Net net) {
   hipStream_t st = e->gs[g], sn = e->gt[g];
   if (split) { HIPCHK(hipEventRecord(e->ev_tree[g], st)); HIPCHK(hipStreamWaitEvent(sn, e->ev_tree[g], 0)); }
-  const int N = std::max(1, std::min(v.G, nmax));
-  const int* nev = v.n_eval + e->wave_par[g];
-  const int* const eslots = v.eval_slots + (size_t)e->wave_par[g] * v.eval_stride;
-  AZCHK((launch_simple<Gm, false>(e, sn, v.leaf_env, eslots, nev, N, nullptr, nullptr, v.Pout, v.Vout, nullptr, Gm::APAD)));
-  if (e->bg_signal) AZCHK(raise_stop_word(e, sn));
+  AZCHK(net(sn));
   if (split) {
     HIPCHK(hipEventRecord(e->ev_net[g], sn));
-    if (!e->ph.fr_on) HIPCHK(hipStreamWaitEvent(st, e->ev_net[g], 0));   // (a free-running wave_group waits for ev_net at its end)
+    if (!e->ph.fr_on) HIPCHK(hipStreamWaitEvent(st, e->ev_net[g], 0));
   }
   return AZ_OK;
+}
+// The leaves of that wave.  N = their upper bound: the group's active slots (a draining phase or a partial explore! launches -- and picks
+// its tower kernel -- for what is left, not for the group's capacity); nev = the leaf counter of this wave (k_tree), eslots = its batch ->
+// slot list
+struct WaveLeaves { int N; const int* nev; const int* eslots; };
+static WaveLeaves wave_leaves(const az_engine* e, int g, int nmax) {
+  const DView& v = e->gv[g];
+  return WaveLeaves{std::max(1, std::min(v.G, nmax)), v.n_eval + e->wave_par[g], v.eval_slots + (size_t)e->wave_par[g] * v.eval_stride};
+}
+// SimpleNet: the one launch takes the place of tower + heads, and the background search's stop word is raised behind it (k_simplenet does
+// not raise it itself).
+template <class Gm> static int wave_simple(az_engine* e, int g, bool split, int nmax) {
+  const DView& v = e->gv[g];
+  const WaveLeaves w = wave_leaves(e, g, nmax);
+  return wave_frame(e, g, split, [&](hipStream_t sn) -> int {
+    AZCHK((launch_simple<Gm, false>(e, sn, v.leaf_env, w.eslots, w.nev, w.N, nullptr, nullptr, v.Pout, v.Vout, nullptr, Gm::APAD)));
+    if (e->bg_signal) AZCHK(raise_stop_word(e, sn));
+    return AZ_OK;
+  });
 }
 
 template <class Gm> static int set_kernel_attrs(az_engine* e) {
@@ -173,94 +209,25 @@ template <class Gm> static int set_kernel_attrs(az_engine* e) {
   AZCHK((set_kernel_attrs_f<Gm, 64>(Forms<Gm, 64>{})));
   AZCHK((set_kernel_attrs_f<Gm, 128>(Forms<Gm, 128>{})));
   memset(e->d_geo, 0, sizeof e->d_geo);
-  AZCHK((upload_geo<T16<Gm, 64, 11>>(e)));
-  AZCHK((upload_geo<T16<Gm, 64, NTS<Gm>>>(e)));
-  AZCHK((upload_geo<T16P<Gm, 64>>(e)));
-  AZCHK((upload_geo<T16P<Gm, 64, 10, 9>>(e)));
-  AZCHK((upload_geo<T16B<Gm, 128, 22>>(e)));
-  if constexpr (NTM<Gm> > 0) AZCHK((upload_geo<T16<Gm, 64, NTM<Gm>>>(e)));
-  AZCHK((upload_geo<T16<Gm, 64, 6>>(e)));
+  AZCHK(upload_geos(e, Forms<Gm, 64>{}));
+  AZCHK(upload_geos(e, Forms<Gm, 128>{}));
+  AZCHK((upload_geo<typename FormMixed<Gm, 64>::T7>(e)));
+  AZCHK((upload_geo<T16<Gm, 64, 6>>(e)));                           // the trainer's 6-tile layer (train.hip k_conv16_layer)
   return AZ_OK;
 }
 
-// Which tower kernel serves a launch of up to n boards.  A workgroup's layer chain is sequential and the MFMA
-// pipe of a CU is shared by its resident workgroups, so the launch costs (workgroups per CU, rounded up) x (rows
-// per workgroup) x (fraction of the tile-tap products it executes): k_tower16 packs 176 rows (4 Connect-Four boards),
-// k_tower 128 (3 boards, every tap), k_tower16 with 3 row tiles 48 (1 board; +10 %: a third of the weight reuse, more
-// barriers per row).  Measured round 2 (tools/run_config.py): Mancala 8192 slots 13.5 M sims/s on k_tower, 21.5 M on
-// k_tower16 (31 of 99 products); 5x128 two groups 1.10 vs 1.20 M.  Returns a TowerForm.
-// n = boards the launch is expected to hold (what the forms are priced with), nb >= n = the most it can hold (what the split
-// tower's co-residency needs; the grid is sized for nb in any case and workgroups beyond the device's count leave at once).
-// INVARIANT: the choice depends on a launch size the host reads from a device-written word WITHOUT synchronising
-// (wave_net_f: h_nleaf), so which form serves a wave differs from run to run.  Results do not, because every fp32 tower form
-// computes the same bits and every bf16 form the same bits (tests/test_net.py, tests/test_net_bf16_gpu.py force each form and compare).
-// A new form must pass those cross-form equality tests before it may be returned from here.
-template <class Gm, int F> static int pick_tower(const az_engine* e, int n, int nb = -1) {
-  if (nb < n) nb = n;
-  // split tower (k_tower16s, 128 filters): both workgroups of every pair must be resident at once -> all slot groups'
-  // launches together at most num_cu workgroups (beyond that the towers queue for CUs and the split only costs: 256
-  // slots in two groups 0.62 vs 0.71 M sims/s); its kernel arguments change per launch (epoch): not under hipGraph replay
-  // (r4) the count runs over ALL engines of the process on this device that may launch split towers side by side (an arena has
-  // two); an engine whose exchange has given up once (another process, a trainer: work this count cannot see) stays unsplit
-  const bool can_split = F == 128 && !e->cfg.net_bf16 && !e->env.use_graphs && e->cfg.num_blocks <= 127 && !e->split_off &&
-                         2 * std::max(std::max(1, e->ngroups), split_streams_on_device(e->device)) * ((nb + T16<Gm, F, NTS<Gm>>::TB - 1) / T16<Gm, F, NTS<Gm>>::TB) <= (e->num_cu > 0 ? e->num_cu : 256);
-  if (e->env.tower_pick == TW_SPLIT && can_split) return TW_SPLIT;
-  if (!e->cfg.net_bf16 && (e->env.tower_pick == TW_11 || e->env.tower_pick == TW_32 || e->env.tower_pick == TW_NTS || ((e->env.tower_pick == TW_P21 || e->env.tower_pick == TW_P19 || e->env.tower_pick == TW_P21C) && F == 64) || (e->env.tower_pick == TW_NTM && NTM<Gm> > 0))) return e->env.tower_pick;
-  if (e->cfg.net_bf16) {                                           // k_tower16b: 22 (128 filters), 11 or 3 row tiles
-    if (e->env.tower_pick == TW_NTS || e->env.tower_pick == TW_11) return e->env.tower_pick;
-    if (e->env.tower_pick == TW_B22 && F == 128) return TW_B22;
-    const long cu2 = e->num_cu > 0 ? e->num_cu : 256;
-    const long a16 = (n + T16B<Gm, F>::TB - 1) / T16B<Gm, F>::TB, a3 = (n + T16B<Gm, F, NTS<Gm>>::TB - 1) / T16B<Gm, F, NTS<Gm>>::TB;
-    const long per = F == 64 ? 2 : 1;                               // workgroups per CU
-    // rounds x rows per workgroup x fraction of the tile-tap products executed (Geo16)
-    constexpr double g16 = T16B<Gm, F>::Geo::tab.cost / (9.0 * 11), g3 = T16B<Gm, F, NTS<Gm>>::Geo::tab.cost / (9.0 * NTS<Gm>);
-    const double d16 = (double)((a16 + per * cu2 - 1) / (per * cu2)) * T16B<Gm, F>::RPAD * g16;
-    const double d3 = 1.1 * (double)((a3 + per * cu2 - 1) / (per * cu2)) * T16B<Gm, F, NTS<Gm>>::RPAD * g3;
-    if constexpr (F == 128) {
-      // 22 row tiles = twice the boards per workgroup: each weight fragment serves twice the rows (10x128, 4096 boards: 578
-      // vs 684 us); only where it does not leave CUs idle that the 11-tile form would use
-      constexpr double g22 = T16B<Gm, F, 22>::Geo::tab.cost / (9.0 * 22);
-      const long a22 = (n + T16B<Gm, F, 22>::TB - 1) / T16B<Gm, F, 22>::TB;
-      const double d22 = 0.9 * (double)((a22 + cu2 - 1) / cu2) * T16B<Gm, F, 22>::RPAD * g22;
-      if (d22 <= d16 && d22 <= d3) return TW_B22;
-    }
-    return d3 <= d16 ? TW_NTS : TW_11;
-  }
-  const long cu = e->num_cu > 0 ? e->num_cu : 256;
-  const long b16 = (n + T16<Gm, F>::TB - 1) / T16<Gm, F>::TB, b32 = (n + TOWER_ROWS / Gm::P - 1) / (TOWER_ROWS / Gm::P);
-  const long b3 = (n + T16<Gm, F, NTS<Gm>>::TB - 1) / T16<Gm, F, NTS<Gm>>::TB;
-  // the k_tower16 family executes only the (tile, tap) products that touch the board (Geo16): cost x executed fraction
-  constexpr double f16 = T16<Gm, F>::Geo::tab.cost / (9.0 * T16<Gm, F>::NTILE), f3 = T16<Gm, F, NTS<Gm>>::Geo::tab.cost / (9.0 * NTS<Gm>),
-                   f21 = T16P<Gm, 64>::Geo::tab.cost / (9.0 * T16P<Gm, 64>::NTW);
-  const double c16 = (double)((b16 + cu - 1) / cu) * T16<Gm, F>::RPAD * f16;
-  const double c32 = (double)((b32 + cu - 1) / cu) * TOWER_ROWS;     // k_tower (32x32x2) computes every tap
-  const double c3 = 1.1 * (double)((b3 + cu - 1) / cu) * T16<Gm, F, NTS<Gm>>::RPAD * f3;
-  if (c3 <= c16 && c3 <= c32) return can_split && e->env.tower_pick != TW_NTS ? TW_SPLIT : TW_NTS;
-  // (r4) the exact-fit variant (NTM tiles: whole boards, no padding rows): where its workgroups fill the CUs evenly it beats
-  // the 11-tile form by the padding rows and by the last, partly filled round of workgroups
-  if constexpr (NTM<Gm> > 0) {
-    using TM = T16<Gm, F, NTM<Gm>>;
-    constexpr double fm = TM::Geo::tab.cost / (9.0 * NTM<Gm>);
-    const long bm = (n + TM::TB - 1) / TM::TB;
-    // +3 %: fewer rows per weight fragment; the half-size form at 128 filters +20 %: half the rows per weight fragment there (the
-    // vector-memory path that streams the weights is what a 128-filter layer waits for: DESIGN.md 4d, the trainer's 6-tile layer)
-    const double cm = (Gm::P == 42 && F == 128 ? 1.2 : 1.03) * (double)((bm + cu - 1) / cu) * TM::RPAD * fm;
-    if (cm < c16 && cm < c32 && (F != 64 || cm < (double)(((n + T16P<Gm, 64>::TB - 1) / T16P<Gm, 64>::TB + cu - 1) / cu) * T16P<Gm, 64>::RPAD * f21)) return TW_NTM;
-  }
-  // paired k_tower16x2: 336 rows = 8 Connect-Four boards per workgroup, no padding rows.  Its 92 KB of LDS allow one
-  // workgroup per CU, so with several slot groups the groups' towers cannot interleave on a CU (Connect-Four, two groups:
-  // 3.80 vs 4.11 M sims/s in round 1): +8 % on its cost there
-  if (F == 64) {
-    const long b21 = (n + T16P<Gm, 64>::TB - 1) / T16P<Gm, 64>::TB;
-    const double c21 = (double)((b21 + cu - 1) / cu) * T16P<Gm, 64>::RPAD * f21 * (e->ngroups > 1 ? 1.08 : 1.0);
-    if (c21 < c16 && c21 < c32) return TW_P21;
-  }
-  return c16 <= c32 ? TW_11 : TW_32;
+// What a launch of up to n boards of this engine asks the choice (tower_choice.h) with; a wave adds its own fields
+static TowerAsk tower_ask(const az_engine* e, int n) {
+  TowerAsk a;
+  a.n = n; a.num_cu = e->num_cu; a.ngroups = e->ngroups;
+  a.bf16 = e->cfg.net_bf16 != 0; a.num_blocks = e->cfg.num_blocks; a.tower_pick = e->env.tower_pick; a.use_graphs = e->env.use_graphs != 0; a.split_off = e->split_off;
+  a.split_streams = split_streams_on_device(e->device);
+  return a;
 }
 // publish areas of k_tower16s for the launches that write `hfeat` (one feature buffer = one stream at a time)
 template <class Gm> static int xch_slot(az_engine* e, const float* hfeat, unsigned long long** xch, unsigned long long* epoch) {
   using T = T16S<Gm, 128>;
-  const size_t words = (size_t)(e->num_cu > 0 ? e->num_cu : 256) * T::XCH_WORDS;
+  const size_t words = (size_t)cus(e->num_cu) * T::XCH_WORDS;
   int slot = AZ_MAX_GROUPS;
   for (int g = 0; g < e->ngroups; ++g) if (hfeat == e->g_hfeat[g]) slot = g;
   if (!e->xch[slot]) {
@@ -283,25 +250,25 @@ template <class Gm> static int xch_slot(az_engine* e, const float* hfeat, unsign
   if (e->env.xch_fail_at > 0 && ++e->xch_launches == e->env.xch_fail_at) *epoch |= 1ull << 63;   // tests: this launch loses a partner (AZHIP_XCH_FAIL_AT)
   return AZ_OK;
 }
-// Dense heads of n_max boards: 16-board tiles (k_heads16: a quarter of the chain latency, 23 instead of 43 us per launch
-// at 64 filters whatever the size) unless several slot groups run big launches side by side -- there the heads hide
-// under the other group's tower anyway and twice as many workgroups asking for a CU cost 1 % (0.867 vs 0.857 ms per
-// step, two groups of 2048): 32-board tiles (k_heads_mfma).  The vector-ALU kernel when the head filters do not fit
-// the MFMA fragments.
-static constexpr int HEADS16_MAX_BOARDS = 1024;
+// the dense heads of n_max boards, by the kernel choose_heads (tower_choice.h) names
 template <class Gm, int F>
 static int launch_heads(az_engine* e, hipStream_t st, const float* hfeat, const GEnv* envs, const int* eslots, const int* n_ptr, int n_max,
                         const float* Amask, float* Pout, float* Vout, float* Pinv, int pstride) {
-  const bool small = e->env.heads_pick == 16 || (e->env.heads_pick != 32 && (n_max <= HEADS16_MAX_BOARDS || e->ngroups == 1));
   const int tiles = (n_max + 15) / 16;
-  if (e->net.hd16_ok && small && 2 * tiles <= (e->num_cu > 0 ? e->num_cu : 256))    // value and policy tiles in two workgroups, features staged in LDS
-    LAUNCH_ON(e, st, AZ_K_HEADS, n_max, (k_heads16<Gm, F, true>), 2 * tiles, (H16<Gm, F, true>::THREADS), (H16<Gm, F, true>::BYTES), e->net, envs, eslots, n_ptr, n_max, Amask, hfeat, Pout, Vout, Pinv, pstride);
-  else if (e->net.hd16_ok && small)
-    LAUNCH_ON(e, st, AZ_K_HEADS, n_max, (k_heads16<Gm, F, false>), tiles, (H16<Gm, F, false>::THREADS), (H16<Gm, F, false>::BYTES), e->net, envs, eslots, n_ptr, n_max, Amask, hfeat, Pout, Vout, Pinv, pstride);
-  else if (e->net.hd_ok)
-    LAUNCH_ON(e, st, AZ_K_HEADS, n_max, (k_heads_mfma<Gm, F>), (n_max + 31) / 32, 64 * (F / 32 + HEADS_NPT<Gm>), 0, e->net, envs, eslots, n_ptr, n_max, Amask, hfeat, Pout, Vout, Pinv, pstride);
-  else
-    LAUNCH_ON(e, st, AZ_K_HEADS, n_max, (k_heads<Gm, F>), (n_max + 3) / 4, 4 * (F + HEADS_LP<Gm>), 0, e->net, envs, eslots, n_ptr, n_max, Amask, hfeat, Pout, Vout, Pinv, pstride);
+  switch (choose_heads(e->env.heads_pick, e->net.hd16_ok, e->net.hd_ok, n_max, e->ngroups, e->num_cu)) {
+    case HD_16_STAGED:
+      LAUNCH_ON(e, st, AZ_K_HEADS, n_max, (k_heads16<Gm, F, true>), 2 * tiles, (H16<Gm, F, true>::THREADS), (H16<Gm, F, true>::BYTES), e->net, envs, eslots, n_ptr, n_max, Amask, hfeat, Pout, Vout, Pinv, pstride);
+      break;
+    case HD_16:
+      LAUNCH_ON(e, st, AZ_K_HEADS, n_max, (k_heads16<Gm, F, false>), tiles, (H16<Gm, F, false>::THREADS), (H16<Gm, F, false>::BYTES), e->net, envs, eslots, n_ptr, n_max, Amask, hfeat, Pout, Vout, Pinv, pstride);
+      break;
+    case HD_MFMA:
+      LAUNCH_ON(e, st, AZ_K_HEADS, n_max, (k_heads_mfma<Gm, F>), (n_max + 31) / 32, 64 * (F / 32 + HEADS_NPT<Gm>), 0, e->net, envs, eslots, n_ptr, n_max, Amask, hfeat, Pout, Vout, Pinv, pstride);
+      break;
+    case HD_VALU:
+      LAUNCH_ON(e, st, AZ_K_HEADS, n_max, (k_heads<Gm, F>), (n_max + 3) / 4, 4 * (F + HEADS_LP<Gm>), 0, e->net, envs, eslots, n_ptr, n_max, Amask, hfeat, Pout, Vout, Pinv, pstride);
+      break;
+  }
   return AZ_OK;
 }
 // Where a tower launch finds its boards (envs[eslots[i]], device count in n_ptr; FROM_PLANES: X) and leaves the head features; xerr = the
@@ -327,13 +294,13 @@ template <class D, bool FROM_PLANES> static int launch_form(az_engine* e, hipStr
                 xa, ep, in.xerr, e->d_xflag);
     } else if constexpr (D::STOP)
       LAUNCH_ON(e, st, AZ_K_TOWER, n, (D::template K<FROM_PLANES>), tiles, T::THREADS, T::BYTES, D::net(e), in.envs, in.eslots, in.n_ptr, n, in.X, in.hfeat,
-                in.stop, in.stop_val, e->num_cu > 0 ? e->num_cu : 256);
+                in.stop, in.stop_val, cus(e->num_cu));
     else
       LAUNCH_ON(e, st, AZ_K_TOWER, n, (D::template K<FROM_PLANES>), tiles, T::THREADS, T::BYTES, D::net(e), in.envs, in.eslots, in.n_ptr, n, in.X, in.hfeat);
     return AZ_OK;
   }
 }
-// The one tower launch: form `form` (what pick_tower returned) of the engine's network on up to n boards.  Sets last_tower, tower_hist
+// The one tower launch: form `form` (what choose_tower returned) of the engine's network on up to n boards.  Sets last_tower, tower_hist
 // and next_exec; the grid is sized for n and workgroups beyond the device's count leave at once.
 template <class Gm, int F, bool FROM_PLANES, class... D>
 static int launch_tower(FormList<D...>, az_engine* e, hipStream_t st, int form, int n, const TowerIn& in) {
@@ -349,7 +316,7 @@ template <class Gm, int F, bool FROM_PLANES>
 static int launch_net_f(az_engine* e, hipStream_t st, float* hfeat, const GEnv* envs, const int* eslots, const int* n_ptr, int n_max, const float* X,
                         const float* Amask, float* Pout, float* Vout, float* Pinv, int pstride) {
   if (n_max <= 0) return AZ_OK;
-  AZCHK((launch_tower<Gm, F, FROM_PLANES>(e, st, pick_tower<Gm, F>(e, n_max), n_max, TowerIn{hfeat, envs, eslots, n_ptr, X, e->v.err})));
+  AZCHK((launch_tower<Gm, F, FROM_PLANES>(e, st, choose_tower(tower_table<Gm, F>(), tower_ask(e, n_max)), n_max, TowerIn{hfeat, envs, eslots, n_ptr, X, e->v.err})));
   return launch_heads<Gm, F>(e, st, hfeat, envs, eslots, n_ptr, n_max, Amask, Pout, Vout, Pinv, pstride);
 }
 // launches tower + heads on `n` boards (device count in n_ptr when given)
@@ -362,74 +329,43 @@ static int launch_net(az_engine* e, hipStream_t st, float* hfeat, const GEnv* en
 }
 
 
+// ResNet: tower, then heads.  The tower runs on the network stream.  Outside a free-running phase the heads follow on the tree stream, once it
+// has met the network stream; in one they follow the tower on the network stream, so that the tree stream is free meanwhile (wave_frame).
 template <class Gm, int F> static int wave_net_f(az_engine* e, int g, bool split, int nmax) {
-  constexpr int L = Gm::APAD;
   const DView& v = e->gv[g];
-  hipStream_t st = e->gs[g], sn = e->gt[g];
-  const int G = v.G;
-  if (split) { HIPCHK(hipEventRecord(e->ev_tree[g], st)); HIPCHK(hipStreamWaitEvent(sn, e->ev_tree[g], 0)); }
-  // N = upper bound of this wave's leaves: the group's active slots (a draining phase or a partial explore! launches
-  // -- and picks its tower kernel -- for what is left, not for the group's capacity)
-  const int N = std::max(1, std::min(G, nmax));
-  const int* nev = v.n_eval + e->wave_par[g];                      // the leaf counter of this wave (k_tree)
-  const int* const eslots = v.eval_slots + (size_t)e->wave_par[g] * v.eval_stride;   // ... and its batch -> slot list
-  // how many boards the launch will really hold: with the evaluation cache answering part of every wave, what the device
-  // reported for the group's last completed wave (+ 1/8: a launch priced too small costs more than one priced too large)
-  int npick = N;
-  if (v.nleaf_host) { const int seen = ((volatile int*)e->h_nleaf)[g]; if (seen >= 0) npick = std::max(1, std::min(N, seen + seen / 8 + 8)); }
-  int tw = pick_tower<Gm, F>(e, npick, N);
-  if (tw == TW_P21 && e->ph.fr_on && e->ngroups == 1 && e->env.tower_pick == 0 && e->ph.fr_kbg > 0 && v.nleaf_host && v.needy_host) {
-    // The paired tower beside the side streams' kernels (resnet16.h k_tower16x2c): a CU that holds a workgroup of the background search
-    // (256 threads = 32 Connect-Four slots of the needy list) takes no workgroup of the 198-register form for as long as that search
-    // runs.  Measured: in the steady state (~8 such workgroups on average, more in some waves) the launch gains a round of workgroups
-    // beyond ~478 of its 512; the margin of 14 is that measurement (the move step is not part of it: within 96 registers it changes
-    // nothing).  Where the counts the device reported for the previous wave say that this adds a round, the 176-register form serves
-    // the launch.
-    const int cu = e->num_cu > 0 ? e->num_cu : 256;
-    const int seen = ((volatile int*)e->h_nleaf)[g], needy = ((volatile int*)e->h_needy)[g];
-    if (seen > 0) {
-      constexpr int TB21 = T16P<Gm, 64>::TB;
-      const int wgs = (seen + TB21 - 1) / TB21, rounds = (wgs + cu - 1) / cu, bg = (std::max(needy, 0) * L + 255) / 256;
-      if (wgs > rounds * (cu - bg) - 14) tw = TW_P21C;
-    }
-  }
-  // the background search's stop word: a paired form raises it itself, from its last round of workgroups (resnet16.h tower16x2_body)
-  const bool tower_stops = e->bg_signal && F == 64 && !e->cfg.net_bf16 && (tw == TW_P21 || tw == TW_P19 || tw == TW_P21C);
-  TowerIn in{e->g_hfeat[g], v.leaf_env, eslots, nev, nullptr, v.xerr};
-  if (tower_stops) { in.stop = e->d_bg_stop; in.stop_val = e->bg_seq; }
-  bool mixed = false;
-  if constexpr (FormMixed<Gm, F>::OK) {
-    // (r6, measured, off unless AZHIP_TOWER_MIXED=1) A batch between 15 and 16 boards per CU (a free-running wave's ~3800 boards at 4096 slots on
-    // 256 CUs) costs two rounds of the 8-board form whatever its size.  As ONE launch of cu 8-board workgroups and up to cu 7-board ones
-    // (k_tower16x2m) it is slower, 1.09 ms per wave instead of 0.80 (profiles/r6/README.md): a workgroup's time hardly shrinks with its
-    // boards, because every workgroup streams the same 1.5 MB of weights through its CU's vector-memory path.
-    using M = FormMixed<Gm, F>;
-    using T8 = typename M::T; using T7 = typename M::T7;
-    const int cu = e->num_cu > 0 ? e->num_cu : 256, first = cu * T8::TB;
-    const int seen = v.nleaf_host ? ((volatile int*)e->h_nleaf)[g] : -1;
-    if (tw == TW_P21 && e->env.tower_mixed && e->env.tower_pick == 0 && N > first && seen > first && seen + 16 <= first + cu * T7::TB) {
-      mixed = true;
-      M::name(e->last_tower, sizeof e->last_tower, game_name(e));
-      e->tower_hist[M::HIST]++;
-      // the launch holds boards of both forms: price the executed fraction by their shares of the expected batch
-      e->next_exec = (first * geo_frac<T8>() + (seen - first) * geo_frac<T7>()) / (double)seen;
-      LAUNCH_ON(e, sn, AZ_K_TOWER, N, (M::template K<false>), cu + (N - first + T7::TB - 1) / T7::TB, T8::THREADS, T8::BYTES, M::net(e), in.envs, in.eslots, in.n_ptr, N, in.X, in.hfeat, cu, in.stop, in.stop_val);
-    }
-  }
-  if (!mixed) AZCHK((launch_tower<Gm, F, false>(e, sn, tw, N, in)));
-  // Free-running phase: the heads follow the tower on the network stream and the tree stream is NOT made to wait here -- the caller
-  // (wave_group, azhip.hip) first queues the group's move step and its background search behind k_tree, then the wait for ev_net: both
-  // run under this tower.
+  const WaveLeaves w = wave_leaves(e, g, nmax);
   const bool fr = e->ph.fr_on && split;
-  if (e->bg_signal && !tower_stops) {
-    // a form that does not raise the word itself.  The tower has run: the background search of this wave winds up while the heads run.  The
-    // word is set from a stream of its own behind an event (a one-thread launch IN the wave's stream sat 7.6 us between tower and heads)
-    AZCHK(raise_stop_word(e, sn));
-  }
-  if (split && !fr) { HIPCHK(hipEventRecord(e->ev_net[g], sn)); HIPCHK(hipStreamWaitEvent(st, e->ev_net[g], 0)); }
-  AZCHK((launch_heads<Gm, F>(e, fr ? sn : st, e->g_hfeat[g], v.leaf_env, eslots, nev, N, (const float*)nullptr, v.Pout, v.Vout, (float*)nullptr, L)));
-  if (fr) HIPCHK(hipEventRecord(e->ev_net[g], sn));
-  return AZ_OK;
+  auto heads = [&](hipStream_t s) -> int {
+    return launch_heads<Gm, F>(e, s, e->g_hfeat[g], v.leaf_env, w.eslots, w.nev, w.N, (const float*)nullptr, v.Pout, v.Vout, (float*)nullptr, Gm::APAD);
+  };
+  AZCHK(wave_frame(e, g, split, [&](hipStream_t sn) -> int {
+    TowerAsk ask = tower_ask(e, w.N);
+    ask.fr_on = e->ph.fr_on; ask.fr_kbg = e->ph.fr_kbg; ask.tower_mixed = e->env.tower_mixed; ask.bg_signal = e->bg_signal;
+    // the device writes these words while the host reads them: ONE read of each per wave, so that every rule sees the same numbers
+    if (v.nleaf_host) ask.seen = ((volatile int*)e->h_nleaf)[g];
+    if (v.needy_host) { ask.needy = ((volatile int*)e->h_needy)[g]; ask.needy_on = true; }
+    const WaveTower tw = choose_wave_tower(tower_table<Gm, F>(), ask);
+    TowerIn in{e->g_hfeat[g], v.leaf_env, w.eslots, w.nev, nullptr, v.xerr};
+    if (tw.tower_stops) { in.stop = e->d_bg_stop; in.stop_val = e->bg_seq; }
+    if constexpr (FormMixed<Gm, F>::OK) {
+      if (tw.mixed) {
+        // workgroups 0 .. cu - 1 hold 8 boards each, the rest 7
+        using M = FormMixed<Gm, F>;
+        using T8 = typename M::T; using T7 = typename M::T7;
+        const int cu = cus(e->num_cu), first = cu * T8::TB;
+        M::name(e->last_tower, sizeof e->last_tower, game_name(e));
+        e->tower_hist[M::HIST]++;
+        // the launch holds boards of both forms: price the executed fraction by their shares of the expected batch
+        e->next_exec = (first * geo_frac<T8>() + (ask.seen - first) * geo_frac<T7>()) / (double)ask.seen;
+        LAUNCH_ON(e, sn, AZ_K_TOWER, w.N, (M::template K<false>), cu + (w.N - first + T7::TB - 1) / T7::TB, T8::THREADS, T8::BYTES, M::net(e), in.envs, in.eslots, in.n_ptr, w.N, in.X, in.hfeat, cu, in.stop, in.stop_val);
+      }
+    }
+    if (!tw.mixed) AZCHK((launch_tower<Gm, F, false>(e, sn, tw.form, w.N, in)));
+    // a form that does not raise the word itself.  The tower has run: the background search of this wave winds up while the heads run
+    if (e->bg_signal && !tw.tower_stops) AZCHK(raise_stop_word(e, sn));
+    return fr ? heads(sn) : AZ_OK;
+  }));
+  return fr ? AZ_OK : heads(e->gs[g]);
 }
 template <class Gm> static int wave_net(az_engine* e, int g, bool split, int nmax) {
   if (e->cfg.oracle == AZ_ORACLE_SIMPLENET) return wave_simple<Gm>(e, g, split, nmax);

@@ -246,7 +246,7 @@ template <class Gm> constexpr int NTS = Gm::P <= 48 ? 3 : (Gm::P + 15) / 16;
 // (r5) A game without one (Connect-Four: 42 positions) gets the HALF-SIZE form instead -- 6 tiles = 96 rows = 2 boards + 12 padding
 // rows: since the evaluation cache answers part of every wave, a launch holds 1000 ... 1600 boards instead of 2048 / 4096, and what
 // a launch costs is set by the CU with the most boards: with 4-board workgroups that is 8 boards wherever 256 CUs share more than
-// 1024, with 2-board workgroups 6 (pick_tower prices both with the launch size the device reported for the last waves).
+// 1024, with 2-board workgroups 6 (choose_wave_tower, tower_choice.h, prices both with the launch size the device reported for the last waves).
 template <class Gm> constexpr int ntm_of() { for (int nt = 4; nt <= 10; ++nt) if ((16 * nt) % Gm::P == 0) return nt; return Gm::P == 42 ? 6 : 0; }
 template <class Gm> constexpr int NTM = ntm_of<Gm>();
 // NT = row tiles per workgroup: 11 (throughput: 4 Connect-Four boards, 2 workgroups per CU at 64 filters) or 3
@@ -851,7 +851,7 @@ k_tower16s(Net16Dev net, const GEnv* __restrict__ leaf_env, const int* __restric
   PairXch x;
   x.mine = xch + (size_t)blockIdx.x * T::XCH_WORDS;
   x.theirs = xch + (size_t)(blockIdx.x ^ 1) * T::XCH_WORDS;
-  x.tag0 = (uint32_t)(epoch << 8);                   // + layer index < 256 (pick_tower)
+  x.tag0 = (uint32_t)(epoch << 8);                   // + layer index < 256 (choose_tower: num_blocks <= 127)
   x.err = err;
   x.hflag = hflag;
   x.pch = ((half ^ 1) * T::CWL + cwl) * 16 + (lane & 15);

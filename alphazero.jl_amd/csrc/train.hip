@@ -603,7 +603,7 @@ static int tr_conv16(az_trainer* t, const float* in, const float* frag, float* o
     using T6 = T16<Gm, 64, 6>;
     // (r4) 64 filters and a batch that gives the 11-tile form at most one workgroup per CU: the 6-tile form (half the boards per
     // workgroup, two workgroups per CU) overlaps one workgroup's fill and epilogue with the other's products
-    const bool small = t->F == 64 && t->env.conv_nt6 && (t->B + T::TB - 1) / T::TB <= (t->e->num_cu > 0 ? t->e->num_cu : 256);
+    const bool small = t->F == 64 && t->env.conv_nt6 && (t->B + T::TB - 1) / T::TB <= cus(t->e->num_cu);
     if (nparts) *nparts = small ? (t->B + T6::TB - 1) / T6::TB : (t->B + T::TB - 1) / T::TB;
     if (t->F == 128) { if (stats) AZCHK((tr_conv16_f<Gm, 128, true, 11>(t, in, frag, out, addend, bn, fin))); else AZCHK((tr_conv16_f<Gm, 128, false, 11>(t, in, frag, out, addend, bn, fin))); }
     else if (small) { if (stats) AZCHK((tr_conv16_f<Gm, 64, true, 6>(t, in, frag, out, addend, bn, fin))); else AZCHK((tr_conv16_f<Gm, 64, false, 6>(t, in, frag, out, addend, bn, fin))); }

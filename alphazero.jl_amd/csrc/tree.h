@@ -98,7 +98,7 @@ struct DView {
   uint32_t ec_floor;          // entries whose claim number is <= ec_floor are EMPTY: az_net_set_params empties the table by raising the floor (a 1 GB memset per weight update before)
   int* ec_claim;          // [G][2] cache entry the slot's pending leaf claimed (its answer goes there when the leaf is expanded; -1 = none) and the meta value of the claim
   int* needy_host;        // host-mapped word: the slots this group's previous wave launch left to the background search (free-running; wave_net_f's choice between the paired tower's two register budgets), or NULL
-  int* nleaf_host;        // host-mapped word: the network batch of this group's previous wave (pick_tower's launch-size estimate), or NULL
+  int* nleaf_host;        // host-mapped word: the network batch of this group's previous wave (choose_wave_tower's launch-size estimate), or NULL
   float* Phit; float* Vhit; // [G][APAD], [G]: the answer of a leaf the cache answered, by SLOT (written by the slot's phase B, read by its next phase A; SlotRec::eidx = -1 says so)
   uint32_t tag_mask;      // 0xffff; tests narrow it (AZHIP_HT_TAG_BITS) so that unequal states share tags and every probe chain reaches the exact key compare
   uint32_t epoch0;        // first live epoch of a slot's table: 1; tests start near the 16-bit wrap (AZHIP_HT_EPOCH0)

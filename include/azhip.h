@@ -816,7 +816,7 @@ int az_prof_get(az_engine* e, az_prof* out);    /* synchronises, accumulates, re
 int az_prof_reset(az_engine* e);
 int az_device_info(az_engine* e, char* name, int32_t name_cap, int32_t* num_cu, int64_t* hbm_bytes);
 /* Name of the tower kernel the engine chose for its most recent network launch ("" before the first one): the
- * kernel is picked per launch size (pick_tower, csrc/net.hip), bench.py reports the one that actually ran. */
+ * kernel is picked per launch size (choose_tower, csrc/tower_choice.h), bench.py reports the one that actually ran. */
 int az_net_last_kernel(const az_engine* e, char* name, int32_t cap);
 
 #ifdef __cplusplus

@@ -4,7 +4,7 @@ Nothing rounds in such a tower, so a correct kernel's tower output equals the em
 the bound is TOL = 1e-5 of tests/test_net.py, where tests/test_net_bf16_gpu.py needs 1.5e-2 at depth 10.  A tap skipped in one
 border class of one layer, a wrong neighbour-table entry, a skip connection that adds the wrong row or a mis-packed weight
 fragment moves the output by 1e-3 and more (tests/test_exact_nets.py measures that on the CPU).  Every case forces each tile
-count the engine can launch, asserts the kernel form it ran, and holds the forms to each other bit for bit (pick_tower's
+count the engine can launch, asserts the kernel form it ran, and holds the forms to each other bit for bit (choose_tower's
 invariant); the device games also go through the fused encode path.  A rounding leg covers what exact networks cannot see.
 
 Every case prints its largest gap to the emulation; the fp32 CPU oracle, whose heads round like the device's, is within
