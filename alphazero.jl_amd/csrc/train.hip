@@ -435,6 +435,7 @@ struct az_trainer {               // every member starts here: az_trainer_destro
   float *dact = nullptr, *dact2 = nullptr, *dact3 = nullptr, *dcol = nullptr;   // [R][F] gradients (dcol / dact / dact3 take turns as the running gradient, dact2 = the skip share)
   float* wg_part = nullptr; int wg_splits = 0, wg_bpw = 0;       // k_wgrad16: partial dW per row split, boards per workgroup
   double *part = nullptr, *sums = nullptr, *terms = nullptr, *bsums = nullptr;
+  size_t npart = 0; int wsum = 0, wbn = 0;                                   // what trainer_build sized them for: part [npart], sums [2][wsum], bn_mf [2][wbn]
   float* bn_mf = nullptr;                                                    // [2][C] the batch-norm backward means of the layer in flight
   int* fin_counter = nullptr;                                                // tr_finish: counter of the workgroups that have left their partial sums
   std::vector<void*> allocs;
@@ -582,6 +583,7 @@ static int trainer_build(az_trainer* t) {
   AZCHK(tr_alloc(t, &t->bX, (size_t)B * gi.C * P)); AZCHK(tr_alloc(t, &t->bA, (size_t)B * A)); AZCHK(tr_alloc(t, &t->bP, (size_t)B * A));
   AZCHK(tr_alloc(t, &t->part, npart));
   AZCHK(tr_alloc(t, &t->sums, (size_t)2 * wsum)); AZCHK(tr_alloc(t, &t->bn_mf, (size_t)2 * wbn));
+  t->npart = npart; t->wsum = wsum; t->wbn = wbn;
   AZCHK(tr_alloc(t, &t->fin_counter, 4, true));                       // tr_finish: workgroups done (every launch leaves it at zero)
   AZCHK(tr_alloc(t, &t->terms, (size_t)4 * B)); AZCHK(tr_alloc(t, &t->bsums, 8 + 1024));
   return AZ_OK;
@@ -639,17 +641,20 @@ static void tr_bn_bwd(az_trainer* t, const float* da, const float* a, const floa
   if (C % 4 == 0) hipLaunchKernelGGL((k_tr_bn_bwd<4>), dim3(tr_grid(n / 2)), dim3(256), 0, t->stream, da, a, g, mean, invstd, gamma, t->bn_mf, n, C, dg, dy_out);
   else hipLaunchKernelGGL((k_tr_bn_bwd<1>), dim3(tr_grid(n)), dim3(256), 0, t->stream, da, a, g, mean, invstd, gamma, t->bn_mf, n, C, dg, dy_out);
 }
-// column sums of mode MODE over R rows, result in t->sums
+// column sums of mode MODE over R rows, result in t->sums.  ran (debug seam): what was launched -- chunks, 1 if k_tr_colsum1v, 1 if the second
+// stage rides in the producer, column blocks (gridDim.y)
 template <int MODE>
 static int tr_colsum(az_trainer* t, const float* x, const float* out_act, const float* g, const float* mean, const float* invstd, long long R, int C,
-                     TrFinal fin = TrFinal{}) {
+                     TrFinal fin = TrFinal{}, int32_t* ran = nullptr) {
   const int nchunks = (int)((R + TR_CHUNK - 1) / TR_CHUNK);
   // (tr_finish -- the second stage in the producer's last workgroup -- is off: measured slower, see k_tr_colsum_final)
   const bool inside = t->env.fin_inside && C <= 128;
   fin.counter = inside ? t->fin_counter : nullptr;
-  if (MODE == 1 && C % 4 == 0 && C <= 128 && 256 % (C / 4) == 0)
-    hipLaunchKernelGGL(k_tr_colsum1v, dim3(nchunks), dim3(256), 0, t->stream, x, out_act, g, mean, invstd, R, C, t->part, fin);
-  else hipLaunchKernelGGL((k_tr_colsum<MODE>), dim3(nchunks, (C + 63) / 64), dim3(256), 0, t->stream, x, out_act, g, mean, invstd, R, C, t->part, fin);
+  const bool vec = MODE == 1 && C % 4 == 0 && C <= 128 && 256 % (C / 4) == 0;
+  const dim3 grid(nchunks, vec ? 1 : (C + 63) / 64);
+  if (vec) hipLaunchKernelGGL(k_tr_colsum1v, grid, dim3(256), 0, t->stream, x, out_act, g, mean, invstd, R, C, t->part, fin);
+  else hipLaunchKernelGGL((k_tr_colsum<MODE>), grid, dim3(256), 0, t->stream, x, out_act, g, mean, invstd, R, C, t->part, fin);
+  if (ran) { ran[0] = nchunks; ran[1] = vec; ran[2] = inside; ran[3] = (int32_t)grid.y; }
   if (!inside) hipLaunchKernelGGL(k_tr_colsum_final, dim3(C), dim3(64), 0, t->stream, t->part, nchunks, C, t->sums, fin);
   return AZ_OK;
 }
@@ -671,20 +676,50 @@ static TrFinal tr_fin_bn_bwd(const az_trainer* t, const TrLayer& c) {
 static BnIn tr_bn_in(const az_trainer* t, const TrLayer& c) {
   return BnIn{c.g, c.mean, c.invstd, t->blob + c.off_bn, t->blob + c.off_bn + c.out, c.skip >= 0 ? t->layers[c.skip].a : nullptr, c.a};
 }
+// a = relu(bn(g) (+ res)) over n = rows x C elements / x = [relu](x + bias) in place / the relu mask of the way back, in place
+static void tr_bn_apply(az_trainer* t, const BnIn& b, long long n, int C) {
+  hipLaunchKernelGGL(k_tr_bn_apply, dim3(tr_grid(n)), dim3(256), 0, t->stream, b.g, b.mean, b.invstd, b.gamma, b.beta, b.res, n, C, b.a_out);
+}
+static void tr_bias_act(az_trainer* t, float* x, const float* bias, long long n, int C, bool relu) {
+  hipLaunchKernelGGL(k_tr_bias_act, dim3(tr_grid(n)), dim3(256), 0, t->stream, x, bias, n, C, relu ? 1 : 0);
+}
+static void tr_relu_bwd(az_trainer* t, float* dy, const float* y, long long n) {
+  hipLaunchKernelGGL(k_tr_relu_bwd, dim3(tr_grid(n)), dim3(256), 0, t->stream, dy, y, n);
+}
 static void tr_layer_act(az_trainer* t, const TrLayer& c) {
   const long long n = c.rows * c.out;
-  if (c.bn) {
-    const BnIn b = tr_bn_in(t, c);
-    hipLaunchKernelGGL(k_tr_bn_apply, dim3(tr_grid(n)), dim3(256), 0, t->stream, b.g, b.mean, b.invstd, b.gamma, b.beta, b.res, n, c.out, b.a_out);
-  } else hipLaunchKernelGGL(k_tr_bias_act, dim3(tr_grid(n)), dim3(256), 0, t->stream, c.g, t->blob + c.off_b, n, c.out, c.relu ? 1 : 0);
+  if (c.bn) tr_bn_apply(t, tr_bn_in(t, c), n, c.out);
+  else tr_bias_act(t, c.g, t->blob + c.off_b, n, c.out, c.relu);
+}
+// the stem's gather: col[rows][9 C] = the 3x3 neighbourhoods of the planes [B][C][H][W]
+static void tr_im2col(az_trainer* t, const float* planes, const TrLayer& c) {
+  hipLaunchKernelGGL((k_tr_im2col<true>), dim3(tr_grid(c.rows * c.in)), dim3(256), 0, t->stream, planes, c.rows, c.in / 9, t->gi.W, t->gi.H, c.col);
+}
+// the loss of the batch in bA / bP / bV / bW with its gradient, per-sample terms in t->terms; force_wide: k_tr_loss_wide whatever A
+// (debug seam: the two kernels on the same inputs).  Returns whether the wide kernel ran.
+static bool tr_loss(az_trainer* t, const float* logits, const float* tpre, float cinv, float rho, float gscale, float* dlogits, float* dt, bool force_wide) {
+  const int A = t->gi.A, B = t->B;
+  hipStream_t st = t->stream;
+  double *tw = t->terms, *tkl = t->terms + B, *tmse = t->terms + 2 * (size_t)B, *tinv = t->terms + 3 * (size_t)B;
+  const bool wide = force_wide || A > AZ_MAX_ACTIONS;
+  if (!wide)
+    hipLaunchKernelGGL(k_tr_loss, dim3(tr_grid(B)), dim3(256), 0, st, logits, tpre, t->bA, t->bP, t->bV, t->bW, B, A, cinv, rho, gscale, dlogits, dt, tw, tkl, tmse, tinv);
+  else                                                              // 64 threads per workgroup: the rows of a wavefront's samples are 4 A bytes apart, so more CUs share the strided reads
+    hipLaunchKernelGGL(k_tr_loss_wide, dim3((B + 63) / 64), dim3(64), 0, st, logits, tpre, t->bA, t->bP, t->bV, t->bW, B, A, cinv, rho, gscale, dlogits, dt, tw, tkl, tmse, tinv);
+  return wide;
+}
+// the five sums of a step: the per-sample terms and the sum of squares of the trainable parameters
+static void tr_step_sums(az_trainer* t, double* d_sums) {
+  const int B = t->B;
+  hipLaunchKernelGGL(k_tr_sumsq, dim3(1024), dim3(256), 0, t->stream, t->blob, t->trainable, (long long)t->nparams, t->bsums + 8);
+  hipLaunchKernelGGL(k_tr_step_sums, dim3(1), dim3(256), 0, t->stream, t->terms, t->terms + B, t->terms + 2 * (size_t)B, t->terms + 3 * (size_t)B, B, t->bsums + 8, 1024, d_sums);
 }
 static const float* tr_input(const az_trainer* t, const TrLayer& c) {   // TR_PLAIN on the planes: flatten = their memory order
   return c.input == TR_IM2COL ? c.col : c.src < 0 ? t->bX : t->layers[c.src].a;
 }
 // every layer but the tower's MFMA convolutions: the GEMM, then batch statistics + k_tr_bn_apply, or k_tr_bias_act
 static int gemm_layer_forward(az_trainer* t, TrLayer& c) {
-  if (c.input == TR_IM2COL)
-    hipLaunchKernelGGL((k_tr_im2col<true>), dim3(tr_grid(c.rows * c.in)), dim3(256), 0, t->stream, t->bX, c.rows, c.in / 9, t->gi.W, t->gi.H, c.col);
+  if (c.input == TR_IM2COL) tr_im2col(t, t->bX, c);
   AZCHK(tr_gemm(t, false, false, (int)c.rows, c.out, c.in, 1.f, tr_input(t, c), c.in, t->work + c.wk_wm, c.out, 0.f, c.g, c.out));
   if (c.bn) AZCHK(tr_colsum<0>(t, c.g, nullptr, nullptr, nullptr, nullptr, c.rows, c.out, tr_fin_stats(t, c)));
   if (!c.act_next) tr_layer_act(t, c);
@@ -701,7 +736,7 @@ static int gemm_layer_backward(az_trainer* t, TrLayer& c, bool accumulate) {
     // the bias of a layer that feeds a train-mode BatchNorm has gradient sum(dg) = gamma invstd (sum dy - R m0 - m1 sum xhat)
     // = 0 exactly (the batch mean absorbs it): its slot in gblob stays 0 and only the L2 term moves it
   } else {
-    if (c.relu) hipLaunchKernelGGL(k_tr_relu_bwd, dim3(tr_grid(n)), dim3(256), 0, t->stream, dg, c.a, n);
+    if (c.relu) tr_relu_bwd(t, dg, c.a, n);
     TrFinal fin{}; fin.mode = 3; fin.out0 = t->gblob + c.off_b;
     AZCHK(tr_colsum<2>(t, dg, nullptr, nullptr, nullptr, nullptr, c.rows, c.out, fin));
   }
@@ -742,15 +777,8 @@ static int tr_forward_backward(az_trainer* t, const int* idx_host, double* d_sum
   TrLayer& val = t->layers[t->ival];
   // ---------------- loss ----------------
   // mean(W)/Wmean / sum(W) = 1 / (B Wmean): the gradient scale needs no reduction first (learning.jl:88)
-  double *tw = t->terms, *tkl = t->terms + B, *tmse = t->terms + 2 * (size_t)B, *tinv = t->terms + 3 * (size_t)B;
-  if (A <= AZ_MAX_ACTIONS)
-    hipLaunchKernelGGL(k_tr_loss, dim3(tr_grid(B)), dim3(256), 0, st, pol.g, val.g, t->bA, t->bP, t->bV, t->bW, B, A,
-                       (float)t->cfg.nonvalidity_penalty, (float)t->cfg.rewards_renormalization, 1.0f / ((float)B * d->Wmean), pol.da, val.da, tw, tkl, tmse, tinv);
-  else                                                              // 64 threads per workgroup: the rows of a wavefront's samples are 4 A bytes apart, so more CUs share the strided reads
-    hipLaunchKernelGGL(k_tr_loss_wide, dim3((B + 63) / 64), dim3(64), 0, st, pol.g, val.g, t->bA, t->bP, t->bV, t->bW, B, A,
-                       (float)t->cfg.nonvalidity_penalty, (float)t->cfg.rewards_renormalization, 1.0f / ((float)B * d->Wmean), pol.da, val.da, tw, tkl, tmse, tinv);
-  hipLaunchKernelGGL(k_tr_sumsq, dim3(1024), dim3(256), 0, st, blob, t->trainable, (long long)t->nparams, t->bsums + 8);
-  hipLaunchKernelGGL(k_tr_step_sums, dim3(1), dim3(256), 0, st, tw, tkl, tmse, tinv, B, t->bsums + 8, 1024, d_sums);
+  tr_loss(t, pol.g, val.g, (float)t->cfg.nonvalidity_penalty, (float)t->cfg.rewards_renormalization, 1.0f / ((float)B * d->Wmean), pol.da, val.da, false);
+  tr_step_sums(t, d_sums);
   // ---------------- backward ----------------
   // The layers in reverse: every consumer of an activation comes before its producer, so da is complete when its layer's turn comes.
   // The trunk's last activation has two consumers (the heads): the first writes its da, the second adds to it.
@@ -987,6 +1015,168 @@ extern "C" int az_debug_trainer_gemm(az_trainer* t, int32_t ta, int32_t tb, int3
   HIPCHK(hipStreamSynchronize(t->stream));
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(Cm, dC, sizeof(float) * (size_t)nc, hipMemcpyDeviceToHost));
+  return AZ_OK;
+}
+
+// debug aids (not part of the ABI in azhip.h): the step's reductions and pointwise passes one at a time, as the seams above -- the
+// trainer's own launch helpers (tr_colsum, tr_bn_apply, tr_bn_bwd, tr_bias_act, tr_relu_bwd, tr_im2col, tr_loss, tr_step_sums) on
+// t->stream with t->part, t->sums, t->bn_mf, t->fin_counter, t->env.fin_inside and the helpers' dispatch rules; the arrays of the
+// caller are scratch of the call from the allocator the trainer's own arrays come from.  tests/test_train_passes_gpu.py.
+static int tr_down(float* host, const float* dev, size_t n) { HIPCHK(hipMemcpy(host, dev, sizeof(float) * n, hipMemcpyDeviceToHost)); return AZ_OK; }
+// a host array [R][C] with one guard row behind it that holds `guard` in every column: a kernel that reads a row past the end reads inside the
+// allocation, and what it reads shows in its sums (x = 4096 under a positive activation, g = 4096) instead of depending on what lies behind an array
+static int tr_up_guarded(Scratch& tmp, float** p, const float* host, size_t n, int C, float guard) {
+  AZCHK(tr_up(tmp, p, nullptr, n + (size_t)C));
+  HIPCHK(hipMemcpy(*p, host, sizeof(float) * n, hipMemcpyHostToDevice));
+  const std::vector<float> row((size_t)C, guard);
+  HIPCHK(hipMemcpy(*p + n, row.data(), sizeof(float) * (size_t)C, hipMemcpyHostToDevice));
+  return AZ_OK;
+}
+// column sums of `mode` (0: x, x^2; 1: dy, dy xhat with dy = x (out_act > 0), xhat = (g - mean) invstd; 2: x, 0) over x[R][C] through
+// tr_colsum<mode>, finished as fin_mode says (TrFinal):
+//   mode 1 reads out_act, g [R][C] and stat_in[2][C] = mean, invstd
+//   fin_mode 1 reads fin_in[3][C] = bias, running mean, running variance and writes fin_out[4][C] = mean, invstd, running mean, running variance
+//   fin_mode 2 writes fin_out[4][C] = dbeta, dgamma, mf[2][C] (mf = t->bn_mf);  fin_mode 3 writes fin_out[C] = out0
+// sums[2][C]: t->sums (the separate second stage writes them; the second stage inside the producer does not: NaN then).
+// info[4] = what tr_colsum launched: chunks, 1 if k_tr_colsum1v, 1 if the second stage ran inside the producer, gridDim.y of the producer.
+// x, out_act and g lie in scratch with a guard row behind them (tr_up_guarded).  Refuses an (R, C) whose partials, sums or means the trainer's
+// scratch cannot hold.
+extern "C" int az_debug_trainer_colsum(az_trainer* t, int32_t mode, int64_t R, int32_t C, const float* x, const float* out_act, const float* g, int64_t n,
+                                       const float* stat_in, int32_t fin_mode, float momentum, int32_t with_bias, const float* fin_in,
+                                       double* sums, float* fin_out, int32_t* info) {
+  TRAINER(t);
+  if (mode < 0 || mode > 2 || fin_mode < 0 || fin_mode > 3) return fail(AZ_ERR_BAD_ARG, "mode %d (0 .. 2), fin_mode %d (0 .. 3)", mode, fin_mode);
+  if (R < 1 || C < 1 || R > (int64_t)1 << 40 || n != R * (int64_t)C || !x || !sums) return fail(AZ_ERR_BAD_ARG, "x must hold R x C = %lld floats, R and C positive", (long long)(R * (int64_t)C));
+  if ((mode == 1) != (out_act && g && stat_in)) return fail(AZ_ERR_BAD_ARG, "mode 1 and only mode 1 takes out_act, g and stat_in");
+  if ((fin_mode != 0) != (fin_out != nullptr) || (fin_mode == 1) != (fin_in != nullptr)) return fail(AZ_ERR_BAD_ARG, "fin_mode %d: fin_out %s, fin_in %s", fin_mode, fin_mode ? "needed" : "not taken", fin_mode == 1 ? "needed" : "not taken");
+  if (fin_mode == 1 && R < 2) return fail(AZ_ERR_BAD_ARG, "batch statistics need two rows");
+  const int64_t nchunks = (R + TR_CHUNK - 1) / TR_CHUNK;
+  if ((size_t)nchunks * 2 * (size_t)C > t->npart) return fail(AZ_ERR_BAD_ARG, "%lld chunks x 2 x %d columns do not fit the trainer's %zu partials", (long long)nchunks, C, t->npart);
+  if (C > t->wsum) return fail(AZ_ERR_BAD_ARG, "%d columns do not fit the trainer's sums (%d)", C, t->wsum);
+  if (fin_mode == 2 && C > t->wbn) return fail(AZ_ERR_BAD_ARG, "%d columns do not fit the trainer's batch-norm means (%d)", C, t->wbn);
+  Scratch tmp;
+  float *dx = nullptr, *da = nullptr, *dgg = nullptr, *dstat = nullptr, *dfin = nullptr, *dout = nullptr;
+  AZCHK(tr_up_guarded(tmp, &dx, x, (size_t)n, C, 4096.0f));
+  if (mode == 1) { AZCHK(tr_up_guarded(tmp, &da, out_act, (size_t)n, C, 1.0f)); AZCHK(tr_up_guarded(tmp, &dgg, g, (size_t)n, C, 4096.0f)); AZCHK(tr_up(tmp, &dstat, stat_in, 2 * (size_t)C)); }
+  // every vector of the finisher an array of its own, as the layers' mean / invstd are
+  float* o[4] = {nullptr, nullptr, nullptr, nullptr};
+  TrFinal fin{};
+  fin.mode = fin_mode; fin.R = R; fin.momentum = momentum;
+  if (fin_mode == 1) {
+    AZCHK(tr_up(tmp, &dfin, fin_in, (size_t)C));
+    for (int k = 0; k < 4; ++k) AZCHK(tr_up(tmp, &o[k], k >= 2 ? fin_in + (size_t)(k - 1) * C : nullptr, (size_t)C));
+    fin.bias = with_bias ? dfin : nullptr; fin.mean = o[0]; fin.invstd = o[1]; fin.run_mean = o[2]; fin.run_var = o[3];
+  } else if (fin_mode == 2) {
+    for (int k = 0; k < 2; ++k) AZCHK(tr_up(tmp, &o[k], nullptr, (size_t)C));
+    fin.dbeta = o[0]; fin.dgamma = o[1]; fin.mf = t->bn_mf;
+  } else if (fin_mode == 3) { AZCHK(tr_up(tmp, &dout, nullptr, (size_t)C)); fin.out0 = dout; }
+  HIPCHK(hipStreamSynchronize(t->stream));
+  HIPCHK(hipStreamSynchronize(t->side));
+  HIPCHK(hipMemsetAsync(t->sums, 0xff, sizeof(double) * 2 * (size_t)C, t->stream));   // NaN where no second stage writes
+  int32_t ran[4] = {0, 0, 0, 0};
+  if (mode == 0) AZCHK(tr_colsum<0>(t, dx, nullptr, nullptr, nullptr, nullptr, R, C, fin, ran));
+  else if (mode == 1) AZCHK(tr_colsum<1>(t, dx, da, dgg, dstat, dstat + C, R, C, fin, ran));
+  else AZCHK(tr_colsum<2>(t, dx, nullptr, nullptr, nullptr, nullptr, R, C, fin, ran));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(sums, t->sums, sizeof(double) * 2 * (size_t)C, hipMemcpyDeviceToHost));
+  if (fin_mode == 1) for (int k = 0; k < 4; ++k) AZCHK(tr_down(fin_out + (size_t)k * C, o[k], (size_t)C));
+  if (fin_mode == 2) { for (int k = 0; k < 2; ++k) AZCHK(tr_down(fin_out + (size_t)k * C, o[k], (size_t)C)); AZCHK(tr_down(fin_out + 2 * (size_t)C, t->bn_mf, 2 * (size_t)C)); }
+  if (fin_mode == 3) AZCHK(tr_down(fin_out, dout, (size_t)C));
+  if (info) for (int k = 0; k < 4; ++k) info[k] = ran[k];
+  return AZ_OK;
+}
+// the pointwise passes over [rows][C], n = rows x C:
+//   op 0  out = relu(gamma ((g - mean) invstd) + beta (+ second))                 tr_bn_apply;  consts[4][C] = mean, invstd, gamma, beta
+//   op 1  out = dg, written over da in place; out2 (optional) = dy                tr_bn_bwd;    first = da, second = a, consts[3][C] = mean, invstd, gamma,
+//                                                                                              mf[2][C] -> t->bn_mf
+//   op 2  out = [relu](g + bias) in place                                         tr_bias_act;  consts[C] = bias, flag = relu
+//   op 3  out = first (second > 0) in place                                       tr_relu_bwd;  first = dy, second = y
+extern "C" int az_debug_trainer_bn(az_trainer* t, int32_t op, int64_t rows, int32_t C, const float* g, const float* first, const float* second,
+                                   const float* consts, const float* mf, int32_t flag, int64_t n, float* out, float* out2) {
+  TRAINER(t);
+  if (op < 0 || op > 3) return fail(AZ_ERR_BAD_ARG, "op %d (0 .. 3)", op);
+  if (rows < 1 || C < 1 || rows > (int64_t)1 << 40 || n != rows * (int64_t)C || !out) return fail(AZ_ERR_BAD_ARG, "the arrays must hold rows x C = %lld floats, rows and C positive", (long long)(rows * (int64_t)C));
+  const bool ok = op == 0 ? (g && !first && consts && !mf && !out2) : op == 1 ? (g && first && second && consts && mf)
+                : op == 2 ? (g && !first && !second && consts && !mf && !out2) : (!g && first && second && !consts && !mf && !out2);
+  if (!ok) return fail(AZ_ERR_BAD_ARG, "op %d does not take these arrays", op);
+  if (op == 1 && C > t->wbn) return fail(AZ_ERR_BAD_ARG, "%d columns do not fit the trainer's batch-norm means (%d)", C, t->wbn);
+  Scratch tmp;
+  float *dg = nullptr, *d1 = nullptr, *d2 = nullptr, *dout = nullptr, *dout2 = nullptr, *dc[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (g) AZCHK(tr_up(tmp, &dg, g, (size_t)n));
+  if (first) AZCHK(tr_up(tmp, &d1, first, (size_t)n));
+  if (second) AZCHK(tr_up(tmp, &d2, second, (size_t)n));
+  const int nc = op == 0 ? 4 : op == 1 ? 3 : op == 2 ? 1 : 0;
+  for (int k = 0; k < nc; ++k) AZCHK(tr_up(tmp, &dc[k], consts + (size_t)k * C, (size_t)C));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  HIPCHK(hipStreamSynchronize(t->side));
+  const float* res = nullptr;
+  if (op == 0) {
+    AZCHK(tr_up(tmp, &dout, nullptr, (size_t)n));
+    tr_bn_apply(t, BnIn{dg, dc[0], dc[1], dc[2], dc[3], d2, dout}, n, C);
+    res = dout;
+  } else if (op == 1) {
+    if (out2) AZCHK(tr_up(tmp, &dout2, nullptr, (size_t)n));
+    HIPCHK(hipMemcpy(t->bn_mf, mf, sizeof(float) * 2 * (size_t)C, hipMemcpyHostToDevice));
+    tr_bn_bwd(t, d1, d2, dg, dc[0], dc[1], dc[2], n, C, d1, dout2);
+    res = d1;
+  } else if (op == 2) { tr_bias_act(t, dg, dc[0], n, C, flag != 0); res = dg; }
+  else { tr_relu_bwd(t, d1, d2, n); res = d1; }
+  HIPCHK(hipStreamSynchronize(t->stream));
+  HIPCHK(hipGetLastError());
+  AZCHK(tr_down(out, res, (size_t)n));
+  if (dout2) AZCHK(tr_down(out2, dout2, (size_t)n));
+  return AZ_OK;
+}
+// the stem's gather on the trainer's geometry and batch: planes[B][C][H][W] -> col[B H W][9 C], column = tap C + c, tap = 3 (dy + 1) + (dx + 1)
+extern "C" int az_debug_trainer_im2col(az_trainer* t, const float* planes, int64_t n_in, float* col, int64_t n_out) {
+  TRAINER(t);
+  if (!t->ntower) return fail(AZ_ERR_BAD_ARG, "the trainer of a SimpleNet engine has no convolution");
+  const TrLayer& c = t->layers[0];
+  const int64_t want_in = (int64_t)t->B * t->gi.C * t->gi.P, want_out = (int64_t)c.rows * c.in;
+  if (!planes || n_in != want_in) return fail(AZ_ERR_BAD_ARG, "planes must hold %lld floats", (long long)want_in);
+  if (!col || n_out != want_out) return fail(AZ_ERR_BAD_ARG, "col must hold %lld floats", (long long)want_out);
+  HIPCHK(hipStreamSynchronize(t->stream));
+  HIPCHK(hipStreamSynchronize(t->side));
+  HIPCHK(hipMemcpy(t->bX, planes, sizeof(float) * (size_t)want_in, hipMemcpyHostToDevice));
+  tr_im2col(t, t->bX, c);
+  HIPCHK(hipStreamSynchronize(t->stream));
+  HIPCHK(hipGetLastError());
+  return tr_down(col, c.col, (size_t)want_out);
+}
+// the loss of one batch of B = the trainer's batch samples and A = the game's actions through tr_loss (force_wide: k_tr_loss_wide whatever A):
+// dlogits[B][A], dt[B] and terms[4][B] = w, kl, mse, inv per sample; *wide = which kernel ran.  Then (terms_in given) k_tr_step_sums through
+// tr_step_sums on terms_in[4][B]: sums5 = their four sums and the sum of squares of the trainable parameters.
+extern "C" int az_debug_trainer_loss(az_trainer* t, int32_t force_wide, const float* logits, const float* tpre, const float* Am, const float* P, int64_t n_ba,
+                                     const float* V, const float* W, int64_t n_b, float cinv, float rho, float gscale,
+                                     float* dlogits, float* dt, double* terms, int32_t* wide, const double* terms_in, double* sums5) {
+  TRAINER(t);
+  const int B = t->B, A = t->gi.A;
+  if (!logits || !Am || !P || !dlogits || n_ba != (int64_t)B * A) return fail(AZ_ERR_BAD_ARG, "logits, Am, P and dlogits must hold %lld floats", (long long)B * A);
+  if (!tpre || !V || !W || !dt || !terms || n_b != B) return fail(AZ_ERR_BAD_ARG, "tpre, V, W and dt must hold %d floats, terms 4 x %d doubles", B, B);
+  if ((terms_in != nullptr) != (sums5 != nullptr)) return fail(AZ_ERR_BAD_ARG, "terms_in and sums5 go together");
+  if (!(rho > 0.0f)) return fail(AZ_ERR_BAD_ARG, "rho must be > 0");
+  Scratch tmp;
+  float *dl = nullptr, *dtp = nullptr, *ddl = nullptr, *ddt = nullptr;
+  AZCHK(tr_up(tmp, &dl, logits, (size_t)n_ba)); AZCHK(tr_up(tmp, &dtp, tpre, (size_t)B));
+  AZCHK(tr_up(tmp, &ddl, nullptr, (size_t)n_ba)); AZCHK(tr_up(tmp, &ddt, nullptr, (size_t)B));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  HIPCHK(hipStreamSynchronize(t->side));
+  HIPCHK(hipMemcpy(t->bA, Am, sizeof(float) * (size_t)n_ba, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(t->bP, P, sizeof(float) * (size_t)n_ba, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(t->bV, V, sizeof(float) * (size_t)B, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(t->bW, W, sizeof(float) * (size_t)B, hipMemcpyHostToDevice));
+  const bool w = tr_loss(t, dl, dtp, cinv, rho, gscale, ddl, ddt, force_wide != 0);
+  HIPCHK(hipStreamSynchronize(t->stream));
+  HIPCHK(hipGetLastError());
+  AZCHK(tr_down(dlogits, ddl, (size_t)n_ba)); AZCHK(tr_down(dt, ddt, (size_t)B));
+  HIPCHK(hipMemcpy(terms, t->terms, sizeof(double) * 4 * (size_t)B, hipMemcpyDeviceToHost));
+  if (wide) *wide = w;
+  if (terms_in) {
+    HIPCHK(hipMemcpy(t->terms, terms_in, sizeof(double) * 4 * (size_t)B, hipMemcpyHostToDevice));
+    tr_step_sums(t, t->bsums);
+    HIPCHK(hipStreamSynchronize(t->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(sums5, t->bsums, sizeof(double) * 5, hipMemcpyDeviceToHost));
+  }
   return AZ_OK;
 }
 

@@ -6,7 +6,8 @@ tests/exact_nets.py): inputs are integers in [-3, 3], weights integers in [-2, 2
 integers, so every fp32 partial sum is a small integer (or a multiple of 1/2) far below 2^24 in ANY summation order, and a wrong row,
 tap, channel, chunk or split is a bit difference against a float64 reference.  The kernels run through the debug seams of
 csrc/train.hip (az_debug_trainer_wgrad / _conv / _gemm): the trainer's own launch helpers, geometry tables, partial buffers, fragment
-maps, workspace and split rule.
+maps, workspace and split rule.  The step's other kernels -- column sums and their second stages, batch-norm apply / backward, the dense
+epilogues, the stem's im2col, the loss, the step sums -- are held the same way in tests/test_train_passes_gpu.py.
 
 Shapes are DERIVED from the device's CU count with the launch arithmetic of trainer_build / tr_wgrad16_f / tr_conv16 / gemm_f32
 (restated below), and every case asserts that it reaches what it is named for: on a chip with another CU count a case fails instead
