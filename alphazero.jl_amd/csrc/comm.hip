@@ -475,8 +475,9 @@ extern "C" int az_comm_gather_push_planes(az_comm* c, az_plane_memory* src, az_p
       if (game_ids[k] < 0) return fail(AZ_ERR_BAD_ARG, "game %d of the table has the negative id %d", k, (int)game_ids[k]);
       B += game_lens[k];
     }
-    if (B != src->cur_batch) return fail(AZ_ERR_BAD_ARG, "the table's lengths sum to %lld, the source's current batch holds %lld samples", B, (long long)src->cur_batch);
-    if (B > src->cap) return fail(AZ_ERR_STATE, "the source's batch of %lld samples was partly overwritten (capacity %lld)", B, (long long)src->cap);
+    // the table must account for the batch as it was pushed (the stored, unclamped count), and all of it must still be held
+    if (B != src->ring.cur_batch) return fail(AZ_ERR_BAD_ARG, "the table's lengths sum to %lld, the source's current batch holds %lld samples", B, (long long)src->ring.cur_batch);
+    if (B > src->ring.cap) return fail(AZ_ERR_STATE, "the source's batch of %lld samples was partly overwritten (capacity %lld)", B, (long long)src->ring.cap);
     HIPCHK(hipStreamSynchronize(src->stream));
     if (dst) HIPCHK(hipStreamSynchronize(dst->stream));
     return AZ_OK;
@@ -533,7 +534,7 @@ extern "C" int az_comm_gather_push_planes(az_comm* c, az_plane_memory* src, az_p
   }));
   std::vector<std::vector<pg::Game>> tables((size_t)W);
   for (int r = 0; r < W; ++r) tables[(size_t)r].assign(tall.begin() + (size_t)r * maxg, tall.begin() + (size_t)r * maxg + (size_t)all[(size_t)COMM_WORDS * r]);
-  const pg::Plan plan = pg::make_plan(tables, R, dst ? (long long)dst->cap : 0);
+  const pg::Plan plan = pg::make_plan(tables, R, dst ? (long long)dst->ring.cap : 0);
   if (plan.dup) return fail(AZ_ERR_BAD_ARG, "game id %d occurs twice in the ranks' tables (ids are global and must be distinct); nothing was pushed", (int)plan.dup_id);
   std::vector<long long> hplan(n_plan, 0);
   long long *h_prefix = hplan.data(), *h_start = h_prefix + n_prefix, *h_goff = h_start + n_start, *h_B = h_goff + (W + 1), *h_src = h_B + W;
@@ -552,14 +553,14 @@ extern "C" int az_comm_gather_push_planes(az_comm* c, az_plane_memory* src, az_p
   const long long* d_myprefix = d_prefix + h_goff[c->rank] + c->rank;
   // 4. rounds: pack -> all-gather -> scatter, R rows per rank; every rank runs plan.rounds of them
   const int vec = (RW % 4 == 0 && rb % 16 == 0) ? 4 : RW % 2 == 0 ? 2 : 1;
-  const long long seq0 = src->total - B;
+  const long long seq0 = src->ring.select(1).seq0;                     // last_batch: exactly the B samples, after the two checks above
   const auto rounds = [&]() -> int {
     HIPCHK(hipMemcpyAsync(d_plan, hplan.data(), sizeof(long long) * n_plan, hipMemcpyHostToDevice, c->stream));
     for (long long k = 0; k < plan.rounds; ++k) {
       const long long base = k * R, nrows = pg::round_rows_of(plan, c->rank, k);
       HIPCHK(hipEventRecord(c->ev[0], c->stream));
       if (nrows > 0) {
-#define PG_PACK(V) hipLaunchKernelGGL(k_pg_pack<V>, dim3(pm_grid(nrows)), dim3(64 * PM_WAVES), 0, c->stream, src->d_XA, src->d_D, src->d_n, (long long)src->cap, \
+#define PG_PACK(V) hipLaunchKernelGGL(k_pg_pack<V>, dim3(pm_grid(nrows)), dim3(64 * PM_WAVES), 0, c->stream, src->d_XA, src->d_D, src->d_n, (long long)src->ring.cap, \
                                       seq0, base, nrows, d_myprefix, d_src, (int)ng, RW, ND, rb, d_rsend)
         if (vec == 4) PG_PACK(uint4); else if (vec == 2) PG_PACK(uint2); else PG_PACK(unsigned int);
 #undef PG_PACK
@@ -570,7 +571,7 @@ extern "C" int az_comm_gather_push_planes(az_comm* c, az_plane_memory* src, az_p
       HIPCHK(hipEventRecord(c->ev[2], c->stream));
       if (dst && plan.T > plan.skip) {
 #define PG_SCATTER(V) hipLaunchKernelGGL(k_pg_scatter<V>, dim3(pm_grid((long long)W * R)), dim3(64 * PM_WAVES), 0, c->stream, d_rall, R, base, W, d_B, d_goff, \
-                                         d_prefix, d_start, plan.skip, (long long)dst->total, (long long)dst->cap, RW, ND, rb, dst->d_XA, dst->d_D, dst->d_n)
+                                         d_prefix, d_start, plan.skip, (long long)dst->ring.total, (long long)dst->ring.cap, RW, ND, rb, dst->d_XA, dst->d_D, dst->d_n)
         if (vec == 4) PG_SCATTER(uint4); else if (vec == 2) PG_SCATTER(uint2); else PG_SCATTER(unsigned int);
 #undef PG_SCATTER
         HIPCHK(hipGetLastError());
@@ -586,7 +587,7 @@ extern "C" int az_comm_gather_push_planes(az_comm* c, az_plane_memory* src, az_p
     return AZ_OK;
   };
   AZCHK(collective(c, rounds));
-  if (dst) { dst->total += plan.T; dst->cur_batch += plan.T; }       // push_trace! of every game: mem.cur_batch_size += n
+  if (dst) dst->ring.pushed(plan.T, true);                           // push_trace! of every game
   if (stats) {
     memset(stats, 0, sizeof *stats);
     stats->games = totg; stats->moves = plan.T; stats->ranks = W;

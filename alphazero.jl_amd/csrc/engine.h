@@ -1,6 +1,6 @@
 // engine.h -- what the translation units of libazhip.so share: the engine record, error / launch macros, the
 // profiling helpers, the entry points of net.hip (network launches) used by azhip.hip, memory.hip and train.hip, the records of
-// the replay memories and their data set (with the one function that makes an empty az_dataset), the check that makes a device
+// the replay memories and their data set (with the frame all three data-set creators share), the check that makes a device
 // current (use_device) and the scoped owner of a call's device scratch (Scratch).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,6 +29,7 @@
 #include "resnet.h"
 #include "resnet16.h"
 #include "resnet16b.h"
+#include "ring_books.h"
 #include "simplenet.h"
 #include "tower_choice.h"
 #include "tree.h"
@@ -395,8 +396,8 @@ struct az_memory {
   int game = 0, device = 0;
   GameInfo gi = {};
   hipStream_t stream = nullptr;
-  az_sample* d_buf = nullptr;
-  int64_t cap = 0, total = 0, cur_batch = 0;   // total = samples pushed since the last empty!; sample of sequence q sits at q % cap
+  az_sample* d_buf = nullptr;         // [ring.cap]
+  Ring ring;                          // ring_books.h
 };
 struct az_dataset {
   int game = 0, device = 0;
@@ -420,6 +421,29 @@ inline int dataset_new(int game, int device, const GameInfo& gi, hipStream_t sha
   *out = d;
   return AZ_OK;
 }
+// ---- the frame of the three data-set creators (from a keyed memory, from a plane memory, from caller tensors) ----
+// what all of them ask of `which` and of samples_weighing_policy
+inline int dataset_check_args(int which, int weighing_policy) {
+  if (which != 0 && which != 1) return fail(AZ_ERR_BAD_ARG, "which must be 0 (get_experience) or 1 (last_batch)");
+  if (weighing_policy < AZ_WEIGHT_CONSTANT || weighing_policy > AZ_WEIGHT_LINEAR) return fail(AZ_ERR_BAD_ARG, "unknown samples_weighing_policy %d", weighing_policy);
+  return AZ_OK;
+}
+// dataset_new, then build(d); *out gets the data set if that succeeded, otherwise it is destroyed and *out stays NULL
+template <class Build> inline int dataset_create(int game, int device, const GameInfo& gi, hipStream_t share, az_dataset** out, Build build) {
+  az_dataset* d = nullptr;
+  AZCHK(dataset_new(game, device, gi, share, &d));
+  const int st = build(d);
+  if (st != AZ_OK) { az_dataset_destroy(d); return st; }
+  *out = d;
+  return AZ_OK;
+}
+// the five tensors of convert_samples for n rows of d's geometry
+inline int dataset_alloc_tensors(az_dataset* d, int64_t n) {
+  const size_t N = (size_t)n, nA = (size_t)d->gi.A, xs = (size_t)d->gi.C * d->gi.P;
+  AZCHK(mem_alloc(&d->allocs, &d->d_W, N)); AZCHK(mem_alloc(&d->allocs, &d->d_V, N));
+  AZCHK(mem_alloc(&d->allocs, &d->d_A, N * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_P, N * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_X, N * xs));
+  return AZ_OK;
+}
 // plane_memory.hip: MemoryBuffer for a host-stepped game.  A sample is what the network sees -- the row (X, A) of RW = C*H*W + nA
 // Float32 words -- plus ND = nA + 2 doubles (pi by full action index, z, t) and n.
 struct az_plane_memory {
@@ -430,7 +454,7 @@ struct az_plane_memory {
   float* d_XA = nullptr;             // [cap][RW]
   double* d_D = nullptr;             // [cap][ND]
   long long* d_n = nullptr;          // [cap]
-  int64_t cap = 0, total = 0, cur_batch = 0;   // as az_memory
+  Ring ring;                         // ring_books.h; d_XA, d_D and d_n have ring.cap rows
   int hash_bits = 128;               // az_debug_plane_memory_hash_bits lowers it
   // GI.symmetries as the host declared them (az_plane_memory_set_symmetries): symmetry k as ONE gather over the row's RW words,
   // perm[k][w] = xperm[k][w] for w < xs, xs + aperm[k][w - xs] after; 16 bits hold an index below RW <= xs + 126

@@ -238,25 +238,8 @@ __global__ void __launch_bounds__(256) k_batch_sums(const double* __restrict__ t
   if (threadIdx.x < 5) out[(size_t)blockIdx.x * 5 + threadIdx.x] = sh[threadIdx.x][0];
 }
 
-struct DevReducer {                     // deterministic sum of doubles (prims.h: fixed tiles, fixed tree)
-  Scratch mem;
-  double* tmp = nullptr;
-  int init(long long nmax, hipStream_t) { return mem.alloc(&tmp, prims::sum_tmp_doubles(nmax)); }
-  int sum(const double* d_in, long long n, hipStream_t st, double* out) {
-    double* d_res = nullptr;
-    HIPCHK(prims::sum_doubles(d_in, n, tmp, &d_res, st));
-    HIPCHK(hipMemcpyAsync(out, d_res, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return AZ_OK;
-  }
-  int sum(const long long* d_in, long long n, hipStream_t st, long long* out) {       // sum(e.n) is an Int: exact, whatever its size
-    long long* d_res = nullptr;
-    HIPCHK(prims::sum_values<long long>(d_in, n, (long long*)tmp, &d_res, st));
-    HIPCHK(hipMemcpyAsync(out, d_res, sizeof(long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return AZ_OK;
-  }
-};
+// the sum of sum(e.n) (DevReducer, prims.h), instantiated ahead of the per-game templates: the unit's kernels keep the order its code object had
+template int DevReducer::sum<long long>(const long long*, long long, hipStream_t, long long*);
 
 #define MEMORY(m) if (!(m)) return fail(AZ_ERR_BAD_ARG, "memory is NULL"); HIPCHK(hipSetDevice((m)->device))
 
@@ -270,7 +253,7 @@ extern "C" int az_memory_create(int32_t game, int32_t device, int64_t capacity, 
   AZCHK(use_device(device));
   az_memory* m = new (std::nothrow) az_memory();
   if (!m) return fail(AZ_ERR_HIP, "out of host memory");
-  m->game = game; m->device = device; m->gi = gi; m->cap = capacity;
+  m->game = game; m->device = device; m->gi = gi; m->ring.cap = capacity;
   int st = [&]() -> int {
     HIPCHK(hipStreamCreate(&m->stream));
     AZCHK(mem_alloc<az_sample>(nullptr, &m->d_buf, (size_t)capacity));
@@ -293,19 +276,17 @@ int memory_push_device(az_memory* m, const az_move_rec* d_moves, const std::vect
   if (!ng) return AZ_OK;
   std::vector<long long> seq0(ng);
   long long tot = 0;
-  for (int g = 0; g < ng; ++g) { seq0[g] = m->total + tot; tot += cnt[g]; }
+  for (int g = 0; g < ng; ++g) { seq0[g] = m->ring.total + tot; tot += cnt[g]; }
   long long *d_first, *d_seq; int* d_cnt;
   Scratch tmp;
   AZCHK(tmp.alloc(&d_first, ng)); AZCHK(tmp.alloc(&d_cnt, ng)); AZCHK(tmp.alloc(&d_seq, ng));
   HIPCHK(hipMemcpyAsync(d_first, first.data(), sizeof(long long) * ng, hipMemcpyHostToDevice, m->stream));
   HIPCHK(hipMemcpyAsync(d_cnt, cnt.data(), sizeof(int) * ng, hipMemcpyHostToDevice, m->stream));
   HIPCHK(hipMemcpyAsync(d_seq, seq0.data(), sizeof(long long) * ng, hipMemcpyHostToDevice, m->stream));
-  const long long min_seq = std::max<long long>(0, m->total + tot - m->cap);
-  DISPATCH_GAME(m->game, hipLaunchKernelGGL((k_mem_push<Gm>), dim3((ng + 255) / 256), dim3(256), 0, m->stream, d_moves, d_first, d_cnt, d_seq, ng, gamma, m->d_buf, (long long)m->cap, min_seq));
+  DISPATCH_GAME(m->game, hipLaunchKernelGGL((k_mem_push<Gm>), dim3((ng + 255) / 256), dim3(256), 0, m->stream, d_moves, d_first, d_cnt, d_seq, ng, gamma, m->d_buf, (long long)m->ring.cap, (long long)m->ring.min_seq(tot)));
   HIPCHK(hipStreamSynchronize(m->stream));
   HIPCHK(hipGetLastError());
-  m->total += tot;
-  m->cur_batch += tot;                                             // mem.cur_batch_size += n, memory.jl:86
+  m->ring.pushed(tot, true);
   return AZ_OK;
 }
 extern "C" int az_memory_push(az_memory* m, const az_trace_buf* tr, double gamma) {
@@ -342,64 +323,54 @@ extern "C" int az_memory_push_engine(az_memory* m, az_engine* e, double gamma) {
   return memory_push_device(m, e->d_phase, first, cnt, gamma);
 }
 // push!(mem.buf, sample) for host-resident TrainingSamples (a reference-side MemoryBuffer, or subsets such as the game
-// stages of memory_report, src/learning.jl:192-216); cur_batch_size is not advanced (push_trace! does that)
+// stages of memory_report, src/learning.jl:192-216)
 extern "C" int az_memory_push_samples(az_memory* m, const az_sample* samples, int64_t n) {
   MEMORY(m);
   if (n < 0 || (n > 0 && !samples)) return fail(AZ_ERR_BAD_ARG, "NULL samples");
-  // keep only what survives in the ring, oldest first, then at most two contiguous copies
-  const int64_t skip = std::max<int64_t>(0, n - m->cap);
-  int64_t left = n - skip;
+  // keep only what survives in the ring, oldest first
+  const int64_t skip = m->ring.skip(n);
   const az_sample* src = samples + skip;
-  int64_t seq = m->total + skip;
-  while (left > 0) {
-    const int64_t pos = seq % m->cap, run = std::min<int64_t>(left, m->cap - pos);
-    HIPCHK(hipMemcpyAsync(m->d_buf + pos, src, sizeof(az_sample) * (size_t)run, hipMemcpyHostToDevice, m->stream));
-    src += run; seq += run; left -= run;
+  for (const Ring::Run& r : m->ring.runs(m->ring.total + skip, n - skip)) {
+    HIPCHK(hipMemcpyAsync(m->d_buf + r.pos, src, sizeof(az_sample) * (size_t)r.run, hipMemcpyHostToDevice, m->stream));
+    src += r.run;
   }
   HIPCHK(hipStreamSynchronize(m->stream));
-  m->total += n;
+  m->ring.pushed(n, false);
   return AZ_OK;
 }
 
 extern "C" int az_memory_length(az_memory* m, int64_t* length, int64_t* cur_batch_size) {
   MEMORY(m);
-  const int64_t len = std::min<int64_t>(m->total, m->cap);
-  if (length) *length = len;
-  if (cur_batch_size) *cur_batch_size = std::min<int64_t>(m->cur_batch, len);     // memory.jl:53
+  if (length) *length = m->ring.len();
+  if (cur_batch_size) *cur_batch_size = m->ring.batch();
   return AZ_OK;
 }
-extern "C" int az_memory_new_batch(az_memory* m) { MEMORY(m); m->cur_batch = 0; return AZ_OK; }
-extern "C" int az_memory_empty(az_memory* m) { MEMORY(m); m->total = 0; m->cur_batch = 0; return AZ_OK; }
+extern "C" int az_memory_new_batch(az_memory* m) { MEMORY(m); m->ring.new_batch(); return AZ_OK; }
+extern "C" int az_memory_empty(az_memory* m) { MEMORY(m); m->ring.empty(); return AZ_OK; }
 
 template <class Gm>
 static int dataset_build(az_memory* m, az_dataset* d, int which, bool use_sym, bool merge, int policy) {
   hipStream_t st = m->stream;
-  const int64_t len = std::min<int64_t>(m->total, m->cap);
-  const int64_t n0 = which == 1 ? std::min<int64_t>(m->cur_batch, len) : len;
-  const long long seq0 = m->total - n0;                            // the newest n0 samples, oldest first
+  const Ring::Selection sel = m->ring.select(which);               // may be empty: the data set then has n = 0
+  const int64_t n0 = sel.n0;
   const int nsym = use_sym ? Gm::NSYM : 0;
   const int64_t n1 = n0 * (1 + nsym);
   if (n1 > (1LL << 31) - 1) return fail(AZ_ERR_CAPACITY, "data set too large");
   Scratch tmp;
   az_sample* s1;
   AZCHK(tmp.alloc(&s1, (size_t)n1));
-  if (n0) hipLaunchKernelGGL(k_mem_gather, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, m->d_buf, (long long)m->cap, seq0, (long long)n0, s1);
+  if (n0) hipLaunchKernelGGL(k_mem_gather, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, m->d_buf, (long long)m->ring.cap, (long long)sel.seq0, (long long)n0, s1);
   if (nsym && n0) hipLaunchKernelGGL((k_mem_augment<Gm>), dim3((unsigned)((n0 * nsym + 255) / 256)), dim3(256), 0, st, s1, (long long)n0, s1);
   int64_t n2 = n1;
   if (merge && n1 > 0) {
-    unsigned long long *k0, *k1, *ks, *ks2; unsigned int *i0, *i1, *i2; int *head, *seg;
-    AZCHK(tmp.alloc(&k0, (size_t)n1)); AZCHK(tmp.alloc(&k1, (size_t)n1)); AZCHK(tmp.alloc(&ks, (size_t)n1)); AZCHK(tmp.alloc(&ks2, (size_t)n1));
-    AZCHK(tmp.alloc(&i0, (size_t)n1)); AZCHK(tmp.alloc(&i1, (size_t)n1)); AZCHK(tmp.alloc(&i2, (size_t)n1));
-    AZCHK(tmp.alloc(&head, (size_t)n1)); AZCHK(tmp.alloc(&seg, (size_t)n1));
     const unsigned gb = (unsigned)((n1 + 255) / 256);
-    hipLaunchKernelGGL(k_mem_keys, dim3(gb), dim3(256), 0, st, s1, (long long)n1, k0, k1, i0);
-    int* stmp;
-    AZCHK(tmp.alloc(&stmp, std::max(prims::sort_tmp_ints(n1), prims::scan_tmp_ints(n1))));
-    HIPCHK(prims::order_by_key(k0, k1, i0, ks, ks2, i1, i2, n1, stmp, st));   // i2: ascending (key[0], key[1], buffer index)
-    hipLaunchKernelGGL(k_mem_heads, dim3(gb), dim3(256), 0, st, s1, i2, (long long)n1, head);
-    HIPCHK(prims::scan_ints(head, seg, n1, true, stmp, st));
+    Grouping g;
+    AZCHK(group_by_key(tmp, n1, st,
+                       [&](unsigned long long* k0, unsigned long long* k1, unsigned int* idx) { hipLaunchKernelGGL(k_mem_keys, dim3(gb), dim3(256), 0, st, s1, (long long)n1, k0, k1, idx); },
+                       [&](const unsigned long long*, const unsigned int* order, int* head) { hipLaunchKernelGGL(k_mem_heads, dim3(gb), dim3(256), 0, st, s1, order, (long long)n1, head); },
+                       &g));
     int nseg = 0;
-    HIPCHK(hipMemcpyAsync(&nseg, seg + (n1 - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&nseg, g.seg + (n1 - 1), sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     n2 = nseg;
     AZCHK(mem_alloc(&d->allocs, &d->d_samples, (size_t)n2));
@@ -408,16 +379,15 @@ static int dataset_build(az_memory* m, az_dataset* d, int which, bool use_sym, b
     const long long max_long = n1 / MERGE_LONG + 1;
     AZCHK(tmp.alloc(&long_count, 1)); AZCHK(tmp.alloc(&long_list, (size_t)(2 * max_long)));
     HIPCHK(hipMemsetAsync(long_count, 0, sizeof(int), st));
-    hipLaunchKernelGGL(k_mem_merge, dim3((unsigned)((n1 * 16 + 255) / 256)), dim3(256), 0, st, s1, i2, head, seg, (long long)n1, d->d_samples, long_count, long_list);
-    hipLaunchKernelGGL(k_mem_merge_long, dim3((unsigned)max_long), dim3(14 * 64), 0, st, s1, i2, seg, long_count, long_list, d->d_samples);
+    hipLaunchKernelGGL(k_mem_merge, dim3((unsigned)((n1 * 16 + 255) / 256)), dim3(256), 0, st, s1, g.order, g.head, g.seg, (long long)n1, d->d_samples, long_count, long_list);
+    hipLaunchKernelGGL(k_mem_merge_long, dim3((unsigned)max_long), dim3(14 * 64), 0, st, s1, g.order, g.seg, long_count, long_list, d->d_samples);
   } else {
     AZCHK(mem_alloc(&d->allocs, &d->d_samples, (size_t)n2));
     if (n2) HIPCHK(hipMemcpyAsync(d->d_samples, s1, sizeof(az_sample) * (size_t)n2, hipMemcpyDeviceToDevice, st));
   }
   d->n = n2;
-  AZCHK(mem_alloc(&d->allocs, &d->d_envs, (size_t)n2)); AZCHK(mem_alloc(&d->allocs, &d->d_W, (size_t)n2)); AZCHK(mem_alloc(&d->allocs, &d->d_V, (size_t)n2));
-  AZCHK(mem_alloc(&d->allocs, &d->d_A, (size_t)n2 * Gm::A)); AZCHK(mem_alloc(&d->allocs, &d->d_P, (size_t)n2 * Gm::A));
-  AZCHK(mem_alloc(&d->allocs, &d->d_X, (size_t)n2 * Gm::C * Gm::P));
+  AZCHK(mem_alloc(&d->allocs, &d->d_envs, (size_t)n2));
+  AZCHK(dataset_alloc_tensors(d, n2));
   if (n2) {
     double *tw, *thp; long long* tn;
     AZCHK(tmp.alloc(&tw, (size_t)n2)); AZCHK(tmp.alloc(&thp, (size_t)n2)); AZCHK(tmp.alloc(&tn, (size_t)n2));
@@ -425,7 +395,7 @@ static int dataset_build(az_memory* m, az_dataset* d, int which, bool use_sym, b
     const long long ne = (long long)n2 * Gm::C * Gm::P;
     hipLaunchKernelGGL((k_mem_planes<Gm>), dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, d->d_envs, (long long)n2, d->d_X);
     DevReducer red;
-    AZCHK(red.init(n2, st));
+    AZCHK(red.init(n2));
     double sw, shp; long long sn;
     AZCHK(red.sum(tw, n2, st, &sw)); AZCHK(red.sum(thp, n2, st, &shp)); AZCHK(red.sum(tn, n2, st, &sn));
     d->Wtot = sw; d->sum_n = (int64_t)sn;
@@ -450,20 +420,13 @@ extern "C" int az_dataset_create(az_memory* m, int32_t which, int32_t use_symmet
   MEMORY(m);
   if (!out) return fail(AZ_ERR_BAD_ARG, "NULL argument");
   *out = nullptr;
-  if (which != 0 && which != 1) return fail(AZ_ERR_BAD_ARG, "which must be 0 (get_experience) or 1 (last_batch)");
-  if (weighing_policy < AZ_WEIGHT_CONSTANT || weighing_policy > AZ_WEIGHT_LINEAR) return fail(AZ_ERR_BAD_ARG, "unknown samples_weighing_policy %d", weighing_policy);
-  az_dataset* d = nullptr;
-  AZCHK(dataset_new(m->game, m->device, m->gi, m->stream, &d));
-  int st = AZ_OK;
-  switch (m->game) {
-    case AZ_GAME_CONNECT_FOUR: st = dataset_build<ConnectFour>(m, d, which, use_symmetries != 0, use_position_averaging != 0, weighing_policy); break;
-    case AZ_GAME_TICTACTOE: st = dataset_build<TicTacToe>(m, d, which, use_symmetries != 0, use_position_averaging != 0, weighing_policy); break;
-    case AZ_GAME_MANCALA: st = dataset_build<Mancala>(m, d, which, use_symmetries != 0, use_position_averaging != 0, weighing_policy); break;
-    default: st = fail(AZ_ERR_BAD_ARG, "game id %d has no device twin", m->game); break;
-  }
-  if (st != AZ_OK) { az_dataset_destroy(d); return st; }
-  *out = d;
-  return AZ_OK;
+  AZCHK(dataset_check_args(which, weighing_policy));
+  if (m->game == AZ_GAME_GO9_PLANES) return fail(AZ_ERR_BAD_ARG, "game id %d has no device twin", m->game);   // the one known id DISPATCH_GAME has no case for
+  return dataset_create(m->game, m->device, m->gi, m->stream, out, [&](az_dataset* d) -> int {   // the data set works on the memory's stream
+    int st = AZ_OK;
+    DISPATCH_GAME(m->game, st = dataset_build<Gm>(m, d, which, use_symmetries != 0, use_position_averaging != 0, weighing_policy));
+    return st;
+  });
 }
 // A data set made from the (W, X, A, P, V) tensors of convert_samples (learning.jl:17-51) that a host computed itself: one thread
 // per sample checks what the loss relies on and leaves the sample's terms of Wtot and of Hp = entropy_wmean(P, W) (learning.jl:63,111).
@@ -506,7 +469,7 @@ int dataset_tensor_stats(az_dataset* d, hipStream_t st) {
   HIPCHK(hipGetLastError());
   AZCHK(sample_fault_status(bad, "W <= 0"));
   DevReducer red;                                                    // the reducer of dataset_build: the same tiles and tree for the same n
-  AZCHK(red.init(n, st));
+  AZCHK(red.init(n));
   double sw, shp;
   AZCHK(red.sum(tw, n, st, &sw)); AZCHK(red.sum(thp, n, st, &shp));
   d->Wtot = sw;
@@ -523,26 +486,19 @@ extern "C" int az_dataset_create_from_tensors(int32_t game, int32_t device, int6
   if (n < 1 || n > (1LL << 31) - 1) return fail(AZ_ERR_BAD_ARG, "n must be in 1..2^31-1");
   if (!W || !X || !A || !P || !V) return fail(AZ_ERR_BAD_ARG, "NULL tensor");
   AZCHK(use_device(device));
-  az_dataset* d = nullptr;
-  AZCHK(dataset_new(game, device, gi, nullptr, &d));
-  d->n = n; d->sum_n = n;
-  int rc = [&]() -> int {
+  return dataset_create(game, device, gi, nullptr, out, [&](az_dataset* d) -> int {
+    d->n = n; d->sum_n = n;
     HIPCHK(hipStreamCreate(&d->stream));
     hipStream_t st = d->stream;
     const size_t xs = (size_t)gi.C * gi.P, nA = (size_t)gi.A, N = (size_t)n;
-    AZCHK(mem_alloc(&d->allocs, &d->d_W, N)); AZCHK(mem_alloc(&d->allocs, &d->d_V, N));
-    AZCHK(mem_alloc(&d->allocs, &d->d_A, N * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_P, N * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_X, N * xs));
+    AZCHK(dataset_alloc_tensors(d, n));
     HIPCHK(hipMemcpyAsync(d->d_W, W, sizeof(float) * N, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d->d_V, V, sizeof(float) * N, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d->d_A, A, sizeof(float) * N * nA, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d->d_P, P, sizeof(float) * N * nA, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d->d_X, X, sizeof(float) * N * xs, hipMemcpyHostToDevice, st));
-    AZCHK(dataset_tensor_stats(d, st));
-    return AZ_OK;
-  }();
-  if (rc != AZ_OK) { az_dataset_destroy(d); return rc; }
-  *out = d;
-  return AZ_OK;
+    return dataset_tensor_stats(d, st);
+  });
 }
 extern "C" int az_dataset_get_info(az_dataset* d, az_dataset_info* out) {
   if (!d || !out) return fail(AZ_ERR_BAD_ARG, "NULL argument");

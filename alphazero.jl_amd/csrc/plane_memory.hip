@@ -226,7 +226,7 @@ extern "C" int az_plane_memory_create(int32_t game, int32_t device, int64_t capa
   AZCHK(use_device(device));
   az_plane_memory* m = new (std::nothrow) az_plane_memory();
   if (!m) return fail(AZ_ERR_HIP, "out of host memory");
-  m->game = game; m->device = device; m->gi = gi; m->cap = capacity;
+  m->game = game; m->device = device; m->gi = gi; m->ring.cap = capacity;
   m->xs = gi.C * gi.P; m->nA = gi.A; m->RW = m->xs + m->nA; m->ND = m->nA + 2;
   int st = [&]() -> int {
     HIPCHK(hipStreamCreate(&m->stream));
@@ -253,13 +253,12 @@ extern "C" int az_plane_memory_destroy(az_plane_memory* m) {
 }
 extern "C" int az_plane_memory_length(az_plane_memory* m, int64_t* length, int64_t* cur_batch_size) {
   PLANE_MEMORY(m);
-  const int64_t len = std::min<int64_t>(m->total, m->cap);
-  if (length) *length = len;
-  if (cur_batch_size) *cur_batch_size = std::min<int64_t>(m->cur_batch, len);     // memory.jl:53
+  if (length) *length = m->ring.len();
+  if (cur_batch_size) *cur_batch_size = m->ring.batch();
   return AZ_OK;
 }
-extern "C" int az_plane_memory_new_batch(az_plane_memory* m) { PLANE_MEMORY(m); m->cur_batch = 0; return AZ_OK; }
-extern "C" int az_plane_memory_empty(az_plane_memory* m) { PLANE_MEMORY(m); m->total = 0; m->cur_batch = 0; return AZ_OK; }
+extern "C" int az_plane_memory_new_batch(az_plane_memory* m) { PLANE_MEMORY(m); m->ring.new_batch(); return AZ_OK; }
+extern "C" int az_plane_memory_empty(az_plane_memory* m) { PLANE_MEMORY(m); m->ring.empty(); return AZ_OK; }
 extern "C" int az_debug_plane_memory_hash_bits(az_plane_memory* m, int32_t bits) {
   PLANE_MEMORY(m);
   if (bits < 1 || bits > 128) return fail(AZ_ERR_BAD_ARG, "hash bits must be in 1..128");
@@ -302,9 +301,10 @@ extern "C" int az_plane_memory_num_symmetries(az_plane_memory* m, int32_t* nsym)
   return AZ_OK;
 }
 
-// stage n host samples, check them, store them (reverse: the last staged sample is pushed first).  Nothing is pushed on failure.
+// stage n host samples, check them -- ALL n, those an over-capacity push then skips included -- and store them (reverse: the last
+// staged sample is pushed first; advance_batch: push_trace!).  Nothing is pushed on failure.
 static int plane_push(az_plane_memory* m, int64_t n, const float* X, const float* A, const double* P, const double* z, const double* t,
-                      const int64_t* nvis, bool reverse) {
+                      const int64_t* nvis, bool reverse, bool advance_batch) {
   const size_t N = (size_t)n, xs = (size_t)m->xs, nA = (size_t)m->nA;
   hipStream_t st = m->stream;
   Scratch tmp;
@@ -325,12 +325,12 @@ static int plane_push(az_plane_memory* m, int64_t n, const float* X, const float
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
   AZCHK(sample_fault_status(bad, "n < 1"));
-  const long long skip = std::max<long long>(0, n - m->cap);
+  const long long skip = m->ring.skip(n);
   hipLaunchKernelGGL(k_pm_store, dim3(pm_grid(n - skip)), dim3(64 * PM_WAVES), 0, st, sX, sA, sP, sz, stt, sn, (long long)n, skip, reverse ? 1 : 0,
-                     m->xs, m->nA, (long long)m->total, (long long)m->cap, m->d_XA, m->d_D, m->d_n);
+                     m->xs, m->nA, (long long)m->ring.total, (long long)m->ring.cap, m->d_XA, m->d_D, m->d_n);
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
-  m->total += n;
+  m->ring.pushed(n, advance_batch);
   return AZ_OK;
 }
 extern "C" int az_plane_memory_push_samples(az_plane_memory* m, int64_t n, const float* X, const float* A, const double* P, const double* z,
@@ -339,7 +339,7 @@ extern "C" int az_plane_memory_push_samples(az_plane_memory* m, int64_t n, const
   if (n < 0 || n > (1LL << 31) - 1) return fail(AZ_ERR_BAD_ARG, "n must be in 0..2^31-1");
   if (!n) return AZ_OK;
   if (!X || !A || !P || !z || !t) return fail(AZ_ERR_BAD_ARG, "NULL array");
-  return plane_push(m, n, X, A, P, z, t, nvis, false);               // cur_batch_size is push_trace!'s to advance
+  return plane_push(m, n, X, A, P, z, t, nvis, false, false);
 }
 extern "C" int az_plane_memory_push_trace(az_plane_memory* m, int32_t len, const float* X, const float* A, const double* P, const double* rewards,
                                           const uint8_t* white_playing, double gamma) {
@@ -356,27 +356,25 @@ extern "C" int az_plane_memory_push_trace(az_plane_memory* m, int32_t len, const
     z[i] = white_playing[i] ? wr : -wr;
     t[i] = (double)(len - i);
   }
-  AZCHK(plane_push(m, len, X, A, P, z.data(), t.data(), nullptr, true));
-  m->cur_batch += len;                                               // mem.cur_batch_size += n, memory.jl:86
-  return AZ_OK;
+  return plane_push(m, len, X, A, P, z.data(), t.data(), nullptr, true, true);
 }
 
-// samples [first, first + count) of the buffer, oldest first, back to the host: at most two contiguous runs of the ring
+// samples [first, first + count) of the buffer, oldest first, back to the host
 extern "C" int az_plane_memory_read(az_plane_memory* m, int64_t first, int64_t count, float* X, float* A, double* P, double* z, double* t, int64_t* nvis) {
   PLANE_MEMORY(m);
-  const int64_t len = std::min<int64_t>(m->total, m->cap);
+  const int64_t len = m->ring.len();
   if (first < 0 || count < 0 || first + count > len) return fail(AZ_ERR_BAD_ARG, "range [%lld, %lld) outside the %lld samples", (long long)first, (long long)(first + count), (long long)len);
   if (!count) return AZ_OK;
   const size_t xs = (size_t)m->xs, nA = (size_t)m->nA, RW = (size_t)m->RW, ND = (size_t)m->ND;
   std::vector<float> xa((size_t)count * RW);
   std::vector<double> dd((size_t)count * ND);
-  int64_t seq = m->total - len + first, left = count, done = 0;
-  while (left > 0) {
-    const int64_t pos = seq % m->cap, run = std::min<int64_t>(left, m->cap - pos);
-    HIPCHK(hipMemcpyAsync(xa.data() + (size_t)done * RW, m->d_XA + (size_t)pos * RW, sizeof(float) * (size_t)run * RW, hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(hipMemcpyAsync(dd.data() + (size_t)done * ND, m->d_D + (size_t)pos * ND, sizeof(double) * (size_t)run * ND, hipMemcpyDeviceToHost, m->stream));
-    if (nvis) HIPCHK(hipMemcpyAsync(nvis + done, m->d_n + pos, sizeof(int64_t) * (size_t)run, hipMemcpyDeviceToHost, m->stream));
-    seq += run; left -= run; done += run;
+  int64_t done = 0;
+  for (const Ring::Run& r : m->ring.runs(m->ring.select(0).seq0 + first, count)) {
+    const size_t pos = (size_t)r.pos, run = (size_t)r.run;
+    HIPCHK(hipMemcpyAsync(xa.data() + (size_t)done * RW, m->d_XA + pos * RW, sizeof(float) * run * RW, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipMemcpyAsync(dd.data() + (size_t)done * ND, m->d_D + pos * ND, sizeof(double) * run * ND, hipMemcpyDeviceToHost, m->stream));
+    if (nvis) HIPCHK(hipMemcpyAsync(nvis + done, m->d_n + pos, sizeof(int64_t) * run, hipMemcpyDeviceToHost, m->stream));
+    done += r.run;
   }
   HIPCHK(hipStreamSynchronize(m->stream));
   for (size_t i = 0; i < (size_t)count; ++i) {
@@ -391,36 +389,35 @@ extern "C" int az_plane_memory_read(az_plane_memory* m, int64_t first, int64_t c
 
 // nsym = 0: the selected samples alone; otherwise [samples ; images] over the declared symmetries (virtual rows, see PmView)
 static int plane_dataset_build(az_plane_memory* m, az_dataset* d, int which, int nsym, bool merge, int policy) {
-  const int64_t len = std::min<int64_t>(m->total, m->cap);
-  const int64_t n0 = which == 1 ? std::min<int64_t>(m->cur_batch, len) : len;
+  const Ring::Selection sel = m->ring.select(which);
+  const int64_t n0 = sel.n0;
   if (n0 < 1) return fail(AZ_ERR_STATE, which == 1 ? "the current batch is empty (push_trace advances it, new_batch resets it)" : "the plane memory is empty");
-  const long long seq0 = m->total - n0;                              // the newest n0 samples, oldest first
   const int64_t n1 = n0 * (1 + nsym);                                // rows of the build; the sort's indices are 32-bit
   if (n1 > (1LL << 31) - 1) return fail(AZ_ERR_BAD_ARG, "%lld samples with %d symmetries are %lld rows: more than 2^31-1", (long long)n0, nsym, (long long)n1);
   const bool sym = nsym > 0;
-  const PmView view{m->d_XA, (long long)m->cap, seq0, (long long)n0, m->RW, nsym, m->d_perm};
+  const PmView view{m->d_XA, (long long)m->ring.cap, (long long)sel.seq0, (long long)n0, m->RW, nsym, m->d_perm};
   const int xs = m->xs, nA = m->nA;
   Scratch tmp;
-  HIPCHK(hipStreamSynchronize(m->stream));
+  HIPCHK(hipStreamSynchronize(m->stream));                           // the memory's pushes are done; the data set works on a stream of its own
   HIPCHK(hipStreamCreate(&d->stream));
   hipStream_t st = d->stream;
   unsigned int *order = nullptr, *gord = nullptr, *gpos = nullptr;
   int64_t n2 = n1;
   if (merge) {
-    unsigned long long *k0, *k1, *k1keep, *ks, *ks2, *gkey, *gks; unsigned int *i0, *i1, *i2, *gval; int *head, *seg, *stmp, *coll;
-    const size_t N = (size_t)n1;
-    AZCHK(tmp.alloc(&k0, N)); AZCHK(tmp.alloc(&k1, N)); AZCHK(tmp.alloc(&k1keep, N)); AZCHK(tmp.alloc(&ks, N)); AZCHK(tmp.alloc(&ks2, N));
-    AZCHK(tmp.alloc(&i0, N)); AZCHK(tmp.alloc(&i1, N)); AZCHK(tmp.alloc(&i2, N));
-    AZCHK(tmp.alloc(&head, N)); AZCHK(tmp.alloc(&seg, N)); AZCHK(tmp.alloc(&coll, 1));
-    AZCHK(tmp.alloc(&stmp, std::max(prims::sort_tmp_ints(n1), prims::scan_tmp_ints(n1))));
-    const unsigned gb = (unsigned)((n1 + 255) / 256);
+    unsigned long long *k1keep, *gkey, *gks; unsigned int* gval; int* coll;   // k1keep: the sort destroys its copy of the key's second half
+    AZCHK(tmp.alloc(&k1keep, (size_t)n1)); AZCHK(tmp.alloc(&coll, 1));
     HIPCHK(hipMemsetAsync(coll, 0, sizeof(int), st));
-    hipLaunchKernelGGL(sym ? k_pm_hash<true> : k_pm_hash<false>, dim3(pm_grid(n1)), dim3(64 * PM_WAVES), 0, st, view, (long long)n1, m->hash_bits, k0, k1, k1keep, i0);
-    HIPCHK(prims::order_by_key(k0, k1, i0, ks, ks2, i1, i2, n1, stmp, st));   // i2: ascending (k0, k1, buffer index), as dataset_build (memory.hip)
-    hipLaunchKernelGGL(sym ? k_pm_heads<true> : k_pm_heads<false>, dim3(pm_grid(n1)), dim3(64 * PM_WAVES), 0, st, view, (long long)n1, k0, k1keep, i2, head, coll);
-    HIPCHK(prims::scan_ints(head, seg, n1, true, stmp, st));
+    Grouping g;
+    AZCHK(group_by_key(tmp, n1, st,
+                       [&](unsigned long long* k0, unsigned long long* k1, unsigned int* idx) {
+                         hipLaunchKernelGGL(sym ? k_pm_hash<true> : k_pm_hash<false>, dim3(pm_grid(n1)), dim3(64 * PM_WAVES), 0, st, view, (long long)n1, m->hash_bits, k0, k1, k1keep, idx);
+                       },
+                       [&](const unsigned long long* k0, const unsigned int* order, int* head) {
+                         hipLaunchKernelGGL(sym ? k_pm_heads<true> : k_pm_heads<false>, dim3(pm_grid(n1)), dim3(64 * PM_WAVES), 0, st, view, (long long)n1, k0, k1keep, order, head, coll);
+                       },
+                       &g));
     int nseg = 0, collision = 0;
-    HIPCHK(hipMemcpyAsync(&nseg, seg + (n1 - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&nseg, g.seg + (n1 - 1), sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&collision, coll, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
@@ -428,22 +425,19 @@ static int plane_dataset_build(az_plane_memory* m, az_dataset* d, int which, int
     n2 = nseg;
     const size_t G = (size_t)n2;
     AZCHK(tmp.alloc(&gkey, G)); AZCHK(tmp.alloc(&gks, G)); AZCHK(tmp.alloc(&gval, G)); AZCHK(tmp.alloc(&gord, G)); AZCHK(tmp.alloc(&gpos, G));
-    hipLaunchKernelGGL(k_pm_groups, dim3(gb), dim3(256), 0, st, head, seg, i2, (long long)n1, gkey, gval, gpos);
-    HIPCHK(prims::sort_pairs(gkey, gks, gval, gord, n2, stmp, st));   // n2 <= n1: stmp is large enough
-    order = i2;
+    hipLaunchKernelGGL(k_pm_groups, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, st, g.head, g.seg, g.order, (long long)n1, gkey, gval, gpos);
+    HIPCHK(prims::sort_pairs(gkey, gks, gval, gord, n2, g.stmp, st));   // n2 <= n1: stmp is large enough
+    order = g.order;
   }
   d->n = n2;
-  const size_t G = (size_t)n2;
-  AZCHK(mem_alloc(&d->allocs, &d->d_W, G)); AZCHK(mem_alloc(&d->allocs, &d->d_V, G));
-  AZCHK(mem_alloc(&d->allocs, &d->d_A, G * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_P, G * nA)); AZCHK(mem_alloc(&d->allocs, &d->d_X, G * xs));
-  long long *tn, *tsum;
-  AZCHK(tmp.alloc(&tn, G)); AZCHK(tmp.alloc(&tsum, prims::sum_tmp_doubles(n2)));
+  AZCHK(dataset_alloc_tensors(d, n2));
+  long long* tn;
+  DevReducer red;
+  AZCHK(tmp.alloc(&tn, (size_t)n2)); AZCHK(red.init(n2));
   hipLaunchKernelGGL(sym ? k_pm_merge<true> : k_pm_merge<false>, dim3(pm_grid(n2)), dim3(64 * PM_WAVES), 0, st, view, m->d_D, m->d_n, (long long)n1, (long long)n2,
                      xs, nA, policy, order, gord, gpos, d->d_W, d->d_X, d->d_A, d->d_P, d->d_V, tn);
-  long long* d_sn = nullptr; long long sn = 0;
-  HIPCHK(prims::sum_values<long long>(tn, n2, tsum, &d_sn, st));    // sum(e.n) is an Int: exact
-  HIPCHK(hipMemcpyAsync(&sn, d_sn, sizeof sn, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  long long sn = 0;
+  AZCHK(red.sum(tn, n2, st, &sn));
   HIPCHK(hipGetLastError());
   d->sum_n = (int64_t)sn;
   AZCHK(dataset_tensor_stats(d, st));                              // Wtot, Wmean, Hp as az_dataset_create_from_tensors computes them
@@ -454,15 +448,11 @@ extern "C" int az_dataset_create_from_plane_memory_sym(az_plane_memory* m, int32
   PLANE_MEMORY(m);
   if (!out) return fail(AZ_ERR_BAD_ARG, "NULL argument");
   *out = nullptr;
-  if (which != 0 && which != 1) return fail(AZ_ERR_BAD_ARG, "which must be 0 (get_experience) or 1 (last_batch)");
-  if (weighing_policy < AZ_WEIGHT_CONSTANT || weighing_policy > AZ_WEIGHT_LINEAR) return fail(AZ_ERR_BAD_ARG, "unknown samples_weighing_policy %d", weighing_policy);
+  AZCHK(dataset_check_args(which, weighing_policy));
   if (use_symmetries && m->nsym == 0) return fail(AZ_ERR_BAD_ARG, "use_symmetries: no symmetries were declared for this memory (game.jl:332; az_plane_memory_set_symmetries)");
-  az_dataset* d = nullptr;
-  AZCHK(dataset_new(m->game, m->device, m->gi, nullptr, &d));
-  const int st = plane_dataset_build(m, d, which, use_symmetries ? m->nsym : 0, use_position_averaging != 0, weighing_policy);
-  if (st != AZ_OK) { az_dataset_destroy(d); return st; }
-  *out = d;
-  return AZ_OK;
+  return dataset_create(m->game, m->device, m->gi, nullptr, out, [&](az_dataset* d) -> int {
+    return plane_dataset_build(m, d, which, use_symmetries ? m->nsym : 0, use_position_averaging != 0, weighing_policy);
+  });
 }
 extern "C" int az_dataset_create_from_plane_memory(az_plane_memory* m, int32_t which, int32_t use_position_averaging, int32_t weighing_policy,
                                                    az_dataset** out) {

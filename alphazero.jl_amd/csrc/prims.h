@@ -4,10 +4,13 @@
 // by-state grouping, shared with plane_memory.hip.  Round 2 took them from hipCUB, the last third-party device code in the
 // library.  Off the hot path (a data set is built once per learning step), so the design goal is small and obviously
 // stable / deterministic rather than fastest: 8-bit digits, one workgroup per tile of 2048 pairs, and a per-tile local
-// split so that equal digits keep their order.
+// split so that equal digits keep their order.  At the end: the grouping frame of both data-set builds (group_by_key) and the
+// sum-and-fetch they share (DevReducer), host code over the primitives and engine.h's Scratch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "engine.h"
 
 namespace prims {
 static constexpr int RS_THREADS = 256, RS_ITEMS = 8, RS_TILE = RS_THREADS * RS_ITEMS, RS_BINS = 256;
@@ -227,3 +230,41 @@ inline hipError_t sum_doubles(const double* in, long long n, double* tmp, double
   return sum_values<double>(in, n, tmp, d_result, st);
 }
 }  // namespace prims
+
+// ---- the two frames the data-set builders put around the primitives (engine.h: Scratch, HIPCHK / AZCHK) ------------------------------
+// The frame of merge_by_state.  keys(k0, k1, idx) launches the caller's kernel that writes the 128-bit key of every row and idx = 0 ..
+// n-1; heads(k0, order, head) its kernel that sets head[i] = 1 where position i of the order starts a group (k0 is still what `keys`
+// wrote, k1 is not).  Between and behind them: order_by_key and the inclusive scan of head, so seg[i] = 1-based number of the group
+// position i belongs to and seg[n - 1] the number of groups.  Everything is only ENQUEUED on st; the caller fetches what it needs
+// behind one synchronisation of its own.  The arrays are `tmp`'s: they live exactly as long as the caller's Scratch.  stmp is what the
+// sorts and the scan worked in, free again when they are done: sort_tmp_ints(n) ints, enough for any sort of up to n pairs.
+struct Grouping { unsigned int* order; int *head, *seg, *stmp; };
+template <class Keys, class Heads>
+inline int group_by_key(Scratch& tmp, long long n, hipStream_t st, Keys keys, Heads heads, Grouping* out) {
+  unsigned long long *k0, *k1, *ks, *ks2; unsigned int *i0, *i1, *order; int *head, *seg, *stmp;
+  const size_t N = (size_t)n;
+  AZCHK(tmp.alloc(&k0, N)); AZCHK(tmp.alloc(&k1, N)); AZCHK(tmp.alloc(&ks, N)); AZCHK(tmp.alloc(&ks2, N));
+  AZCHK(tmp.alloc(&i0, N)); AZCHK(tmp.alloc(&i1, N)); AZCHK(tmp.alloc(&order, N));
+  AZCHK(tmp.alloc(&head, N)); AZCHK(tmp.alloc(&seg, N));
+  AZCHK(tmp.alloc(&stmp, std::max(prims::sort_tmp_ints(n), prims::scan_tmp_ints(n))));
+  keys(k0, k1, i0);
+  HIPCHK(prims::order_by_key(k0, k1, i0, ks, ks2, i1, order, n, stmp, st));   // order: ascending (k0, k1, buffer index)
+  heads((const unsigned long long*)k0, (const unsigned int*)order, head);
+  HIPCHK(prims::scan_ints(head, seg, n, true, stmp, st));
+  *out = Grouping{order, head, seg, stmp};
+  return AZ_OK;
+}
+// deterministic sum of n <= nmax values and its fetch: one synchronisation of st per sum
+struct DevReducer {
+  Scratch mem;
+  double* tmp = nullptr;
+  int init(long long nmax) { return mem.alloc(&tmp, prims::sum_tmp_doubles(nmax)); }
+  // T = double, or long long: sum(e.n) is an Int, exact whatever its size.  (A template, so a unit gets the kernels of the types it sums only.)
+  template <class T> int sum(const T* d_in, long long n, hipStream_t st, T* out) {
+    T* d_res = nullptr;
+    HIPCHK(prims::sum_values<T>(d_in, n, (T*)tmp, &d_res, st));
+    HIPCHK(hipMemcpyAsync(out, d_res, sizeof(T), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return AZ_OK;
+  }
+};
