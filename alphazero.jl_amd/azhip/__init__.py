@@ -10,7 +10,7 @@ from ._lib import (AzError, GAME_CONNECT_FOUR, GAME_GO9_PLANES, GAME_MANCALA, GA
 from .engine import Engine, cached_engine, clear_engine_cache, default_cfg
 from .comm import Comm
 from .params import ArenaParams, ConstSchedule, MctsParams, PLSchedule, SimParams
-from .game import ConnectFourSpec, GameEnv, GameSpec, Go9PlanesSpec, MancalaSpec, TicTacToeSpec, plane_symmetries
+from .game import ConnectFourSpec, GameEnv, GameSpec, Go9PlanesSpec, GridWorldRules, MancalaSpec, TicTacToeSpec, plane_symmetries
 from .network import ResNet, ResNetHP, SimpleNet, SimpleNetHP
 from . import mcts as MCTS
 from . import minmax as MinMax

@@ -117,11 +117,12 @@ class SolverCfg(C.Structure):
 
 HOST_TREE_MAX_ACTIONS = 128                 # AZ_HOST_TREE_MAX_ACTIONS
 HT_PLAY, HT_ROOT, HT_FULL, HT_DEPTH = 0, 1, 2, 3   # az_host_tree_request_kind
+HOST_TREE_CHANCE = 1                        # AZ_HOST_TREE_CHANCE (az_host_tree_cfg.flags)
 
 
 class HostTreeCfg(C.Structure):
     """az_host_tree_cfg: the MctsParams the device trees of a host-stepped game use"""
-    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("gamma", C.c_double), ("cpuct", C.c_double),
+    _fields_ = [("struct_size", C.c_int32), ("flags", C.c_int32), ("gamma", C.c_double), ("cpuct", C.c_double),
                 ("dirichlet_noise_eps", C.c_double), ("dirichlet_noise_alpha", C.c_double), ("prior_temperature", C.c_double),
                 ("seed", C.c_uint64)]
 
@@ -260,6 +261,7 @@ SYMBOLS = {
     "az_host_tree_advance": [_VP, _I32, _VP, _VP],
     "az_host_tree_reset": [_VP, _I32, _VP],
     "az_host_tree_get_stats": [_VP, C.POINTER(HostTreeStats)],
+    "az_host_tree_request_depths": [_VP, _VP, _I32, C.POINTER(_I32)],
 }
 
 # az_struct_id order of include/azhip.h

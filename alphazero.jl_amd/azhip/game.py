@@ -88,6 +88,74 @@ class Go9PlanesSpec(GameSpec):
         raise NotImplementedError("Go9PlanesSpec carries the network geometry only: the host encodes its own states")
 
 
+class GridWorldRules:
+    """games/grid-world/game.jl on the host, as the rules object HostSteppedEnv drives over chance trees (HostTree(chance=True)): a
+    one-player MDP whose play is random.  A state is (x, y, time), 1-based like the reference; the key is built from (x, y) only,
+    as the reference's state is -- time is the env's, which is why the host keeps an env per simulation.  The four actions
+    r, l, u, d (game.jl:37) are always available and sit on the action indices 0..3 of whatever width is asked for.
+
+    size (w, h); rewards {(x, y): reward}, every such cell terminal (default: the reference's four cells, which a 9 x 9 world holds
+    too); slip: the probability that a move goes in a uniformly drawn direction instead (game.jl:45); the episode ends when
+    time > episode_length_bound; rng: the numpy Generator play draws from -- the rules own it.  gspec: the network geometry planes
+    and mask are written for (default: one plane of the world's size, four actions)."""
+    MOVES = ((1, 0), (-1, 0), (0, 1), (0, -1))
+    REWARDS = {(9, 3): 10.0, (8, 8): 3.0, (4, 3): -10.0, (4, 6): -5.0}
+    KEY_TAG = 0x67726964776f726c                                      # "gridworl": the second key word
+
+    def __init__(self, size=(10, 10), rewards=None, slip=0.4, episode_length_bound=200, rng=None, gspec=None):
+        self.size = (int(size[0]), int(size[1]))
+        self.rewards = dict(self.REWARDS if rewards is None else rewards)
+        self.slip, self.episode_length_bound = float(slip), int(episode_length_bound)
+        self.rng = np.random.default_rng() if rng is None else rng
+        if gspec is None:
+            self.num_actions, self.plane_shape = 4, (1, self.size[1], self.size[0])
+        else:
+            w, h, c = gspec.state_dim()
+            self.num_actions, self.plane_shape = gspec.num_actions(), (c, h, w)
+        if self.num_actions < 4 or self.plane_shape[1] < self.size[1] or self.plane_shape[2] < self.size[0]:
+            raise ValueError("a %d x %d world does not fit the geometry %s with %d actions" % (self.size + (self.plane_shape, self.num_actions)))
+        for (x, y) in self.rewards:
+            if not (1 <= x <= self.size[0] and 1 <= y <= self.size[1]):
+                raise ValueError("reward cell (%d, %d) outside the %d x %d world" % ((x, y) + self.size))
+
+    def init(self):
+        """RL.reset! (game.jl:36): a uniformly drawn cell, time 0"""
+        return (int(self.rng.integers(1, self.size[0] + 1)), int(self.rng.integers(1, self.size[1] + 1)), 0)
+
+    def play(self, state, action):
+        """RL.act! (game.jl:43-51)"""
+        x, y, time = state
+        if not 0 <= action < 4:
+            raise ValueError("action %r outside 0..3" % (action,))
+        if self.rng.random() < self.slip:
+            action = int(self.rng.integers(4))
+        dx, dy = self.MOVES[action]
+        return (min(max(x + dx, 1), self.size[0]), min(max(y + dy, 1), self.size[1]), time + 1)
+
+    def mask(self, state):
+        m = np.zeros(self.num_actions, dtype=bool)
+        m[:4] = True
+        return m
+
+    def key(self, state):
+        return (state[0] | (state[1] << 32), self.KEY_TAG)
+
+    def reward(self, state):
+        return self.rewards.get((state[0], state[1]), 0.0)
+
+    def terminal(self, state):
+        return (state[0], state[1]) in self.rewards or state[2] > self.episode_length_bound
+
+    def white_playing(self, state):
+        return True
+
+    def planes(self, state):
+        """GI.vectorize_state (game.jl:86-90): the one-hot position, in plane 0"""
+        X = np.zeros(self.plane_shape, dtype=np.float32)
+        X[0, state[1] - 1, state[0] - 1] = 1.0
+        return X
+
+
 SPECS = {"connect-four": ConnectFourSpec, "tictactoe": TicTacToeSpec, "mancala": MancalaSpec}
 
 

@@ -2,7 +2,7 @@
 
 HostTree is the thin mirror of az_host_tree_*: W per-worker MCTS trees (MCTS.Env, src/mcts.jl:124-226) in HBM that ask the host
 one question per simulation at most.  HostSteppedEnv drives one for any rules object and keeps the host's share of the tree: the
-game states, by (worker, node id)."""
+game states, by (worker, node id) -- or, over chance trees (AZ_HOST_TREE_CHANCE: play may be random), one simulation env per worker."""
 import ctypes as C
 
 import numpy as np
@@ -30,16 +30,19 @@ def _arr(a, dtype, shape=None):
 
 class HostTree:
     """az_host_tree: engine = an azhip.Engine with the ResNet oracle and its parameters set (new states are evaluated by its network
-    on the device), or None (the caller supplies P and V with every non-terminal reply)."""
+    on the device), or None (the caller supplies P and V with every non-terminal reply).  chance: AZ_HOST_TREE_CHANCE, the trees of a
+    game whose play may give another state each time -- no edge is remembered, every ply of every simulation asks."""
 
     def __init__(self, num_actions, num_workers, nodes_per_worker, edge_slots_per_worker=None, max_depth=256, engine=None, device=0,
-                 gamma=1.0, cpuct=1.0, dirichlet_noise_eps=0.0, dirichlet_noise_alpha=1.0, prior_temperature=1.0, seed=0):
+                 gamma=1.0, cpuct=1.0, dirichlet_noise_eps=0.0, dirichlet_noise_alpha=1.0, prior_temperature=1.0, seed=0, chance=False):
         self._lib = _lib.lib()
         self.h = C.c_void_p()
         cfg = _lib.HostTreeCfg()
         _lib.check(self._lib.az_host_tree_cfg_init(C.byref(cfg)))
         cfg.gamma, cfg.cpuct, cfg.dirichlet_noise_eps, cfg.dirichlet_noise_alpha = gamma, cpuct, dirichlet_noise_eps, dirichlet_noise_alpha
         cfg.prior_temperature, cfg.seed = prior_temperature, seed
+        cfg.flags = _lib.HOST_TREE_CHANCE if chance else 0
+        self.chance = bool(chance)
         if edge_slots_per_worker is None:
             edge_slots_per_worker = nodes_per_worker * num_actions
         self.engine = engine                                          # keeps it alive: the tree launches on its stream
@@ -48,6 +51,7 @@ class HostTree:
                                                  edge_slots_per_worker, max_depth, C.byref(cfg), C.byref(self.h)))
         self._req = np.zeros(num_workers, dtype=REQUEST_DTYPE)
         self._new = np.zeros(num_workers, dtype=np.int32)
+        self._dep = np.zeros(num_workers, dtype=np.int32)
 
     def close(self):
         if self.h:
@@ -81,6 +85,12 @@ class HostTree:
         _lib.check(self._lib.az_host_tree_step(self.h, n, _vp(replies), _vp(X), _vp(A), _vp(P), _vp(V), _vp(self._req), C.byref(nreq), _vp(self._new)))
         return self._req[:nreq.value].copy(), self._new[:n].copy()
 
+    def request_depths(self):
+        """-> the path length at which each PLAY / ROOT request of the last step was asked, in their order (0: the simulation starts)"""
+        n = C.c_int32()
+        _lib.check(self._lib.az_host_tree_request_depths(self.h, _vp(self._dep), len(self._dep), C.byref(n)))
+        return self._dep[:n.value].copy()
+
     def root_stats(self, workers):
         """-> N [n][nA] int32, W float64, P float32 by full action index, Vest [n], root_node [n]"""
         w = _arr(workers, np.int32)
@@ -111,11 +121,18 @@ class HostSteppedEnv:
     rules: play(state, action) -> state, mask(state) -> availability by action, key(state) -> (k0, k1), reward(state) -> white's
     reward on reaching the state, terminal(state), white_playing(state), and planes(state) -> the network's input (engine mode).
     oracle(state) -> (P by full action index, V): host-oracle mode only.  The host keeps what the device cannot: the states, by
-    (worker, node id), and answers the tree's requests from them."""
+    (worker, node id), and answers the tree's requests from them.
+
+    Over chance trees (tree.chance) rules.play(state, action) may be random -- the rules own their generator -- and a state may carry
+    more than its key tells (grid-world's time), so a node id does not name one.  The host then keeps one simulation env per worker:
+    a request at depth 0 (tree.request_depths) starts from roots[w], any other goes on from where the last reply left the worker;
+    request.node is only checked against that env's key.  advance plays the real move with the rules, the tree forgets its root."""
 
     def __init__(self, rules, tree, oracle=None):
         self.rules, self.tree, self.oracle = rules, tree, oracle
-        self.states = {}          # worker -> {node id: state}
+        self.chance = bool(getattr(tree, "chance", False))
+        self.states = {}          # worker -> {node id: state}; chance: {node id: key}
+        self.sims = {}            # chance: worker -> the env of its simulation in progress
         self.roots = {}           # worker -> the state its explore starts from
         self.stopped = {}         # worker -> FULL / DEPTH of its last explore
 
@@ -148,12 +165,16 @@ class HostSteppedEnv:
         reqs, _ = self.tree.step()
         while True:
             rows, asked = [], []
+            depths = iter(self.tree.request_depths()) if self.chance else None
             for q in reqs:
                 w, kind = int(q["worker"]), int(q["kind"])
                 if kind in (FULL, DEPTH):
                     self.stopped[w] = kind
                     continue
-                state = self.roots[w] if kind == ROOT else self.rules.play(self.states[w][int(q["node"])], int(q["action"]))
+                if self.chance:
+                    state = self._chance_reply(w, kind, int(q["node"]), int(q["action"]), int(next(depths)))
+                else:
+                    state = self.roots[w] if kind == ROOT else self.rules.play(self.states[w][int(q["node"])], int(q["action"]))
                 self._describe(state, rows)
                 asked.append((w, state))
             if not asked:
@@ -168,7 +189,19 @@ class HostSteppedEnv:
                 reqs, new = self.tree.step(replies, X, A)
             for (w, state), node in zip(asked, new):
                 if node >= 0:
-                    self.states[w].setdefault(int(node), state)
+                    self.states[w].setdefault(int(node), tuple(map(int, self.rules.key(state))) if self.chance else state)
+
+    def _chance_reply(self, w, kind, node, action, depth):
+        """the state worker w's simulation reaches: its env is a copy of the root at depth 0 and plays on from there"""
+        if kind == ROOT:
+            state = self.roots[w]
+        else:
+            cur = self.roots[w] if depth == 0 else self.sims[w]
+            if self.states[w].get(node) != tuple(map(int, self.rules.key(cur))):
+                raise RuntimeError("worker %d: the tree asks about node %d, whose key is not that of the state its simulation stands in" % (w, node))
+            state = self.rules.play(cur, action)
+        self.sims[w] = state
+        return state
 
     def policy(self, workers):
         """MCTS.policy (mcts.jl:255-271): per worker (available actions, pi = N / sum N)"""

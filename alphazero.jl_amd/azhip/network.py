@@ -227,6 +227,10 @@ class ResNet:
                     num_policy_head_filters=h.num_policy_head_filters,
                     num_value_head_filters=h.num_value_head_filters, net_bf16=1 if self.bf16 else 0)
 
+    def engine(self):
+        """the engine that evaluates this network (created on first use, its parameters set): what HostTree(engine=...) takes"""
+        return self._eng()
+
     def _eng(self):
         if self._engine is None:
             self._engine = Engine(game=self.gspec.game_id, oracle=self.ORACLE, device=self.device,

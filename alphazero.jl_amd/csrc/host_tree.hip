@@ -7,6 +7,8 @@
 //   edges  [W][EPW]   bump-allocated runs of n slots by RANK: P f32, W f64, N i32, action, child, r f64, flags (known / terminal / pswitch)
 //   table  [W][HS]    open addressing on az_hash_key(key), entries = node ids, HS = a power of two >= max(64, 2 NPW): never full
 //   path   [W][max_depth]  edge slots of the simulation in progress;  eta [W][128] the root's noise;  ws [W] the worker's state
+//   pr, pps [W][max_depth] chance mode only (AZ_HOST_TREE_CHANCE): the mover's reward and pswitch of every path entry -- there they
+//                          belong to the entry, not to the edge, whose memo (child, r, flags) is never written
 // One wavefront per worker (k_ht_step): lanes run over ranks, two per lane beyond 64, so a select is one coalesced load per array.
 // Everything a wavefront decides is wave-uniform; values that lanes hand to each other through memory are separated by a barrier
 // of the one-wave workgroup.
@@ -30,12 +32,13 @@ struct HTReply { unsigned long long k0, k1; float wr; int row; int terminal; int
 struct HTArm { int worker, nsims; uint32_t game, move; };
 
 struct HTView {
-  int W, nA, NPW, EPW, HS, max_depth;
+  int W, nA, NPW, EPW, HS, max_depth, chance;
   double gamma, cpuct, eps, alpha;
   unsigned long long seed;
   unsigned long long* nkey; int* nbase; int* ncount; float* nvest; unsigned char* nwp;
   float* eP; double* eW; int* eN; short* eact; int* echild; double* er; unsigned char* eflag;
   int* table; int* path; double* eta; HTWorker* ws;
+  double* pr; unsigned char* pps;
 };
 
 __device__ __forceinline__ int wave_sum_i(int v) {
@@ -101,15 +104,37 @@ __device__ __forceinline__ bool ht_create(const HTView& v, int w, HTWorker& s, c
   return true;
 }
 
+// What the reply R says about the move along the path's last entry (edge slot e, out of a node whose mover is white iff wpp): the mover's
+// reward and pswitch, and child = the node it led to or -1 for a terminal state.  Chance mode keeps them with the entry, the
+// deterministic mode remembers them on the edge.
+__device__ __forceinline__ void ht_record(const HTView& v, int w, int plen, int e, bool wpp, const HTReply& R, int child) {
+  const double r = wpp ? (double)R.wr : -(double)R.wr;
+  const bool ps = wpp != (R.wp != 0);
+  if (v.chance) {
+    const size_t i = (size_t)w * v.max_depth + plen - 1;
+    v.pr[i] = r; v.pps[i] = (unsigned char)(ps ? EF_PSWITCH : 0);
+    return;
+  }
+  const size_t i = (size_t)w * v.EPW + e;
+  v.er[i] = r;
+  if (child >= 0) v.echild[i] = child;
+  v.eflag[i] = (unsigned char)(EF_KNOWN | (child < 0 ? EF_TERMINAL : 0) | (ps ? EF_PSWITCH : 0));
+}
+
 // mcts.jl:216-223 over the path, last entry first; q = the leaf's value.  The chain of q runs in every lane (shuffles), lane k
 // updates entry k.  An edge that is on the path twice (a line of play that repeats a state) is updated one entry at a time.
+// r and pswitch are the edge's memo, or in chance mode the path entry's own: the mode selects the two base pointers once per call and
+// the index per lane (path position or edge slot), so either mode does one load of each and the loop has no mode branch.  The selects
+// are not free: DESIGN.md 4e has the deterministic step's time with them and with them compiled out.
 __device__ __forceinline__ void ht_unwind(const HTView& v, int w, int plen, double q, int lane) {
   const int* pp = v.path + (size_t)w * v.max_depth;
   const size_t E = (size_t)w * v.EPW;
+  const double* rsrc = v.chance ? v.pr + (size_t)w * v.max_depth : v.er + E;
+  const unsigned char* fsrc = v.chance ? v.pps + (size_t)w * v.max_depth : v.eflag + E;
   for (int hi = plen; hi > 0; hi -= 64) {
     const int cnt = hi < 64 ? hi : 64;
     int e = -1 - lane; double r = 0.0; int ps = 0;
-    if (lane < cnt) { e = pp[hi - 1 - lane]; r = v.er[E + e]; ps = v.eflag[E + e] & EF_PSWITCH; }
+    if (lane < cnt) { e = pp[hi - 1 - lane]; const int i = v.chance ? hi - 1 - lane : e; r = rsrc[i]; ps = fsrc[i] & EF_PSWITCH; }
     bool dup = false;
     double myq = 0.0;
     for (int k = 0; k < cnt; ++k) {
@@ -143,9 +168,11 @@ __global__ void __launch_bounds__(64) k_ht_arm(HTView v, const HTArm* arms, int 
 }
 
 // One wavefront per active worker: absorb its reply, then unwind / select until it needs the host or its quota is spent.
-// active[j] = {worker, index of its reply or -1}; reqtmp[j] = its request (kind -1: none).
+// active[j] = {worker, index of its reply or -1}; reqtmp[j] = its request (kind -1: none), deptmp[j] = the path length it was asked at.
+// Chance mode: the reply to AZ_HT_PLAY gives the path entry its reward and pswitch (ht_record); no edge is ever marked known, so every
+// select asks and az_host_tree_advance always forgets the root.
 __global__ void __launch_bounds__(64) k_ht_step(HTView v, const int2* active, int nactive, const HTReply* replies, const float* Arows, const float* Prows,
-                                                int pstride, const float* Vrows, az_host_tree_request* reqtmp, int* new_nodes) {
+                                                int pstride, const float* Vrows, az_host_tree_request* reqtmp, int* deptmp, int* new_nodes) {
   const int j = blockIdx.x, lane = threadIdx.x;
   if (j >= nactive) return;
   const int w = active[j].x, ri = active[j].y;
@@ -154,6 +181,7 @@ __global__ void __launch_bounds__(64) k_ht_step(HTView v, const int2* active, in
   const size_t NB = (size_t)w * v.NPW, E = (size_t)w * v.EPW;
   int* pp = v.path + (size_t)w * v.max_depth;
   az_host_tree_request rq = {w, -1, -1, -1};
+  int rdepth = 0;
   bool unwind = false, descending = false, stop = false;
   double q = 0.0;
 
@@ -164,10 +192,7 @@ __global__ void __launch_bounds__(64) k_ht_step(HTView v, const int2* active, in
       if (s.pending == PEND_PLAY && s.plen > 0) {
         const int e = pp[s.plen - 1];
         const bool wpp = v.nwp[NB + s.cur] != 0;
-        if (lane == 0) {
-          v.er[E + e] = wpp ? (double)R.wr : -(double)R.wr;
-          v.eflag[E + e] = (unsigned char)(EF_KNOWN | EF_TERMINAL | ((wpp != (R.wp != 0)) ? EF_PSWITCH : 0));
-        }
+        if (lane == 0) ht_record(v, w, s.plen, e, wpp, R, -1);
         __syncthreads();
         q = 0.0; unwind = true;
       }
@@ -189,11 +214,7 @@ __global__ void __launch_bounds__(64) k_ht_step(HTView v, const int2* active, in
         if (s.pending == PEND_PLAY && s.plen > 0) {
           const int e = pp[s.plen - 1];
           const bool wpp = v.nwp[NB + s.cur] != 0;
-          if (lane == 0) {
-            v.er[E + e] = wpp ? (double)R.wr : -(double)R.wr;
-            v.echild[E + e] = id;
-            v.eflag[E + e] = (unsigned char)(EF_KNOWN | ((wpp != (R.wp != 0)) ? EF_PSWITCH : 0));
-          }
+          if (lane == 0) ht_record(v, w, s.plen, e, wpp, R, id);
           __syncthreads();
         } else {
           s.root = id;
@@ -258,19 +279,20 @@ __global__ void __launch_bounds__(64) k_ht_step(HTView v, const int2* active, in
     s.plen += 1;
     __syncthreads();
     const int fl = v.eflag[E + e];
-    if (!(fl & EF_KNOWN)) {
-      rq.node = s.cur; rq.action = (int)v.eact[E + e]; rq.kind = AZ_HT_PLAY;
+    if (!(fl & EF_KNOWN)) {                                         // chance mode: always, no edge is ever marked known
+      rq.node = s.cur; rq.action = (int)v.eact[E + e]; rq.kind = AZ_HT_PLAY; rdepth = s.plen - 1;
       s.pending = PEND_PLAY; s.touched = 1;
       break;
     }
     if (fl & EF_TERMINAL) { q = 0.0; unwind = true; continue; }
     s.cur = v.echild[E + e];
   }
-  if (lane == 0) { v.ws[w] = s; reqtmp[j] = rq; }
+  if (lane == 0) { v.ws[w] = s; reqtmp[j] = rq; deptmp[j] = rdepth; }
 }
 
-// requests of the active workers, compacted in worker order: out[0] = count, reqs[0 .. count)
-__global__ void __launch_bounds__(256) k_ht_compact(const az_host_tree_request* reqtmp, int nactive, int* count, az_host_tree_request* reqs) {
+// requests of the active workers and their depths, compacted in worker order: out[0] = count, reqs[0 .. count), deps[0 .. count)
+__global__ void __launch_bounds__(256) k_ht_compact(const az_host_tree_request* reqtmp, const int* deptmp, int nactive, int* count, az_host_tree_request* reqs,
+                                                    int* deps) {
   __shared__ int s_wave[4];
   int base = 0;
   for (int t0 = 0; t0 < nactive; t0 += 256) {
@@ -278,7 +300,7 @@ __global__ void __launch_bounds__(256) k_ht_compact(const az_host_tree_request* 
     const bool has = i < nactive && reqtmp[i].kind >= 0;
     int total;
     const int off = prims::block_excl_scan(has ? 1 : 0, s_wave, &total);
-    if (has) reqs[base + off] = reqtmp[i];
+    if (has) { reqs[base + off] = reqtmp[i]; deps[base + off] = deptmp[i]; }
     base += total;
   }
   if (threadIdx.x == 0) *count = base;
@@ -305,6 +327,7 @@ __global__ void __launch_bounds__(64) k_ht_root_stats(HTView v, const int* worke
 }
 
 // apply == 0: res[i] = 1 where the root of workers[i] is known and has no edge `actions[i]`; apply != 0: the root moves along it
+// (chance mode: to "unknown" for every action the root has -- the device cannot know where the real move led)
 __global__ void __launch_bounds__(64) k_ht_advance(HTView v, const int* workers, const int* actions, int n, int apply, int* res) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= n) return;
@@ -318,7 +341,7 @@ __global__ void __launch_bounds__(64) k_ht_advance(HTView v, const int* workers,
     int k = 0;
     while (k < cnt && v.eact[E + k] != actions[i]) ++k;
     if (k == cnt) bad = 1;
-    else if ((v.eflag[E + k] & (EF_KNOWN | EF_TERMINAL)) == EF_KNOWN) next = v.echild[E + k];
+    else if (!v.chance && (v.eflag[E + k] & (EF_KNOWN | EF_TERMINAL)) == EF_KNOWN) next = v.echild[E + k];
   }
   if (!apply) { res[i] = bad; return; }
   if (!bad) { s.root = next; s.cur = next; s.plen = 0; }
@@ -350,8 +373,9 @@ struct az_host_tree {
   char* h_in = nullptr; char* d_in = nullptr; size_t in_bytes = 0;      // pinned / device staging of a step's input, one layout
   char* h_out = nullptr; char* d_out = nullptr; size_t out_bytes = 0;   // count, new_nodes, requests (and the results of the other calls)
   float* h_X = nullptr;                      // engine mode: pinned rows for the engine's d_X
-  az_host_tree_request* d_reqtmp = nullptr;
+  az_host_tree_request* d_reqtmp = nullptr; int* d_deptmp = nullptr;
   std::vector<az_host_tree_request> outstanding;   // AZ_HT_PLAY / AZ_HT_ROOT requests of the last step, in order
+  std::vector<int32_t> depths;                     // the path length each of them was asked at (az_host_tree_request_depths)
   std::vector<uint8_t> armed;
   std::vector<HTArm> arms;                   // az_host_tree_explore since the last step
   long long steps = 0;
@@ -391,11 +415,12 @@ static int ht_create_body(az_host_tree* t) {
   AZCHK(ht_alloc(t, &v.eP, NE)); AZCHK(ht_alloc(t, &v.eW, NE)); AZCHK(ht_alloc(t, &v.eN, NE)); AZCHK(ht_alloc(t, &v.eact, NE)); AZCHK(ht_alloc(t, &v.echild, NE));
   AZCHK(ht_alloc(t, &v.er, NE)); AZCHK(ht_alloc(t, &v.eflag, NE));
   AZCHK(ht_alloc(t, &v.table, W * v.HS)); AZCHK(ht_alloc(t, &v.path, W * v.max_depth)); AZCHK(ht_alloc(t, &v.eta, W * HT_MAXA)); AZCHK(ht_alloc(t, &v.ws, W));
-  AZCHK(ht_alloc(t, &t->d_reqtmp, W));
+  AZCHK(ht_alloc(t, &t->d_reqtmp, W)); AZCHK(ht_alloc(t, &t->d_deptmp, W));
+  if (v.chance) { AZCHK(ht_alloc(t, &v.pr, W * v.max_depth)); AZCHK(ht_alloc(t, &v.pps, W * v.max_depth)); }
   // a step's input: active [W] int2, arms [W], replies [W], V [W], A [W][nA], P [W][nA]; the other calls use the front of it
   t->in_bytes = al16(W * sizeof(int2)) + al16(W * sizeof(HTArm)) + al16(W * sizeof(HTReply)) + al16(W * 4) + 2 * al16(W * v.nA * 4);
-  // a step's output: count (16 bytes), new_nodes [W], requests [W]; root_stats: N, W, P [W][nA], Vest, root [W]
-  t->out_bytes = std::max(16 + al16(W * 4) + al16(W * sizeof(az_host_tree_request)), al16(W * v.nA * 8) + 2 * al16(W * v.nA * 4) + 2 * al16(W * 4));
+  // a step's output: count (16 bytes), new_nodes [W], requests [W], their depths [W]; root_stats: N, W, P [W][nA], Vest, root [W]
+  t->out_bytes = std::max(16 + 2 * al16(W * 4) + al16(W * sizeof(az_host_tree_request)), al16(W * v.nA * 8) + 2 * al16(W * v.nA * 4) + 2 * al16(W * 4));
   AZCHK(ht_alloc(t, &t->d_in, t->in_bytes)); AZCHK(ht_alloc(t, &t->d_out, t->out_bytes));
   HIPCHK(hipHostMalloc((void**)&t->h_in, t->in_bytes, hipHostMallocDefault));
   HIPCHK(hipHostMalloc((void**)&t->h_out, t->out_bytes, hipHostMallocDefault));
@@ -415,6 +440,9 @@ extern "C" int az_host_tree_create(az_engine* e, int32_t device, int32_t num_act
   if (!out) return fail(AZ_ERR_BAD_ARG, "out is NULL");
   *out = nullptr;
   if (!cfg || cfg->struct_size != (int32_t)sizeof(az_host_tree_cfg)) return fail(AZ_ERR_BAD_ARG, "az_host_tree_cfg: NULL or wrong struct_size (use az_host_tree_cfg_init)");
+  if (const unsigned unknown = (unsigned)cfg->flags & ~(unsigned)AZ_HOST_TREE_CHANCE)   // names the lowest bit nobody defined
+    return fail(AZ_ERR_BAD_ARG, "az_host_tree_cfg.flags = 0x%x: bit 0x%x is not defined (AZ_HOST_TREE_CHANCE = 0x%x is the only one)", (unsigned)cfg->flags,
+                unknown & (0u - unknown), (unsigned)AZ_HOST_TREE_CHANCE);
   if (cfg->prior_temperature != 1.0) return fail(AZ_ERR_BAD_ARG, "prior_temperature = %g: only 1 is built for the device trees of a host-stepped game", cfg->prior_temperature);
   if (!std::isfinite(cfg->gamma) || !std::isfinite(cfg->cpuct)) return fail(AZ_ERR_BAD_ARG, "gamma / cpuct must be finite");
   if (!(cfg->dirichlet_noise_eps >= 0.0 && cfg->dirichlet_noise_eps <= 1.0)) return fail(AZ_ERR_BAD_ARG, "dirichlet_noise_eps = %g outside [0, 1]", cfg->dirichlet_noise_eps);
@@ -444,6 +472,7 @@ extern "C" int az_host_tree_create(az_engine* e, int32_t device, int32_t num_act
   HTView& v = t->v;
   v.W = num_workers; v.nA = num_actions; v.NPW = nodes_per_worker; v.EPW = edge_slots_per_worker; v.max_depth = max_depth;
   v.HS = 64; while (v.HS < 2 * (long long)nodes_per_worker) v.HS <<= 1;
+  v.chance = (cfg->flags & AZ_HOST_TREE_CHANCE) != 0;
   v.gamma = cfg->gamma; v.cpuct = cfg->cpuct; v.eps = cfg->dirichlet_noise_eps; v.alpha = cfg->dirichlet_noise_alpha; v.seed = cfg->seed;
   const int st = ht_create_body(t);
   if (st != AZ_OK) { const std::string keep = az_last_error(); az_host_tree_destroy(t); return fail(st, "%s", keep.c_str()); }
@@ -562,12 +591,14 @@ extern "C" int az_host_tree_step(az_host_tree* t, int32_t nreplies, const az_hos
   if (t->prof) HIPCHK(hipEventRecord(t->ev[0], st));
   if (narms) hipLaunchKernelGGL(k_ht_arm, dim3((narms + 63) / 64), dim3(64), 0, st, t->v, (const HTArm*)(t->d_in + o_arms), narms);
   int* d_count = (int*)t->d_out; int* d_nn = (int*)(t->d_out + 16);
-  az_host_tree_request* d_req = (az_host_tree_request*)(t->d_out + 16 + al16((size_t)nreplies * 4));
+  const size_t o_req = 16 + al16((size_t)nreplies * 4), o_dep = o_req + (size_t)nactive * sizeof(az_host_tree_request);
+  az_host_tree_request* d_req = (az_host_tree_request*)(t->d_out + o_req);
   hipLaunchKernelGGL(k_ht_step, dim3(nactive), dim3(64), 0, st, t->v, (const int2*)(t->d_in + o_active), nactive, (const HTReply*)(t->d_in + o_rep), d_A, d_P,
-                     pstride, d_V, t->d_reqtmp, d_nn);
-  hipLaunchKernelGGL(k_ht_compact, dim3(1), dim3(256), 0, st, (const az_host_tree_request*)t->d_reqtmp, nactive, d_count, d_req);
+                     pstride, d_V, t->d_reqtmp, t->d_deptmp, d_nn);
+  hipLaunchKernelGGL(k_ht_compact, dim3(1), dim3(256), 0, st, (const az_host_tree_request*)t->d_reqtmp, (const int*)t->d_deptmp, nactive, d_count, d_req,
+                     (int*)(t->d_out + o_dep));
   if (t->prof) HIPCHK(hipEventRecord(t->ev[1], st));
-  const size_t ob = 16 + al16((size_t)nreplies * 4) + (size_t)nactive * sizeof(az_host_tree_request);
+  const size_t ob = o_dep + (size_t)nactive * sizeof(int);
   HIPCHK(hipMemcpyAsync(t->h_out, t->d_out, ob, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
@@ -576,16 +607,27 @@ extern "C" int az_host_tree_step(az_host_tree* t, int32_t nreplies, const az_hos
   if (t->prof) { float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, t->ev[0], t->ev[1])); t->kernel_ms += ms; t->prof_steps += 1; }
   // ---- the step happened: bookkeeping of who is armed, the outstanding requests
   const int nreq = std::min(std::max(*(int*)t->h_out, 0), nactive);
-  const az_host_tree_request* hr = (const az_host_tree_request*)(t->h_out + 16 + al16((size_t)nreplies * 4));
+  const az_host_tree_request* hr = (const az_host_tree_request*)(t->h_out + o_req);
+  const int32_t* hd = (const int32_t*)(t->h_out + o_dep);
   for (int i = 0; i < nactive; ++i) t->armed[h_active[i].x] = 0;
   t->arms.clear();
-  t->outstanding.clear();
+  t->outstanding.clear(); t->depths.clear();
   for (int i = 0; i < nreq; ++i) {
     requests[i] = hr[i];
-    if (hr[i].kind == AZ_HT_PLAY || hr[i].kind == AZ_HT_ROOT) { t->outstanding.push_back(hr[i]); t->armed[hr[i].worker] = 1; }
+    if (hr[i].kind == AZ_HT_PLAY || hr[i].kind == AZ_HT_ROOT) { t->outstanding.push_back(hr[i]); t->depths.push_back(hd[i]); t->armed[hr[i].worker] = 1; }
   }
   memcpy(new_nodes, t->h_out + 16, sizeof(int32_t) * (size_t)nreplies);
   *nrequests = nreq;
+  return AZ_OK;
+}
+
+extern "C" int az_host_tree_request_depths(az_host_tree* t, int32_t* depths, int32_t cap, int32_t* n) {
+  if (!t) return fail(AZ_ERR_BAD_ARG, "host tree is NULL");
+  if (!n) return fail(AZ_ERR_BAD_ARG, "az_host_tree_request_depths: n is NULL");
+  *n = (int32_t)t->depths.size();
+  if (*n == 0) return AZ_OK;
+  if (!depths || cap < *n) return fail(AZ_ERR_CAPACITY, "az_host_tree_request_depths: %d outstanding requests, room for %d", *n, depths ? cap : 0);
+  memcpy(depths, t->depths.data(), sizeof(int32_t) * (size_t)*n);
   return AZ_OK;
 }
 

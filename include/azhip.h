@@ -648,14 +648,33 @@ int az_dataset_create_from_plane_memory_sym(az_plane_memory* m, int32_t which, i
  *                 requests', a non-finite reward or V, a terminal root, an A row with no legal action or entries outside {0, 1},
  *                 P < 0 or not finite or P > 0 where A == 0 (host-oracle mode), a worker index out of range, az_host_tree_explore
  *                 on an armed worker (or naming one twice), root_stats / advance / reset on an armed worker (AZ_ERR_STATE), an
- *                 advance by an action the root does not have.  The tree is unchanged and the outstanding requests stay outstanding.
- * Not built: prior_temperature != 1 (refused by az_host_tree_create), more than AZ_HOST_TREE_MAX_ACTIONS actions, freeing the
- * subtrees an advance leaves unreachable (the tree is kept, as the reference keeps it between the moves of a game). */
+ *                 advance by an action the root does not have, a bit of az_host_tree_cfg.flags nobody defined (az_host_tree_create
+ *                 names it).  The tree is unchanged and the outstanding requests stay outstanding.
+ *   chance        flags & AZ_HOST_TREE_CHANCE: a game whose play! may give another state every time it is called (a stochastic MDP,
+ *                 games/grid-world), searched as mcts.jl:199-226 searches it: the rules are consulted at every ply of every
+ *                 simulation, the statistics stay per (state, action), and the backup runs along the states actually met.
+ *                 protocol: no edge is ever remembered; every descent through an edge ends the step with AZ_HT_PLAY, one ply per
+ *                 step, request.node = the node of the state the simulation stands in.  reply: the state reached THIS time; the
+ *                 mover's reward (white_playing of the node ? wr : -wr, Float64 of the Float32) and pswitch (the node's white_playing
+ *                 != the reply's) belong to this path entry, not to the edge.  Terminal -> backed up with 0.0; a key the worker's
+ *                 table holds -> the descent goes on from that node in the same step (its evaluation is discarded and counted in
+ *                 transposition_hits); otherwise the node is created and backed up with Float64(Vest).  backup: the same recurrence
+ *                 with the entry's r and pswitch; an edge may stand on one path several times with different rewards, and is then
+ *                 updated one entry at a time, last entry first.  advance: the device cannot know where the real move led, so the
+ *                 root becomes unknown (the action must still be one the root has) and the tree is kept; the next explore asks
+ *                 AZ_HT_ROOT and the reply's key finds the node if the worker has met that state -- the tree is reused as the
+ *                 reference reuses env.tree.  AZ_HT_FULL, AZ_HT_DEPTH, the noise at the root and the refusals are those above;
+ *                 sims_without_host counts only simulations that never asked.  Cost: one host round trip per ply, and every
+ *                 non-terminal reply's row is evaluated although most land on nodes the worker knows.
+ * Not built, in either mode: prior_temperature != 1 (refused by az_host_tree_create), more than AZ_HOST_TREE_MAX_ACTIONS actions,
+ * freeing the subtrees an advance leaves unreachable (the tree is kept, as the reference keeps it between the moves of a game).
+ * Not built in chance mode: outcome lists sampled on the device, skipping the evaluation of a reply that lands on a known node. */
 #define AZ_HOST_TREE_MAX_ACTIONS 128
+#define AZ_HOST_TREE_CHANCE 1   /* az_host_tree_cfg.flags: "chance" above */
 typedef struct az_host_tree az_host_tree;
 typedef struct {
   int32_t struct_size;        /* sizeof(az_host_tree_cfg), set by az_host_tree_cfg_init */
-  int32_t reserved;           /* 0 */
+  int32_t flags;              /* 0, or AZ_HOST_TREE_CHANCE; any other bit is refused */
   double gamma, cpuct, dirichlet_noise_eps, dirichlet_noise_alpha;   /* MctsParams (src/params.jl:49-57) */
   double prior_temperature;   /* must be 1 */
   uint64_t seed;
@@ -678,7 +697,7 @@ typedef struct {
   int64_t max_nodes, max_edge_slots, max_path;   /* high-water marks over the workers (they survive a reset) */
   int64_t steps;                  /* az_host_tree_step calls that launched */
 } az_host_tree_stats;
-int az_host_tree_cfg_init(az_host_tree_cfg* cfg);   /* gamma 1, cpuct 1, eps 0, alpha 1, prior_temperature 1, seed 0 */
+int az_host_tree_cfg_init(az_host_tree_cfg* cfg);   /* flags 0, gamma 1, cpuct 1, eps 0, alpha 1, prior_temperature 1, seed 0 */
 /* num_actions 1..AZ_HOST_TREE_MAX_ACTIONS, num_workers 1..2^20, nodes_per_worker >= 1, edge_slots_per_worker >= num_actions,
  * max_depth >= 1.  Engine mode: num_workers must not exceed what one network launch of the engine takes; the engine must outlive the
  * tree, and the tree uses the engine's stream.  `device` is ignored in engine mode (the engine's is taken). */
@@ -693,10 +712,15 @@ int az_host_tree_explore(az_host_tree* t, int32_t n, const int32_t* workers, con
  * terminal replies are not read.  requests and new_nodes must hold num_workers entries; *nrequests = requests written. */
 int az_host_tree_step(az_host_tree* t, int32_t nreplies, const az_host_tree_reply* replies, const float* X, const float* A, const float* P,
                       const float* V, az_host_tree_request* requests, int32_t* nrequests, int32_t* new_nodes);
+/* The path length at which each outstanding request (AZ_HT_PLAY / AZ_HT_ROOT) of the last step was asked, in the order of the requests:
+ * 0 for AZ_HT_ROOT and for a question about the root's own move ("this simulation starts"), k where k edges were walked before.  It
+ * came with the step's output: no launch, no synchronisation.  *n = their number; AZ_ERR_CAPACITY when cap is below it.  Both modes.
+ * A host whose environment carries more than the state (grid-world's time) needs it: a node id does not name an environment there. */
+int az_host_tree_request_depths(az_host_tree* t, int32_t* depths, int32_t cap, int32_t* n);
 /* tree[root] of n workers by FULL action index (unavailable: 0): N [n][num_actions], W, P, Vest [n], root_node [n] (-1 and zeros
  * where the root is unknown); any pointer may be NULL.  What MCTS.policy (mcts.jl:255-271) and the explorer need. */
 int az_host_tree_root_stats(az_host_tree* t, int32_t n, const int32_t* workers, int32_t* N, double* W, float* P, float* Vest, int32_t* root_node);
-/* The root becomes the child the edge `actions[i]` leads to if that is a known node, else unknown; the tree is kept. */
+/* The root becomes the child the edge `actions[i]` leads to if that is a known node, else unknown (chance mode: always unknown); the tree is kept. */
 int az_host_tree_advance(az_host_tree* t, int32_t n, const int32_t* workers, const int32_t* actions);
 int az_host_tree_reset(az_host_tree* t, int32_t n, const int32_t* workers);   /* MCTS.reset!: the tree is emptied, node ids restart at 0, counters are kept */
 int az_host_tree_get_stats(az_host_tree* t, az_host_tree_stats* stats);

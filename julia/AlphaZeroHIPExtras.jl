@@ -297,6 +297,7 @@ const UNBOUND = Dict(
   :az_host_tree_advance => "see az_host_tree_cfg_init",
   :az_host_tree_reset => "see az_host_tree_cfg_init; MCTS.reset!",
   :az_host_tree_get_stats => "see az_host_tree_cfg_init",
+  :az_host_tree_request_depths => "see az_host_tree_cfg_init; the path length behind each request, for hosts whose environment carries more than the state (games/grid-world's time)",
   :az_simplenet_hp_init => "NetLib.SimpleNet engines (simplenet.jl:15-64): the glue builds ResNet engines only; az_simplenet_hp mirrors SimpleNetHP field by field when a SimpleNet constructor is added here",
   :az_engine_create_simplenet => "see az_simplenet_hp_init; every other entry point takes the engine it returns unchanged",
 )
