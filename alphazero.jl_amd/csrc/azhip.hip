@@ -418,17 +418,18 @@ static int create_eval_cache(az_engine* e) {
   AZCHK(dalloc(e, &v.Pout, (size_t)std::max(G, 1) * gi.APAD)); AZCHK(dalloc(e, &v.Vout, G));
   const bool on = e->env.eval_cache >= 0 ? e->env.eval_cache != 0 && c->oracle != AZ_ORACLE_ROLLOUT : oracle_is_net(*c);
   if (!on || e->env.use_graphs) return AZ_OK;
-  // sized from the workload: 8 x slots x simulations per move entries of 64 bytes, 2^16 (4 MB) ... 2^24 (1 GB: BASELINE
-  // configs[1]; a phase there evaluates 2-6 x 10^7 states) -- an 8-slot test engine and the 128-worker arena players no longer hold
-  // 1 GB each; AZHIP_EVAL_CACHE_LOG2 says otherwise
-  int lg = e->env.eval_cache_log2;
-  if (!lg) for (lg = 16; lg < 24 && ((long long)1 << lg) < 8LL * G * std::max(1, c->num_iters_per_turn);) ++lg;
-  AZCHK(dalloc(e, &e->d_ec, (size_t)1 << lg));                      // zeroed: every entry EC_EMPTY
-  e->ec_mask = ((uint32_t)1 << lg) - 1u;
+  // sized from the workload and the memory that is free now (eval_cache_rule.h ec_size_log2): an 8-slot test engine and the
+  // 128-worker arena players hold a few MB, a self-play engine that runs long phases a table that keeps a phase's answers;
+  // AZHIP_EVAL_CACHE_LOG2 says otherwise
+  size_t free_b = 0, total_b = 0;
+  HIPCHK(hipMemGetInfo(&free_b, &total_b));
+  const int lg = ec_size_log2(G, c->num_iters_per_turn, e->env.eval_cache_log2, (unsigned long long)free_b);
+  e->ec_entries = (size_t)1 << lg;
+  AZCHK(dalloc(e, &e->d_ec, e->ec_entries));                        // zeroed: every entry EC_EMPTY
   AZCHK(dalloc(e, &e->d_ec_claim, (size_t)2 * G, false));
   HIPCHK(hipMemsetAsync(e->d_ec_claim, 0xff, sizeof(int) * 2 * (size_t)G, e->stream));
   AZCHK(dalloc(e, &e->d_Phit, (size_t)G * gi.APAD)); AZCHK(dalloc(e, &e->d_Vhit, G));
-  v.ec = e->d_ec; v.ec_mask = e->ec_mask; v.ec_seq = 0; v.ec_claim = e->d_ec_claim; v.Phit = e->d_Phit; v.Vhit = e->d_Vhit;
+  v.ec = e->d_ec; v.ec_set_mask = (uint32_t)(e->ec_entries / EC_WAYS) - 1u; v.ec_seq = 0; v.ec_claim = e->d_ec_claim; v.Phit = e->d_Phit; v.Vhit = e->d_Vhit;
   return AZ_OK;
 }
 
@@ -966,7 +967,7 @@ extern "C" int az_net_evaluate_keys(az_engine* e, const uint64_t* keys, int32_t 
 static int ec_empty(az_engine* e, bool wipe) {
   if (!e->d_ec) return AZ_OK;
   AZCHK(sync_all(e));
-  if (wipe) HIPCHK(hipMemsetAsync(e->d_ec, 0, sizeof(ECEnt) * ((size_t)e->ec_mask + 1), e->stream));
+  if (wipe) HIPCHK(hipMemsetAsync(e->d_ec, 0, sizeof(ECEnt) * e->ec_entries, e->stream));
   HIPCHK(hipMemsetAsync(e->d_ec_claim, 0xff, sizeof(int) * 2 * (size_t)e->v.G, e->stream));   // no slot holds an entry any more
   HIPCHK(hipStreamSynchronize(e->stream));
   if (wipe) e->ec_seq = 0;

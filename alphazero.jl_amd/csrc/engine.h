@@ -160,7 +160,7 @@ struct az_engine {
   // d_perm_prev [G][2] totals at the last move step)
   int* d_perm = nullptr; long long* d_perm_prev = nullptr;
   // evaluation cache (tree.h ECEnt): one table per engine = per network; az_net_set_params empties it
-  ECEnt* d_ec = nullptr; uint32_t ec_mask = 0; uint32_t ec_seq = 0; int* d_ec_claim = nullptr; float* d_Phit = nullptr; float* d_Vhit = nullptr;
+  ECEnt* d_ec = nullptr; size_t ec_entries = 0; uint32_t ec_seq = 0; int* d_ec_claim = nullptr; float* d_Phit = nullptr; float* d_Vhit = nullptr;
   size_t stat_words = 0; std::vector<long long> h_stat;   // per-workgroup statistics accumulators of k_tree (DView::stat), summed on request
   std::vector<void*> net_allocs;   // device copies of the packed network (replaced by az_net_set_params)
   // network

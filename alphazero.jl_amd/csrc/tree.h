@@ -28,6 +28,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "../../include/az_numerics.h"
+#include "eval_cache_rule.h"
 #include "../../include/azhip.h"
 #include "games.h"
 
@@ -76,7 +77,11 @@ static_assert(sizeof(SlotRec) == 64, "slot record");
 // own (src/simulations.jl:23-38, src/networks/network.jl:308-315); a test-mode evaluation is a pure function of the state and every
 // tower form gives the same bits (tests/test_net.py), so an answer that was computed once -- for another slot, in an earlier wave --
 // IS the answer: the records of a phase do not change (tests/test_eval_cache_gpu.py), the network evaluates each state once while
-// the entry lives.  Direct-mapped, 64-byte entries, RAW oracle output (prior_temperature is applied by the slot that stores the node).
+// the entry lives.  RAW oracle output (prior_temperature is applied by the slot that stores the node).
+// Two-way sets of 64-byte entries (eval_cache_rule.h holds the rules: set of a state, hit predicate, which way a new answer may
+// take, the table's size): entries 2 set and 2 set + 1 are the two halves of one 128-byte line, a look reads both ways in ONE round
+// of loads and the first way that answers wins; a state that finds no answer claims ec_pick_victim's way.  Hits store nothing, so
+// two answered ways are replaced oldest claim first.
 //   meta = seq << 2 | state:  0 empty;  EC_PENDING claimed by the slot that sent the state to the network (launch seq of the claim);
 //          EC_FILLING its answer is being written (exclusive: taken by CAS);  EC_READY answered.  seq makes every value of meta
 //          unique per claim.
@@ -89,12 +94,12 @@ static_assert(sizeof(SlotRec) == 64, "slot record");
 // evict concurrently in the same launch -- the idiom of k_tower16s' exchange.
 struct alignas(64) ECEnt { unsigned long long ka, kb; float P[AZ_MAX_ACTIONS]; float V; uint32_t cs; uint32_t meta; };
 static_assert(sizeof(ECEnt) == 64, "evaluation cache entry");
-enum { EC_EMPTY = 0, EC_PENDING = 1, EC_READY = 2, EC_FILLING = 3, EC_STALE_AFTER = 64 };
+static_assert(sizeof(ECEnt) == EC_ENTRY_BYTES, "eval_cache_rule.h sizes the table in entries of this size");
 
 struct DView {
   int G, cap_nodes, ht_size, max_depth, max_moves;
-  ECEnt* ec;              // evaluation cache [ec_mask + 1] or NULL (off)
-  uint32_t ec_mask, ec_seq;   // ec_seq: number of this k_tree launch (any slot group of the engine), > 0
+  ECEnt* ec;              // evaluation cache [2 (ec_set_mask + 1)] or NULL (off): the ways of set s are entries 2 s and 2 s + 1
+  uint32_t ec_set_mask, ec_seq;   // ec_seq: number of this k_tree launch (any slot group of the engine), > 0
   uint32_t ec_floor;          // entries whose claim number is <= ec_floor are EMPTY: az_net_set_params empties the table by raising the floor (a 1 GB memset per weight update before)
   int* ec_claim;          // [G][2] cache entry the slot's pending leaf claimed (its answer goes there when the leaf is expanded; -1 = none) and the meta value of the claim
   int* needy_host;        // host-mapped word: the slots this group's previous wave launch left to the background search (free-running; wave_net_f's choice between the paired tower's two register budgets), or NULL
@@ -287,15 +292,6 @@ __device__ __forceinline__ uint32_t ec_term(float p, int lane) {    // a lane's 
   const uint32_t b = __float_as_uint(p), r = (uint32_t)(5 * lane + 1) & 31u;
   return (b << r) | (b >> ((32u - r) & 31u));
 }
-__device__ __forceinline__ uint32_t ec_checksum(uint32_t px, unsigned long long ka, unsigned long long kb, float V, uint32_t ready_meta) {
-  unsigned long long h = az_hash_key(ka, kb);
-  h = az_mix64(h ^ (((unsigned long long)px << 32) | (unsigned long long)__float_as_uint(V)));
-  h = az_mix64(h + (unsigned long long)ready_meta);
-  return (uint32_t)(h >> 32) ^ (uint32_t)h;
-}
-__device__ __forceinline__ uint32_t ec_index(unsigned long long ka, unsigned long long kb, uint32_t mask) {
-  return (uint32_t)(az_hash_key(ka, kb) >> 17) & mask;              // other bits than the slot table's position (low) -- and than its tag where the mask allows
-}
 
 // ---- Dict lookup: haskey(env.tree, state) (src/mcts.jl:165-174) ---------------------------
 // Returns the node index or -1; *ins receives the table position a new entry would take.
@@ -478,7 +474,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(160))) k_t
           const uint32_t px = group_xor<L>(inrec ? ec_term(Praw, lane) : 0u);
           if (got) {
             if (inrec) ec_stf(&ent->P[lane], Praw);
-            if (lane == 0) { ec_stf(&ent->V, Vans); ec_st32(&ent->cs, ec_checksum(px, lenv.a, lenv.b, Vans, ready)); }
+            if (lane == 0) { ec_stf(&ent->V, Vans); ec_st32(&ent->cs, ec_checksum(px, az_hash_key(lenv.a, lenv.b), Vans, ready)); }
             __builtin_amdgcn_s_waitcnt(0);                           // every lane's stores have been performed ...
             if (lane == 0) ec_st32(&ent->meta, ready);              // ... before the value that lets readers in
           }
@@ -652,29 +648,34 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(160))) k_t
       if (kind == LEAF_NEW) {
         n_evl += 1;
         if (v.ec) {
-          // oracle(state): has the engine evaluated this state before (for another slot, in an earlier wave)?  One look at the entry.
-          const uint32_t ci = ec_index(env.a, env.b, v.ec_mask);
-          ECEnt* const ent = v.ec + ci;
-          const uint32_t m1 = ec_ld32(&ent->meta);
-          const unsigned long long ka = ec_ld64(&ent->ka), kb = ec_ld64(&ent->kb);
-          const float pl = inrec ? ec_ldf(&ent->P[lane]) : 0.f;
-          const float vv = ec_ldf(&ent->V);
-          const uint32_t cs = ec_ld32(&ent->cs);
-          const uint32_t px = group_xor<L>(inrec ? ec_term(pl, lane) : 0u);
-          const bool okc = (m1 & 3u) == EC_READY && (m1 >> 2) > v.ec_floor && ka == env.a && kb == env.b && cs == ec_checksum(px, ka, kb, vv, m1);
-          ishit = group_bcast0<L>(okc ? 1 : 0, lane) != 0;          // lane 0's verdict (its checksum covers every lane's prior)
-          if (ishit) { Pans = inrec ? pl : 0.f; Vans = vv; n_hit += 1; }   // no network for this leaf
+          // oracle(state): has the engine evaluated this state before (for another slot, in an earlier wave)?  One look at the
+          // state's set: both ways -- the two halves of one 128-byte line -- in ONE round of loads, the first way that answers wins.
+          const unsigned long long hk = az_hash_key(env.a, env.b);
+          const uint32_t ci = 2u * ec_set_of_hash(hk, v.ec_set_mask);
+          ECEnt* const e0 = v.ec + ci;
+          ECEnt* const e1 = e0 + 1;
+          const uint32_t m0 = ec_ld32(&e0->meta), m1 = ec_ld32(&e1->meta);
+          const unsigned long long ka0 = ec_ld64(&e0->ka), kb0 = ec_ld64(&e0->kb), ka1 = ec_ld64(&e1->ka), kb1 = ec_ld64(&e1->kb);
+          const float pl0 = inrec ? ec_ldf(&e0->P[lane]) : 0.f, pl1 = inrec ? ec_ldf(&e1->P[lane]) : 0.f;
+          const float vv0 = ec_ldf(&e0->V), vv1 = ec_ldf(&e1->V);
+          const uint32_t cs0 = ec_ld32(&e0->cs), cs1 = ec_ld32(&e1->cs);
+          const uint32_t px0 = group_xor<L>(inrec ? ec_term(pl0, lane) : 0u), px1 = group_xor<L>(inrec ? ec_term(pl1, lane) : 0u);
+          const int okw = ec_way_hit(m0, v.ec_floor, ka0, kb0, vv0, cs0, px0, env.a, env.b, hk) ? 1
+                        : ec_way_hit(m1, v.ec_floor, ka1, kb1, vv1, cs1, px1, env.a, env.b, hk) ? 2 : 0;
+          const int hitw = group_bcast0<L>(okw, lane);              // lane 0's verdict (its checksum covers every lane's prior): way + 1, 0 = no answer
+          ishit = hitw != 0;
+          if (ishit) { Pans = hitw == 1 ? pl0 : pl1; Vans = hitw == 1 ? vv0 : vv1; n_hit += 1; }   // no network for this leaf (pl = 0 outside the record)
           else {
-            // the state goes to the network; its answer goes into the cache if the entry can be taken: empty, answered (the older
-            // answer makes room), or a claim so old that its slot has gone away (a phase that ended, a retired slot).  Launches of
-            // other slot groups run side by side and may carry a HIGHER number than this one: a claim "from the future" is fresh
-            // (signed age).
+            // the state goes to the network; its answer goes into the cache if a way can be taken (ec_pick_victim): empty, a claim
+            // so old that its slot has gone away (a phase that ended, a retired slot), or answered -- the older answer makes room.
+            // The loser of a race for a way goes without a claim: it does not try the other way.
             claim = -1; cmeta = 0;
             if (lane == 0) {
-              const int32_t age = (int32_t)(v.ec_seq - (m1 >> 2));
-              if (m1 == 0u || (m1 & 3u) == EC_READY || age > (int32_t)EC_STALE_AFTER || (m1 >> 2) <= v.ec_floor) {
+              const int w = ec_pick_victim(m0, m1, ka0 == env.a && kb0 == env.b, ka1 == env.a && kb1 == env.b, v.ec_seq, v.ec_floor);
+              if (w >= 0) {
+                ECEnt* const ent = w ? e1 : e0;
                 const uint32_t mine = (v.ec_seq << 2) | EC_PENDING;
-                if (ec_cas(&ent->meta, m1, mine)) { ec_st64(&ent->ka, env.a); ec_st64(&ent->kb, env.b); claim = (int)ci; cmeta = mine; }
+                if (ec_cas(&ent->meta, w ? m1 : m0, mine)) { ec_st64(&ent->ka, env.a); ec_st64(&ent->kb, env.b); claim = (int)ci + w; cmeta = mine; }
               }
             }
           }
